@@ -12,10 +12,13 @@ inside the library (typlonk_msm_g1_sharded_devptr): total work is fixed, so scal
           bucket set) that is 13*m bucket additions + 2*2^19 additions of the row/column bucket reduction
           = 14.7 M; without tables (--tables none, c = 16) W*m + 2*W*2^(c-1) + c*(W-1) = 17.8 M.  For N > 1 the
           numerator stays the 1-GPU count (total work of the job), so the value moves only with time.
-Besides the contract line it reports msm_terms_per_s, the NTT (2^20) time with its algorithmic GB/s and its
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the contract line with
+msm_terms_per_s next to it; `--dump-outputs DIR` also writes the commitment of the last timed step to DIR.  With --full
+it reports as well the stage split of the MSM, nine MSMs in one call, the NTT (2^20) time with its algorithmic GB/s and its
 Fr-multiplication rate against the instruction-count ceiling, the kernel sequence of one prove() (13 MSM + 15 NTT,
 plonk/src/proof.rs:96-194) in ms, a real prove(), the roofline of the dominant kernel (bucket accumulation) from HIP
-events on the library's stream, and the CPU baselines of BASELINE.md section 3 timed on this box's host cores.
+events on the library's stream, the CPU baselines of BASELINE.md section 3 timed on this box's host cores and the parity
+checks against the oracle that withhold the number when they fail.
 
 The contract line is printed from a `finally`: a failure in any later section (or in the multi-GPU teardown) is
 recorded in the line (`*_error` keys) instead of losing the numbers already measured.
@@ -346,11 +349,17 @@ def main() -> None:
     ap.add_argument("--cpu-full", action="store_true",
                     help="the long CPU legs of BASELINE.md section 3 as well: reference-faithful MSM on the full vector "
                          "(minutes on one core), schoolbook quotient at 2^12")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: MSM stage split and roofline, batched MSMs, NTT, prove() (also at "
+                         "2^22), CPU baselines and parity against the oracle; for N > 1 the sharded prove() and the scaling "
+                         "context.  Off: the timed MSM steps and the contract line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the commitment the last timed step returned to DIR/*.npy (float64)")
     ap.add_argument("--msm-only", action="store_true",
-                    help="only the timed MSM loop and its roofline (the command the rocprofv3 summaries "
+                    help="with --full: only the timed MSM loop and its roofline (the command the rocprofv3 summaries "
                          "profiles/r0x_kernel_stats_bench_msm_only.csv are taken from)")
     ap.add_argument("--no-prove-2-22", action="store_true",
-                    help="skip the extra 2^22-row prove() (BASELINE config 5's size) the default 2^20 run reports next to the headline")
+                    help="skip the extra 2^22-row prove() (BASELINE config 5's size) a --full 2^20 run reports next to the headline")
     ap.add_argument("--no-sharded-prove", action="store_true",
                     help="N > 1: skip the extra measurement of prove() with every MSM sharded over the ranks")
     ap.add_argument("--tables", default="auto",
@@ -425,16 +434,27 @@ def main() -> None:
         sys.exit(code)
 
 
+def dump_outputs(out_dir: str, out_xy, out_inf) -> None:
+    """--dump-outputs: what the timed path returned to its caller in the last timed step -- the commitment as
+    typlonk_msm_g1_devptr hands it over (affine x, y as 12 little-endian u64 Montgomery limbs, and the identity flag).
+    The 96 bytes of x, y are written one float64 per byte (exact; a one-bit change moves a value by at least 1/255)."""
+    os.makedirs(out_dir, exist_ok=True)
+    xy = np.ascontiguousarray(np.asarray(out_xy, dtype=np.uint64).reshape(12))
+    np.save(os.path.join(out_dir, "commit_xy_bytes.npy"), xy.view(np.uint8).astype(np.float64))
+    np.save(os.path.join(out_dir, "commit_inf.npy"), np.array([float(out_inf)], dtype=np.float64))
+
+
 def run(args, rank, world, backend, dev_index, device, result, state) -> None:
     log_n = args.log_n
     n = 1 << log_n
     srs_len = n + 3  # Srs::from_secret(s, gates) has gates + 3 points (kzg/src/srs.rs:31)
     ctx = typlonk_amd.Context(dev_index)
     state["ctx"] = ctx
-    # the timed region brackets ONLY the dominant kernel with HIP events (level 2: the roofline's `achieved` is measured
-    # live over the timed steps); the full stage split is collected afterwards, untimed -- bracketing every stage costs
-    # ~0.1 ms of event traffic per MSM, which a caller never pays
-    ctx.set_profiling(2)
+    # --full: the timed region brackets ONLY the dominant kernel with HIP events (level 2: the roofline's `achieved` is
+    # measured live over the timed steps); the full stage split is collected afterwards, untimed -- bracketing every stage
+    # costs ~0.1 ms of event traffic per MSM, which a caller never pays.  A plain run brackets nothing.
+    if args.full:
+        ctx.set_profiling(2)
     secret = fr_mont_limbs(2)  # the reference's test secret (kzg/src/lib.rs:97)
     sh = ShardedMsm(ctx, srs_len, rank, world, device if backend == "nccl" else torch.device("cpu"))
     sh.generate_srs(secret)
@@ -497,15 +517,31 @@ def run(args, rank, world, backend, dev_index, device, result, state) -> None:
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out_xy, out_inf = step()
-        for name, ms in ctx.profile():
-            stage_ms[name] = stage_ms.get(name, 0.0) + ms
-            accum_launches += name == "msm_accum"
+        if args.full:
+            for name, ms in ctx.profile():
+                stage_ms[name] = stage_ms.get(name, 0.0) + ms
+                accum_launches += name == "msm_accum"
     sync_all()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_xy, out_inf)
+    Wl = table_windows(tables_c) if tables_c else ctx.msm_plan(max(m_local, 1))[1]
+    result.update({
+        "value": ops_1gpu * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
+        "config": {"workload": f"2^{log_n}-term BLS12-381 G1 MSM (KZG commit of a 2^{log_n}-row polynomial), "
+                               f"SRS [s^i]G with s=2, {srs_len} points", "window_bits": c1, "windows": W1,
+                   "parallelism": (f"index-sharded x{world}, RCCL all-gather + fold inside the library" if sh.native else
+                                   f"index-sharded x{world} + all-gather fold ({backend})") if world > 1 else "single GPU",
+                   "fixed_base_tables": f"c={tables_c}, {Wl} tables per rank" if tables_c else "none"},
+        "msm_terms_per_s": n * args.steps / dt,
+    })
+    if not args.full:
+        return
+    # ---- --full from here on: everything the contract line does not need
     stage_ms = {k: v / args.steps for k, v in stage_ms.items()}
     # the full stage split (sort / accumulate / reduce): a few untimed steps with every stage bracketed
     ctx.set_profiling(1)
@@ -519,17 +555,7 @@ def run(args, rank, world, backend, dev_index, device, result, state) -> None:
             stage_ms[name] = ms
     stage_ms_note = ("msm_accum: HIP events over the timed steps; the other stages: five untimed steps with every stage bracketed "
                      "(typlonk_set_profiling 2 / 1)")
-    Wl = table_windows(tables_c) if tables_c else ctx.msm_plan(max(m_local, 1))[1]
-    result.update({
-        "value": ops_1gpu * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
-        "config": {"workload": f"2^{log_n}-term BLS12-381 G1 MSM (KZG commit of a 2^{log_n}-row polynomial), "
-                               f"SRS [s^i]G with s=2, {srs_len} points", "window_bits": c1, "windows": W1,
-                   "parallelism": (f"index-sharded x{world}, RCCL all-gather + fold inside the library" if sh.native else
-                                   f"index-sharded x{world} + all-gather fold ({backend})") if world > 1 else "single GPU",
-                   "fixed_base_tables": f"c={tables_c}, {Wl} tables per rank" if tables_c else "none"},
-        "msm_terms_per_s": n * args.steps / dt,
-        "msm_stage_ms": stage_ms, "msm_stage_ms_note": stage_ms_note,
-    })
+    result.update({"msm_stage_ms": stage_ms, "msm_stage_ms_note": stage_ms_note})
 
     # ---- a prover round's worth of MSMs in one call (typlonk_msm_g1_batch_devptr / _sharded_batch_devptr): sort and
     # reduction of one MSM hide behind the accumulation of another, and N ranks exchange all nine sums at once.  Not the
@@ -804,7 +830,7 @@ def bench_prove_2_22(dev_index, result) -> None:
     quotient on the 2^24 coset, in the reference's proof shape through the one-call native prover and with batched
     openings; its own context and SRS (tables c = 20), released before the CPU legs.  r(zeta) = 0 is checked here; the
     proofs at this size are compared element for element with the single-rank / eight-rank / CPU provers by the test suite
-    (tests/test_gpu_prove.py, tests/test_gpu_dist.py) and by `bench.py --log-n 22`."""
+    (tests/test_gpu_prove.py, tests/test_gpu_dist.py) and by `bench.py --full --log-n 22`."""
     from typlonk_amd.circuits import SquaringChain
 
     log_n = 22

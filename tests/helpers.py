@@ -2,6 +2,7 @@
 from __future__ import annotations
 import ctypes
 import os
+import re
 import sys
 import numpy as np
 
@@ -52,3 +53,31 @@ def load_golden(name):
 
 def hex_pt(p):
     return None if p is None else (int(p[0], 16), int(p[1], 16))
+
+
+def patch_preimages(path):
+    """a `git diff` patch -> {file: {"blob": abbreviated pre-image blob id, "hunks": [(start, length, lines)]}}: what each
+    hunk expects to find in the file it patches (its context and removed lines, in order, from line `start` on)"""
+    files, cur, old_rem, new_rem = {}, None, 0, 0
+    with open(path, encoding="utf-8") as f:
+        text = f.read()
+    for line in text.split("\n")[:-1]:
+        if old_rem or new_rem:                       # inside a hunk body
+            tag, body = (line[:1] or " "), line[1:]
+            if tag == "\\":                          # "\ No newline at end of file"
+                continue
+            if tag in " -":
+                cur["hunks"][-1][2].append(body)
+                old_rem -= 1
+            if tag in " +":
+                new_rem -= 1
+            continue
+        if line.startswith("diff --git "):
+            cur = files.setdefault(line.split(" b/", 1)[1], {"blob": None, "hunks": []})
+        elif line.startswith("index "):
+            cur["blob"] = line.split()[1].split("..")[0]
+        elif line.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            old_rem, new_rem = int(m.group(2) or 1), int(m.group(4) or 1)
+            cur["hunks"].append((int(m.group(1)), old_rem, []))
+    return files

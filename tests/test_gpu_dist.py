@@ -34,7 +34,7 @@ def _run(env_extra, nproc, args):
 
 
 def test_two_ranks_sharded_msm_on_one_gpu():
-    d = _run({"TYPLONK_BENCH_BACKEND": "gloo"}, 2, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "18"])
+    d = _run({"TYPLONK_BENCH_BACKEND": "gloo"}, 2, ["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "18"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["metric"] == "msm_g1_adds_per_s"
     assert d["parity"]["full_commit_identity"] is True and d["value"] is not None
     assert "index-sharded x2" in d["config"]["parallelism"]
@@ -47,7 +47,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
     env = dict(os.environ, TYPLONK_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-n", "20", "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log-n", "20", "--steps", "3",
                         "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     out = [l for l in r.stdout.splitlines() if l.strip()]
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -68,8 +68,36 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
     assert exp["speedup"]["batched_msms"] > exp["speedup"]["one_msm"] > 1 and "shard_latency" in exp["source"]
 
 
+def test_plain_run_times_the_steps_and_dumps_the_commitment(tmp_path):
+    """`python bench.py --gpus 1` without --full: the contract line holds the headline and nothing measured besides it,
+    and --dump-outputs writes the commitment of the last timed step, which is [p(s)]G for the benchmark's own scalars
+    (the reference's identity, kzg/src/lib.rs:102-105) -- the same inputs on every run"""
+    import numpy as np
+
+    import bench
+    from oracle import coracle as CO
+
+    log_n = 16
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--log-n", str(log_n), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = [l for l in r.stdout.splitlines() if l.strip()]
+    assert r.returncode == 0 and out and out[-1].startswith('{"metric"'), r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads(out[-1])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and "error" not in d
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert key in d
+    for key in ("msm_stage_ms", "msm_batch", "roofline", "ntt", "prove_ms", "cpu_baseline", "parity"):
+        assert key not in d, key
+    sc = bench.synthetic_scalars(1 << log_n, 0x5EED0000 + log_n, bench.torch.device("cuda", 0))
+    exp_xy, exp_inf = CO.g1_mul_generator(CO.poly_eval(sc.cpu().numpy().view(np.uint64), bench.fr_mont_limbs(2)))
+    got_xy, got_inf = np.load(tmp_path / "commit_xy_bytes.npy"), np.load(tmp_path / "commit_inf.npy")
+    assert got_xy.dtype == np.float64 and got_inf.dtype == np.float64
+    assert (got_xy == np.ascontiguousarray(exp_xy, dtype=np.uint64).view(np.uint8).astype(np.float64)).all()
+    assert got_inf.tolist() == [float(exp_inf)]
+
+
 def test_one_rank_through_rccl_all_gather():
-    d = _run({"TYPLONK_FORCE_COLLECTIVE": "1"}, 1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16",
+    d = _run({"TYPLONK_FORCE_COLLECTIVE": "1"}, 1, ["--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16",
                                                     "--cpu-sample", "2048"])
     assert d["n_gpus"] == 1 and d["parity"]["sample_vs_oracle"] and d["parity"]["full_commit_identity"]
     assert d["prove_valid"] is True and d["rccl_world"] == 1 and "rccl" in d["exchange"]
@@ -95,7 +123,7 @@ def test_config4_eight_ranks_share_the_gpu_at_2_20():
     points and c = 17 tables).  bench.py's headline loop: the folded commitment equals [p(s)]G; the worker: the sharded
     proof -- both shapes -- equals the proof of one rank holding the whole SRS, element for element, r(zeta) = 0."""
     d = _run({"TYPLONK_BENCH_BACKEND": "gloo", "TYPLONK_BENCH_PG_TIMEOUT": "600"}, 8,
-             ["--gpus", "8", "--steps", "3", "--warmup", "1", "--log-n", "20"])
+             ["--full", "--gpus", "8", "--steps", "3", "--warmup", "1", "--log-n", "20"])
     assert d["n_gpus"] == 8 and d["parity"]["full_commit_identity"] is True and d["value"] is not None
     assert d["prove_valid"] is True and "prove_sharded_error" not in d and "error" not in d
     assert "c=17" in d["config"]["fixed_base_tables"]

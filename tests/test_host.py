@@ -525,18 +525,34 @@ def test_rust_ffi_mirror_is_generated_from_the_header_and_complete(built):
 
 
 def test_rust_patches_apply_to_the_reference(tmp_path):
-    """the two patches under integration/rust/patches apply cleanly (`git apply --check`) to a copy of the reference's
-    kzg / plonk crates -- where the reference tree exists (the development container; not on the GPU box)"""
-    import shutil
+    """the two patches under integration/rust/patches apply cleanly to the reference's kzg / plonk crates.  The reference
+    tree is pinned by tests/golden/patch_preimages.json (tests/golden/gen_patch_preimages.py: per touched file its git blob
+    id and line count, per hunk the SHA-256 of the reference's lines there): every patch names that blob as its pre-image,
+    every hunk's context and removed lines hash to the reference's lines at the hunk's position, and `git apply --check`
+    accepts each patch against files of the reference's length that hold exactly those lines there."""
+    import hashlib
     import subprocess
 
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "kzg")):
-        pytest.skip("no reference tree here")
-    for crate in ("kzg", "plonk"):
-        shutil.copytree(os.path.join(ref, crate), tmp_path / crate)
-    subprocess.run(["git", "init", "-q", "."], cwd=tmp_path, check=True)
+    from helpers import load_golden, patch_preimages
+
+    pinned = load_golden("patch_preimages.json")
     for p in ("0001-kzg-msm-on-hip.patch", "0002-plonk-prove-on-hip.patch"):
-        r = subprocess.run(["git", "apply", "--check", os.path.join(ROOT, "integration", "rust", "patches", p)],
-                           cwd=tmp_path, capture_output=True, text=True)
+        patch = os.path.join(ROOT, "integration", "rust", "patches", p)
+        files = patch_preimages(patch)
+        assert set(files) == set(pinned[p]), p
+        tree = tmp_path / p
+        for path, d in files.items():
+            ref = pinned[p][path]
+            assert ref["blob"].startswith(d["blob"]), f"{p}: {path} was cut against blob {d['blob']}, the reference holds {ref['blob']}"
+            assert [(h["start"], h["length"]) for h in ref["hunks"]] == [(s, n) for s, n, _ in d["hunks"]], f"{p}: {path}"
+            body = [f"@@ line {i + 1} of the reference's {path} @@" for i in range(ref["lines"])]
+            for (start, length, lines), h in zip(d["hunks"], ref["hunks"]):
+                assert len(lines) == length, f"{p}: {path} hunk at {start}"
+                assert hashlib.sha256("".join(l + "\n" for l in lines).encode("utf-8")).hexdigest() == h["sha256"], \
+                    f"{p}: {path} hunk at line {start} does not match the reference"
+                body[start - 1:start - 1 + length] = lines
+            (tree / path).parent.mkdir(parents=True, exist_ok=True)
+            (tree / path).write_text("".join(l + "\n" for l in body), encoding="utf-8")
+        subprocess.run(["git", "init", "-q", "."], cwd=tree, check=True)
+        r = subprocess.run(["git", "apply", "--check", patch], cwd=tree, capture_output=True, text=True)
         assert r.returncode == 0, p + ": " + r.stderr

@@ -6,10 +6,10 @@ timeout 1200 python3 -m pytest tests/test_gpu_msm.py tests/test_gpu_msm_shard.py
 tail -5 $O/pytest.log
 for rep in 1 2 3; do
   for t in 256 512; do
-  echo "== new L1=$t rep $rep"; TYPLONK_MSM_L1_THREADS=$t python3 bench.py --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"
+  echo "== new L1=$t rep $rep"; TYPLONK_MSM_L1_THREADS=$t python3 bench.py --full --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"
   echo "== batch new L1=$t rep $rep"; TYPLONK_MSM_L1_THREADS=$t REPS=10 python3 tools/msm_batch_loop.py 2>/dev/null | tail -1
   done
-  echo "== r5base rep $rep"; TYPLONK_LIB_PATH=tools/_ab/r5base/libtyplonk_hip.so python3 bench.py --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"
+  echo "== r5base rep $rep"; TYPLONK_LIB_PATH=tools/_ab/r5base/libtyplonk_hip.so python3 bench.py --full --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"
   echo "== batch r5base rep $rep"; TYPLONK_LIB_PATH=tools/_ab/r5base/libtyplonk_hip.so REPS=10 python3 tools/msm_batch_loop.py 2>/dev/null | tail -1
 done > $O/msm_ab.txt 2>&1
 cat $O/msm_ab.txt

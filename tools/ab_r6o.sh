@@ -8,6 +8,6 @@ TYPLONK_MSM_SORT_PRIO=$v REPS=16 rocprofv3 --kernel-trace --output-format csv -d
 echo "== TYPLONK_MSM_SORT_PRIO=$v"; python3 tools/msm_timeline.py $(find $O/trace$v -name "*kernel_trace.csv" | head -1) 10 2>&1 | tee $O/msm_timeline_$v.txt
 done
 find $O -name "*kernel_trace.csv" -size +4M -delete
-for rep in 1 2 3; do for v in 1 0; do echo "== PRIO=$v rep $rep"; TYPLONK_MSM_SORT_PRIO=$v python3 bench.py --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"; echo "== batch PRIO=$v"; TYPLONK_MSM_SORT_PRIO=$v REPS=10 python3 tools/msm_batch_loop.py 2>/dev/null | tail -1; done; done > $O/ab.txt 2>&1; cat $O/ab.txt
+for rep in 1 2 3; do for v in 1 0; do echo "== PRIO=$v rep $rep"; TYPLONK_MSM_SORT_PRIO=$v python3 bench.py --full --msm-only --steps 30 --warmup 5 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['msm_stage_ms'])"; echo "== batch PRIO=$v"; TYPLONK_MSM_SORT_PRIO=$v REPS=10 python3 tools/msm_batch_loop.py 2>/dev/null | tail -1; done; done > $O/ab.txt 2>&1; cat $O/ab.txt
 for rep in 1 2 3; do for v in 1 0; do echo "== prove PRIO=$v"; TYPLONK_MSM_SORT_PRIO=$v python3 tools/prove_rounds.py 2>/dev/null | tail -2; done; done > $O/prove_ab.txt 2>&1; cat $O/prove_ab.txt
 for v in 1 0; do echo "== 2^22 prove PRIO=$v"; LOG_N=22 TYPLONK_MSM_SORT_PRIO=$v python3 tools/prove_rounds.py 2>/dev/null | tail -2; done > $O/prove_ab_22.txt 2>&1; cat $O/prove_ab_22.txt

@@ -4,8 +4,8 @@
 # proof, and a proof timeline with its accumulation-free stretches.
 export TMPDIR=/tmp
 O=gpurun_out/r5p; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_msm -- python3 bench.py --steps 20 --warmup 5 --msm-only > $O/bench_msm_only.json 2> $O/bench_msm.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_msm -- python3 bench.py --full --steps 20 --warmup 5 --msm-only > $O/bench_msm_only.json 2> $O/bench_msm.err
 REPS=10 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 tools/msm_loop.py > $O/pmc_fetch.log 2>&1
 REPS=10 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 tools/msm_loop.py > $O/pmc_write.log 2>&1
 REPS=10 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq -- python3 tools/msm_loop.py > $O/pmc_sq.log 2>&1
@@ -43,7 +43,7 @@ python3 tools/pmc_sq_summary.py $O/pmc_sq > $O/pmc_sq_msm.json 2>/dev/null
 find $O -name "*counter_collection.csv" -size +2M -delete
 ls -la $O | head -40; tail -c 600 $O/bench_full.json; cat $O/shard_latency.jsonl; tail -25 $O/prove_timeline.txt; cat $O/prove_rounds.txt | tail -3
 # round 5 additions: the 2^22 configuration, the inversion pricing + affine-round A/B, the SRS set-up cost
-python3 bench.py --log-n 22 --cpu-sample 8192 --steps 10 --warmup 3 > $O/bench_2_22.json 2> $O/bench_2_22.err
+python3 bench.py --full --log-n 22 --cpu-sample 8192 --steps 10 --warmup 3 > $O/bench_2_22.json 2> $O/bench_2_22.err
 LOG_N=22 python3 tools/prove_rounds.py 2>/dev/null | tail -2 > $O/prove_rounds_2_22.txt
 ./tools/ubench5 > $O/ubench_inversion.txt 2>&1
 python3 tools/srs_setup_bench.py > $O/srs_setup.jsonl 2>/dev/null

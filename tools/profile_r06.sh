@@ -3,8 +3,8 @@
 # run, no other trace domains), NTT stats single and batched, the shard-sized MSM, a proof timeline, the 2^22 configuration.
 export TMPDIR=/tmp
 O=gpurun_out/r6p; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_msm -- python3 bench.py --steps 20 --warmup 5 --msm-only > $O/bench_msm_only.json 2> $O/bench_msm.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_msm -- python3 bench.py --full --steps 20 --warmup 5 --msm-only > $O/bench_msm_only.json 2> $O/bench_msm.err
 python3 tools/msm_timeline.py $(find $O/bench_msm -name "*kernel_trace.csv" | head -1) 15 > $O/msm_2_20_timeline.txt 2>&1
 REPS=10 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 tools/msm_loop.py > $O/pmc_fetch.log 2>&1
 REPS=10 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 tools/msm_loop.py > $O/pmc_write.log 2>&1
@@ -47,7 +47,7 @@ F=$(find $O/pmc_fetch -name "*counter_collection.csv" | head -1); W=$(find $O/pm
 python3 tools/pmc_summary.py $F $W $O/pmc_summary.json > /dev/null
 python3 tools/pmc_sq_summary.py $O/pmc_sq > $O/pmc_sq_msm.json 2>/dev/null
 find $O -name "*counter_collection.csv" -size +2M -delete
-python3 bench.py --log-n 22 --cpu-sample 8192 --steps 10 --warmup 3 > $O/bench_2_22.json 2> $O/bench_2_22.err
+python3 bench.py --full --log-n 22 --cpu-sample 8192 --steps 10 --warmup 3 > $O/bench_2_22.json 2> $O/bench_2_22.err
 python3 tools/srs_setup_bench.py > $O/srs_setup.jsonl 2>/dev/null
 ls -la $O | head -50; tail -c 1500 $O/bench_full.json; cat $O/shard_latency.jsonl; tail -25 $O/prove_timeline.txt; cat $O/prove_rounds.txt | tail -3; cat $O/prove_rounds_2_22.txt; cat $O/msm_2_20_timeline.txt; cat $O/pmc_sq_ntt_batched.json
 # the host-memory seams (the reference's commit() and prove() as a host caller sees them)

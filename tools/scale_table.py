@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Arrival day of a multi-GPU box: read the contract lines of `python bench.py --gpus N` for N = 1, 2, 4, 8 and print, for
+"""Arrival day of a multi-GPU box: read the contract lines of `python bench.py --full --gpus N` for N = 1, 2, 4, 8 and print, for
 the three modes (one stand-alone MSM per step / nine MSMs in flight / the sharded prove()), what was MEASURED next to what
 DESIGN.md section 7 projected from one GPU (`expected_from_1gpu`), plus the size of the RCCL communicator the library held
 (`rccl_world`: N means the exchange ran inside the library over real RCCL).
 
 usage:  python tools/scale_table.py line1.json line2.json ...     (files holding bench.py's last stdout line, any order)
-        python tools/scale_table.py --run                         (runs bench.py --gpus 1, 2, 4, 8 itself, one after the other;
+        python tools/scale_table.py --run                         (runs bench.py --full --gpus 1, 2, 4, 8 itself, one after the other;
                                                                    each is a child process -- nothing here touches the GPU)
 Speed-ups are this run's N-GPU time into this run's 1-GPU time when a 1-GPU line is given, else into the line's own
 `one_gpu_same_run` (rank 0's unsharded MSM measured in the same process)."""
@@ -35,9 +35,9 @@ def load(paths):
 def run_all():
     lines = {}
     for n in (1, 2, 4, 8):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)], capture_output=True, text=True, cwd=ROOT)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n)], capture_output=True, text=True, cwd=ROOT)
         if r.returncode != 0:
-            print(f"bench.py --gpus {n} failed (rc {r.returncode}): {r.stderr[-400:]}", file=sys.stderr)
+            print(f"bench.py --full --gpus {n} failed (rc {r.returncode}): {r.stderr[-400:]}", file=sys.stderr)
             continue
         lines[n] = last_json_line(r.stdout)
     return lines
