@@ -108,7 +108,9 @@ def build_hip_test_hooks(force: bool = False) -> str:
     obj = os.path.join(out_dir, "comm.o")
     base_obj = os.path.join(CSRC, "_obj")
     objs = [obj if u == "comm.hip" else os.path.join(base_obj, u.replace(".hip", ".o")) for u in HIP_UNITS]
-    if force or _stale(obj, [src] + hdrs):
+    # comm.o is linked with the base objects, so it must be compiled from the same headers (typlonk_ctx's layout): one older
+    # than the base library may come from other sources with newer mtimes, and is rebuilt
+    if force or _stale(obj, [src] + hdrs + [LIB]):
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DTYPLONK_TEST_HOOKS", "-c", src, "-o", obj])
     if force or _stale(lib, objs):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib])

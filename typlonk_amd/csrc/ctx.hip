@@ -91,14 +91,8 @@ int typlonk_init(typlonk_ctx** out, int device_ordinal) {
         return TYPLONK_ERR_HIP;
     }
     ctx->stream = ctx->own_stream;
-    if (const char* e = getenv("TYPLONK_MSM_REDUCE")) {
-        ctx->msm_rc4 = (strcmp(e, "rc4") == 0);
-        ctx->msm_rc2_force = (strcmp(e, "rc2") == 0);
-    }
-    if (const char* e = getenv("TYPLONK_MSM_RC2_LOGW")) ctx->msm_rc2_logw = std::max(8, std::min(atoi(e), 14));
+    if (const char* e = getenv("TYPLONK_MSM_REDUCE")) ctx->msm_rc4 = (strcmp(e, "rc4") == 0);
     if (const char* e = getenv("TYPLONK_MSM_SCATTER")) ctx->msm_scatter_staged = strcmp(e, "direct") != 0;
-    if (const char* e = getenv("TYPLONK_MSM_L1_THREADS")) ctx->msm_l1_threads = atoi(e) == 256 ? 256 : (atoi(e) == 512 ? 512 : 0);
-    if (const char* e = getenv("TYPLONK_MSM_SORT_PRIO")) ctx->msm_sort_prio = atoi(e) != 0;
     if (const char* e = getenv("TYPLONK_MSM_CHAIN")) ctx->msm_chain = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("TYPLONK_MSM_LANES")) {
         const int l = atoi(e);
@@ -106,10 +100,6 @@ int typlonk_init(typlonk_ctx** out, int device_ordinal) {
     }
     if (const char* e = getenv("TYPLONK_MSM_INFLIGHT")) ctx->msm_inflight = atoi(e);
     if (const char* e = getenv("TYPLONK_MSM_CHUNKS")) ctx->msm_chunks = std::max(0, std::min(atoi(e), MSM_MAX_CHUNKS));
-    if (const char* e = getenv("TYPLONK_MSM_FIRST_PCT")) ctx->msm_first_pct = std::max(0, std::min(atoi(e), 99));
-    if (const char* e = getenv("TYPLONK_PROVER_PIPE")) ctx->prover_pipe = atoi(e) != 0;
-    if (const char* e = getenv("TYPLONK_PROVER_FETCH")) ctx->prover_pinned_slots = atoi(e) != 0;
-    if (const char* e = getenv("TYPLONK_PROVER_NTT_BATCH")) ctx->prover_ntt_batch = std::max(0, std::min(atoi(e), 3));
     if (const char* e = getenv("TYPLONK_NTT_FR30")) ctx->ntt_fr30 = std::max(0, std::min(atoi(e), 2));
     if (const char* e = getenv("TYPLONK_NTT_BIG")) ctx->ntt_big = std::max(0, std::min(atoi(e), 2));
     *out = ctx;

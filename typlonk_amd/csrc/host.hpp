@@ -117,21 +117,16 @@ struct typlonk_buf {
     size_t n = 0;
 };
 
-// Environment switches read by typlonk_init (the ones the parity tests parametrise; every combination gives the same bits):
+// Environment switches read by typlonk_init.  Each forces one of the forms the default policy itself picks by shape, so
+// the parity tests can reach every form at every shape (every combination gives the same bits):
 //   TYPLONK_MSM_INFLIGHT  MSMs of a batch in flight at once (1..4; default: by SRS length, MsmQueue)
 //   TYPLONK_MSM_CHAIN     0 | 1: the lanes of a batch run free / chain their accumulations (default: by term count)
 //   TYPLONK_MSM_CHUNKS    chunks of a stand-alone MSM (0 = by length)
 //   TYPLONK_MSM_LANES     lanes per bucket of the accumulation (1, 2, 4, 8, 16; 0 = by bucket load)
 //   TYPLONK_MSM_SCATTER   staged | direct: level 1 of the bucket sort stages its runs in the LDS / writes entry by entry
-//   TYPLONK_MSM_L1_THREADS 256 | 512: workgroup size of the sort's level-1 passes (default: by whether the sort runs beside an accumulation)
-//   TYPLONK_MSM_SORT_PRIO 0 | 1: raised wavefront priority + 256-thread level 1 for the sorts of a stand-alone MSM's overlapped chunks
-//   TYPLONK_MSM_REDUCE    rc2 | rc4: force the two- / four-launch row/column bucket reduction
+//   TYPLONK_MSM_REDUCE    rc4: always the four-launch row/column bucket reduction (default: two launches for small bucket sets)
 //   TYPLONK_NTT_FR30      0 | 1 | 2: the 9 x 30-bit butterflies never / where they measure faster / always
 //   TYPLONK_NTT_BIG       0 | 1 | 2: the two-pass 2^20 plan (4096-element tiles) never / where it measures faster / always
-//   TYPLONK_PROVER_NTT_BATCH 0 | 1 | 2 | 3: round 1 transforms its columns one by one (each commitment submitted as soon as its
-//                         polynomial exists) / as one batched transform per group (ntt_run_batch) / the first alone, the rest
-//                         batched / interpolations one by one, coset extensions batched
-//   TYPLONK_PROVER_PIPE   0 | 1: round 3's nine commitments queued as in rounds 1-4 / behind one fence (prover_round3_core)
 // (TYPLONK_RCCL_LIB, read by comm.hip, names the RCCL library to load.)
 struct typlonk_ctx {
     int device = 0;
@@ -167,29 +162,12 @@ struct typlonk_ctx {
     // 0.419 -> 0.464 ms per MSM -- so the switch sits below the shard size; from 2^19 on the chain is never worse and
     // 2^20 needs it.  -1 = by term count (MSM_CHAIN_MIN_TERMS), 0 / 1 = TYPLONK_MSM_CHAIN.
     int msm_chain = -1;
-    int prover_ntt_batch = 0;      // TYPLONK_PROVER_NTT_BATCH: round 1's interpolations / coset extensions 0 = one by one (each commitment
-                                   // submitted as soon as its polynomial exists), 1 = one batched transform per group, 2 = the first
-                                   // column alone, the rest batched, 3 = interpolations one by one, extensions batched.  Measured
-                                   // (profiles/r06_ab_prover_ntt_batch.txt): inside a proof the batched forms LOSE 0.3-0.5 ms at 2^20 --
-                                   // they delay a commitment's start by the other columns' transforms, and the transforms were
-                                   // already hidden beside the commitments' sorts; the batched entry point pays where nothing
-                                   // runs beside it (typlonk_circuit_load, a caller's interpolate groups)
-    bool prover_pipe = true;       // TYPLONK_PROVER_PIPE (A/B switch of the round-5 queueing fix, prover_round3_core)
-    bool prover_pinned_slots = true;  // the prover's evaluation slots in pinned host memory (TYPLONK_PROVER_FETCH=0: device slots + copy)
     tyh::Fr* eval_slots_host = nullptr;  // 16 pinned, device-visible result slots (prover_ops_tmp)
     int msm_chunks = 0;            // chunks of a stand-alone MSM (0 = choose by length)
-    int msm_first_pct = 0;         // share of the terms in the first chunk, per cent (0 = equal chunks)
     int msm_lanes = 0;             // lanes per bucket of the accumulation (0 = choose by bucket load)
     bool msm_scatter_staged = true;  // TYPLONK_MSM_SCATTER=direct: level 1 of the bucket sort writes every entry straight to global
                                    // memory (the rounds 1-5 form, the A/B reference) instead of staging runs in the LDS
-    int msm_l1_threads = 0;        // TYPLONK_MSM_L1_THREADS = 256 | 512: threads per workgroup of the sort's level-1 passes (staged form);
-                                   // 0 = 512 for a sort that has the chip to itself (histogram 18.5 -> 14 us, scatter 49 -> 32 us per
-                                   // 2^19 terms), 256 for an overlapped chunk's (msm_enqueue)
-    bool msm_sort_prio = true;     // TYPLONK_MSM_SORT_PRIO=0: the overlapped chunks' sorts get neither the raised wavefront priority
-                                   // nor the 256-thread shape (the A/B reference)
     bool msm_rc4 = false;          // always the four-launch row/column reduction
-    bool msm_rc2_force = false;    // the two-launch form for every bucket-set size
-    int msm_rc2_logw = 10;         // log2 wavefronts of the two-launch form's first launch (TYPLONK_MSM_RC2_LOGW)
     // NTT
     tyh::DevBuf ntt_scratch, ntt_io, quot_ext, quot_tab, ops_tmp, prover_mem;
     bool prover_busy = false;  // one proof in flight per context (the arena above is shared)

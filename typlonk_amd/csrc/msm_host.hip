@@ -137,12 +137,9 @@ int msm_enqueue(typlonk_ctx* ctx, MsmWs& ws, hipStream_t stream, const SrsEntry&
     //  * scalars in HOST memory (typlonk_msm_g1): the first chunk's copy over PCIe is the exposed one, so it is 2^18 terms (8 MB)
     //    instead of 2^19 and there is one chunk more -- 2.73-2.75 -> 2.59-2.65 ms per 2^20-term commitment
     //    (profiles/r06_ab_host_scalar_path.txt, calls U and V); device-resident scalars keep equal chunks (an unequal first
-    //    chunk loses there: profiles/r06_ab_first_chunk_and_rc2.txt);
-    //  * TYPLONK_MSM_FIRST_PCT: that share of the terms (experiments).
+    //    chunk loses there: profiles/r06_ab_first_chunk_and_rc2.txt).
     size_t first = 0;
-    if (standalone && nch > 1 && ctx->msm_first_pct > 0 && ctx->msm_first_pct < 100) {
-        first = std::max<size_t>(4096, (m / 100 * (size_t)ctx->msm_first_pct) & ~(size_t)63);
-    } else if (overlap_host_first(ctx, standalone, h_scalars, nch, m)) {
+    if (overlap_host_first(ctx, standalone, h_scalars, nch, m)) {
         first = (size_t)1 << 18;
         nch = std::min<uint32_t>(nch + 1, MSM_MAX_CHUNKS);
     }
@@ -225,15 +222,14 @@ int msm_enqueue(typlonk_ctx* ctx, MsmWs& ws, hipStream_t stream, const SrsEntry&
             // kernels finish in 0.14 ms instead of trailing the whole accumulation (0.95 ms), and the next accumulation
             // starts 6 us after the previous one instead of 56 (profiles/r06_ab_sort_prio.txt).  The exposed first sort has
             // the chip to itself and takes 512.  NOT for the queued MSMs of a batch: there it is neutral to slightly
-            // negative (the sorts steal from another MSM's accumulation what they gain).  TYPLONK_MSM_L1_THREADS forces one.
-            const bool beside = ctx->msm_sort_prio && ss != s;
-            const uint32_t l1 = ctx->msm_l1_threads ? (uint32_t)ctx->msm_l1_threads : (beside ? 256u : 512u);
+            // negative (the sorts steal from another MSM's accumulation what they gain).
+            const bool beside = ss != s;
             StageTimer st(ctx, ss == s ? "msm_sort" : "msm_sort_overlapped", ss);
             launch_msm_segsort(sc, (uint64_t)mk, c, W, digit_v, (uint32_t)seg.hb, seg.ibits, tables ? (uint32_t)srs.len : 0u,
                                tables ? nsets : 0u, (uint32_t*)sb.blk_hist.p, (uint32_t*)sb.blk_base.p, blocksums,
                                (uint32_t*)sb.blk_cnt.p, (uint32_t*)sb.seg_start.p, keys, counts, offsets, sorted, cap,
                                (uint32_t*)sb.ohist.p, (uint32_t*)sb.heavy.p, (uint32_t*)sb.tasks.p, (uint32_t*)sb.order.p,
-                               centred, ctx->msm_scatter_staged ? 1 : 0, l1, beside, ss);
+                               centred, ctx->msm_scatter_staged ? 1 : 0, beside, ss);
         } else {
             {
                 StageTimer st(ctx, "msm_digits", ss);
@@ -315,9 +311,8 @@ int msm_enqueue(typlonk_ctx* ctx, MsmWs& ws, hipStream_t stream, const SrsEntry&
         StageTimer st(ctx, "msm_reduce", s);
         // two launches for small bucket sets, where the reduction is a latency chain; big sets are work-bound and the
         // four-launch form wastes fewer lanes (2^19 buckets: 0.39 ms against 0.49, profiles/r03_shard_variants.jsonl)
-        if (!ctx->msm_rc4 && msm_rc2_ok(sh) && (ctx->msm_rc2_force || nb <= (1u << 17)))
-            launch_msm_rc2_reduce(buckets, sh, (uint32_t*)ws.part_b.p, (uint32_t*)ws.part_a.p, planes_out,
-                                  (uint32_t)ctx->msm_rc2_logw, s);
+        if (!ctx->msm_rc4 && msm_rc2_ok(sh) && nb <= (1u << 17))
+            launch_msm_rc2_reduce(buckets, sh, (uint32_t*)ws.part_b.p, (uint32_t*)ws.part_a.p, planes_out, s);
         else
             launch_msm_rc_reduce(buckets, sh, (uint32_t*)ws.part_b.p, (uint32_t*)ws.part_a.p, (uint32_t*)ws.rc_sums.p,
                                  (uint32_t*)ws.rc_bits.p, planes_out, s);

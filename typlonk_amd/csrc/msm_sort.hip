@@ -858,12 +858,12 @@ template <uint32_t C>
 static void launch_msm_segsort_c(const Fr* scalars, uint64_t m, const MsmShape& sh, uint32_t* blk_hist, uint32_t* blk_base,
                                  uint32_t* scan_scratch, uint32_t* blk_cnt, uint32_t* seg_start, uint32_t* entries,
                                  uint32_t* counts, uint32_t* offsets, uint32_t* sorted, uint32_t cap, uint32_t* hist514,
-                                 uint32_t* heavy, uint32_t* tasks, uint32_t* order, int staged_mode, uint32_t l1_threads,
-                                 hipStream_t s) {
+                                 uint32_t* heavy, uint32_t* tasks, uint32_t* order, int staged_mode, hipStream_t s) {
     const uint64_t nmat = (uint64_t)sh.nseg * sh.nblk;
     const uint32_t nt1 = msm_seg1_threads();
-    // threads of the staged scatter and of the histogram beside it: 256 (one wavefront per SIMD) or 512 where the chunk divides
-    const uint32_t nts = (l1_threads == 512 && sh.chunk % 512 == 0) ? 512u : 256u;
+    // threads of the staged scatter and of the histogram beside it: 256 (one wavefront per SIMD) for a sort beside an
+    // accumulation, else 512 where the chunk divides (msm_enqueue)
+    const uint32_t nts = (!sh.prio && sh.chunk % 512 == 0) ? 512u : 256u;
     // the fused row-prefix form scans the segment totals in LDS next to the scatter's cursors (nseg + nt1 words); wider
     // segment sets take the three-launch scan of the whole workgroup x segment matrix
     const bool fused = sh.nseg <= 8192;
@@ -899,7 +899,7 @@ void launch_msm_segsort(const Fr* scalars, uint64_t m, uint32_t c, uint32_t W, u
                         uint32_t ibits, uint32_t tlen, uint32_t nsets, uint32_t* blk_hist, uint32_t* blk_base,
                         uint32_t* scan_scratch, uint32_t* blk_cnt, uint32_t* seg_start, uint32_t* entries, uint32_t* counts,
                         uint32_t* offsets, uint32_t* sorted, uint32_t cap, uint32_t* hist514, uint32_t* heavy, uint32_t* tasks,
-                        uint32_t* order, bool centred, int staged_mode, uint32_t l1_threads, bool beside_accum, hipStream_t s) {
+                        uint32_t* order, bool centred, int staged_mode, bool beside_accum, hipStream_t s) {
     MsmShape sh;
     sh.centred = centred ? 1u : 0u;
     sh.prio = beside_accum ? 1u : 0u;
@@ -916,7 +916,7 @@ void launch_msm_segsort(const Fr* scalars, uint64_t m, uint32_t c, uint32_t W, u
     sh.chunk = msm_chunk_for(m);
     sh.nblk = (uint32_t)((m + sh.chunk - 1) / sh.chunk);
 #define TY_SEGSORT(C) launch_msm_segsort_c<C>(scalars, m, sh, blk_hist, blk_base, scan_scratch, blk_cnt, seg_start, entries, counts, \
-                                              offsets, sorted, cap, hist514, heavy, tasks, order, staged_mode, l1_threads, s)
+                                              offsets, sorted, cap, hist514, heavy, tasks, order, staged_mode, s)
     // the table windows get the constant-width digit extraction; every other width the run-time form
     if (c == 20) TY_SEGSORT(20);
     else if (c == 17) TY_SEGSORT(17);

@@ -348,20 +348,7 @@ int prover_extend(typlonk_prover* p, int k, const Fr* coeffs) {
     if (!rc) p->extended |= 1u << k;
     return rc;
 }
-// the same for several inputs at once (ks[]: their slots): one launch per pass for the group
-int prover_extend_batch(typlonk_prover* p, const int* ks, const Fr* const* coeffs, size_t count) {
-    typlonk_ctx* ctx = p->ctx;
-    const uint64_t n4 = 4 * p->n;
-    int rc = ensure(ctx, ctx->quot_ext, (size_t)5 * n4 * sizeof(Fr));
-    if (rc) return rc;
-    Fr* dst[5];
-    for (size_t i = 0; i < count; ++i) dst[i] = (Fr*)ctx->quot_ext.p + (uint64_t)ks[i] * n4;
-    rc = quotient_extend_batch(ctx, dst, coeffs, count, p->n, p->log_n + 2);
-    if (!rc)
-        for (size_t i = 0; i < count; ++i) p->extended |= 1u << ks[i];
-    return rc;
-}
-// ops_tmp layout of the prover's openings: [0, 8*2048) per-workgroup carries, then 16 result slots.
+// Scratch of the prover's openings: 8*2048 per-workgroup carries in ops_tmp, and 16 result slots.
 // The slots are only ever WRITTEN by kernels (p(z) of an opening) and read by the host, so they live in pinned host memory the
 // kernels store into directly: a fetch is one stream synchronisation, no copy.  (Device slots + hipMemcpyAsync into a stack
 // array -- pageable, so staged by the runtime -- left the GPU idle for ~170 us before the linearisation and ~120 us before
@@ -369,14 +356,11 @@ int prover_extend_batch(typlonk_prover* p, const int* ks, const Fr* const* coeff
 constexpr size_t PROVER_EVAL_BLOCKS = 8 * 2048;
 int prover_ops_tmp(typlonk_prover* p, Fr** blocks, Fr** slots) {
     typlonk_ctx* ctx = p->ctx;
-    int rc = ensure(ctx, ctx->ops_tmp, (PROVER_EVAL_BLOCKS + 16) * sizeof(Fr));
+    int rc = ensure(ctx, ctx->ops_tmp, PROVER_EVAL_BLOCKS * sizeof(Fr));
     if (rc) return rc;
+    if (!ctx->eval_slots_host) HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
     *blocks = (Fr*)ctx->ops_tmp.p;
-    *slots = *blocks + PROVER_EVAL_BLOCKS;
-    if (ctx->prover_pinned_slots) {
-        if (!ctx->eval_slots_host) HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
-        *slots = ctx->eval_slots_host;
-    }
+    *slots = ctx->eval_slots_host;
     return TYPLONK_OK;
 }
 // open() without waiting: p(z) lands in result slot `slot`, the quotient (if q) in q; stream-ordered
@@ -395,13 +379,8 @@ int prover_fetch(typlonk_prover* p, Fr* out, int count) {
     Fr *blocks, *slots;
     int rc = prover_ops_tmp(p, &blocks, &slots);
     if (rc) return rc;
-    if (ctx->prover_pinned_slots) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        memcpy((void*)out, (const void*)slots, (size_t)count * sizeof(Fr));
-        return TYPLONK_OK;
-    }
-    HIPCHK(hipMemcpyAsync(out, slots, (size_t)count * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    memcpy((void*)out, (const void*)slots, (size_t)count * sizeof(Fr));
     return TYPLONK_OK;
 }
 int prover_open(typlonk_prover* p, const Fr* poly, uint64_t m, const Fr& z, Fr* q, Fr* y) {
@@ -478,7 +457,9 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     // a, b, c = interpolate(columns) (proof.rs:50); the column values themselves are kept for round 2
     // (proof.rs:113-115 recomputes them with three forward FFTs).  Each commitment (round1, proof.rs:107-110) is
     // submitted to its own lane as soon as its polynomial exists, so the next interpolation and the coset transforms
-    // of the quotient inputs run while it is being sorted and accumulated.
+    // of the quotient inputs run while it is being sorted and accumulated.  (Batched transforms, ntt_run_batch, LOSE
+    // 0.3-0.5 ms per 2^20 proof here: they delay a commitment's start by the other columns' transforms, which were already
+    // hidden beside the commitments' sorts, profiles/r06_ab_prover_ntt_batch.txt.)
     auto d2d = [&](Fr* dst, const Fr* src) -> int {
         const hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(Fr), hipMemcpyDeviceToDevice, s);
         return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
@@ -493,50 +474,20 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     };
     MsmQueue q(ctx, srs, /*first_lane=*/1);
     p->has_pi = pi_src.present();  // absent: public inputs [0] -> the zero polynomial
-    if (ctx->prover_ntt_batch == 1 || ctx->prover_ntt_batch == 2) {
-        // mode 1: the three interpolations (and the public-input column's, proof.rs:105-106) as ONE batched transform
-        // (ntt_run_batch), then the three commitments; mode 2: the first column alone -- its commitment starts at once --
-        // and the others as one batch beside it.  Either way the coset extensions of the group are one batch.
-        for (int i = 0; i < 3 && !rc; ++i) {
-            if ((rc = fetch(p->ev[i], wires[i]))) break;
-            rc = d2d(p->co[i], p->ev[i]);
-        }
-        if (!rc && p->has_pi) rc = fetch(p->pi, pi_src);
-        Fr* grp[4] = {p->co[0], p->co[1], p->co[2], p->pi};
-        const size_t cnt = p->has_pi ? 4 : 3;
-        if (ctx->prover_ntt_batch == 2) {
-            if (!rc) rc = ntt_run(ctx, p->co[0], log_n, 1, nullptr, false);
-            if (!rc) rc = q.submit(p->co[0], n, commit_xy[0], commit_inf);
-            if (!rc) rc = ntt_run_batch(ctx, grp + 1, cnt - 1, log_n, 1, nullptr, false);
-            for (int i = 1; i < 3 && !rc; ++i) rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
-        } else {
-            if (!rc) rc = ntt_run_batch(ctx, grp, cnt, log_n, 1, nullptr, false);
-            for (int i = 0; i < 3 && !rc; ++i) rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
-        }
-        const int slots[4] = {0, 1, 2, 4};
-        if (!rc) rc = prover_extend_batch(p, slots, grp, cnt);
-    } else {
-        for (int i = 0; i < 3 && !rc; ++i) {
-            if ((rc = fetch(p->ev[i], wires[i]))) break;
-            if ((rc = d2d(p->co[i], p->ev[i]))) break;
-            if ((rc = ntt_run(ctx, p->co[i], log_n, 1, nullptr, false))) break;
-            rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
-        }
-        if (!rc && p->has_pi) {
-            rc = fetch(p->pi, pi_src);
-            if (!rc) rc = ntt_run(ctx, p->pi, log_n, 1, nullptr, false);  // proof.rs:105-106
-        }
-        // the coset transforms of the quotient's per-proof inputs run beside the commitments (measured: -1 % per proof;
-        // submitting round 3's first opening MSMs before the quotient loses 1 %: profiles/r02_ab_prover_overlap.txt)
-        if (ctx->prover_ntt_batch == 3) {   // mode 3: interpolations one by one (above), the extensions as one batch
-            Fr* grp[4] = {p->co[0], p->co[1], p->co[2], p->pi};
-            const int slots[4] = {0, 1, 2, 4};
-            if (!rc) rc = prover_extend_batch(p, slots, grp, p->has_pi ? 4 : 3);
-        } else {
-            for (int i = 0; i < 3 && !rc; ++i) rc = prover_extend(p, i, p->co[i]);
-            if (!rc && p->has_pi) rc = prover_extend(p, 4, p->pi);
-        }
+    for (int i = 0; i < 3 && !rc; ++i) {
+        if ((rc = fetch(p->ev[i], wires[i]))) break;
+        if ((rc = d2d(p->co[i], p->ev[i]))) break;
+        if ((rc = ntt_run(ctx, p->co[i], log_n, 1, nullptr, false))) break;
+        rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
     }
+    if (!rc && p->has_pi) {
+        rc = fetch(p->pi, pi_src);
+        if (!rc) rc = ntt_run(ctx, p->pi, log_n, 1, nullptr, false);  // proof.rs:105-106
+    }
+    // the coset transforms of the quotient's per-proof inputs run beside the commitments (measured: -1 % per proof;
+    // submitting round 3's first opening MSMs before the quotient loses 1 %: profiles/r02_ab_prover_overlap.txt)
+    for (int i = 0; i < 3 && !rc; ++i) rc = prover_extend(p, i, p->co[i]);
+    if (!rc && p->has_pi) rc = prover_extend(p, 4, p->pi);
     {
         const int r = q.wait_all();
         if (!rc) rc = r;
@@ -725,9 +676,7 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     // r(zeta) and its witness polynomial (proof.rs:175).  The reference shape does not wait for the value here: it is an
     // OUTPUT (and the r(zeta) != 0 check), nothing of this round's commitments depends on it -- it is read from its pinned slot
     // once the commitments have been waited for, and the first sort starts without a drain of the context's stream in between.
-    const bool late_r = !batched && ctx->prover_pinned_slots;
-    if (!rc) rc = late_r ? prover_open_async(p, p->r, n, ze, p->q[5], 0)
-                         : prover_open(p, p->r, n, ze, batched ? nullptr : p->q[5], &ev[5]);
+    if (!rc) rc = batched ? prover_open(p, p->r, n, ze, nullptr, &ev[5]) : prover_open_async(p, p->r, n, ze, p->q[5], 0);
     if (!rc && batched) {
         // evaluations only: every commitment of this shape is issued by round4_batched in ONE five-MSM batch
         for (int i = 0; i < 6; ++i) memcpy(evals_out->evals[i], ev[i].v, 32);
@@ -744,17 +693,15 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
         // lane, included the whole MSM submitted to it just before.  (Rounds 1-4: commitments 4 and 5 started their sorts
         // only when commitment 3 had finished, and 7 and 8 after 6: two stretches of 1.2 ms with no accumulation in
         // flight, profiles/r04_prove_timeline.txt 23.1-24.4 and 30.6-31.9 ms.)
-        if (ctx->prover_pipe) {
-            if (!ctx->batch_fence) HIPCHK(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ctx->batch_fence, ctx->stream));
-            q.fence = ctx->batch_fence;
-        }
+        if (!ctx->batch_fence) HIPCHK(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ctx->batch_fence, ctx->stream));
+        q.fence = ctx->batch_fence;
         for (int k = 0; k < 9 && !rc; ++k) rc = q.submit(polys[k], m[k], xy[k], inf + k);
         {
             const int r = q.wait_all();
             if (!rc) rc = r;
         }
-        if (!rc && late_r) rc = prover_fetch(p, &ev[5], 1);   // (every lane has been waited for: this returns at once)
+        if (!rc) rc = prover_fetch(p, &ev[5], 1);   // (every lane has been waited for: this returns at once)
         if (!rc) {
             memcpy(out->w_xy, xy, 6 * 96);
             memcpy(out->w_inf, inf, 6);
