@@ -3,6 +3,7 @@
   typlonk_amd/libtyplonk_hip.so   HIP kernels + C ABI (include/typlonk.h)       -- hipcc
   tests/cpp/hooks/libtyplonk_hip.so  the same library with the fault-injection hook (-DTYPLONK_TEST_HOOKS, tests only) -- hipcc
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
+  tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
 Every target is rebuilt only when one of its sources is newer than the output.
@@ -127,6 +128,17 @@ def build_host_shim(force: bool = False) -> str:
     return out
 
 
+def build_device_arith(force: bool = False) -> str:
+    """tests/cpp/libdevice_arith.so: the arithmetic headers' device code behind element-wise test kernels
+    (tests/test_gpu_arith.py).  Test-only and not linked into the shipped library; the flags are build_hip()'s."""
+    src = os.path.join(ROOT, "tests", "cpp", "device_arith.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_arith.so")
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
+    if force or _stale(out, [src] + hdrs):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
 def build_host_tests(force: bool = False) -> list[str]:
     """test binaries of the C++ host mirror (typlonk_amd/host/typlonk_host.hpp), linked to the HIP library"""
     outs = []
@@ -159,6 +171,7 @@ def build_all(force: bool = False) -> None:
     build_hip(force)
     build_hip_test_hooks(force)
     build_host_shim(force)
+    build_device_arith(force)
     build_host_tests(force)
     build_fake_rccl(force)
 

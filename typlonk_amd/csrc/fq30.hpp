@@ -123,8 +123,10 @@ TY_HD Fq30 fq30_redc(const uint32_t (&T)[26]) {
     return r;
 }
 
-// a*b*2^-390 mod p.  Needs normalised limbs and a*b < 2^780; output < (1 + A*B/630) p for
-// a < A p, b < B p.  338 + 26 mads, no carry instructions inside a column.
+// a*b*2^-390 mod p.  Needs normalised limbs and a*b < (2^390 - p) 2^390 (~2^780 - 2^771: the result
+// p + a*b/2^390 must fit 390 bits; above it, up to 2^780, the columns still hold but the top bit of the
+// result is lost); output < (1 + A*B/630) p for a < A p, b < B p.  338 + 26 mads, no carry instructions
+// inside a column.
 TY_HD Fq30 fq30_mul_split(const Fq30& a, const Fq30& b) {
     uint32_t T[26];
     uint64_t acc = 0;
@@ -176,10 +178,11 @@ TY_HD Fq30 fq30_sqr_split(const Fq30& a) {
 // first ten product terms (which provably fit) are accumulated first and only the remaining 11 terms of a
 // multiplication (8 of a squaring) capture the carry-out of the mad into a third word
 // (v_mad_u64_u32 ..., vcc + v_addc_co_u32).  The schedule below was computed with exact bounds by
-// tools/fq30_fused_bounds.py; tests/cpp and the GPU tests compare every variant with fq30_mul on
-// random and extreme (all-ones digits) inputs.
+// tools/fq30_fused_bounds.py; tests/test_gpu_arith.py checks the device fq30_mul / fq30_sqr against Python integers
+// (the exact REDC value, residue and value bound) on random, lifted and extreme (all-ones digits, 2^390 - 1) inputs.
 //
-// Same contract as fq30_mul / fq30_sqr: normalised limbs, a*b < 2^780, result < p + a*b / 2^390.
+// Same contract as fq30_mul_split / fq30_sqr_split: normalised limbs, a*b < (2^390 - p) 2^390, result
+// < p + a*b / 2^390 (the column bounds hold up to a*b < 2^780).
 
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -294,7 +297,7 @@ TY_HD void fq30_mul_wide(const Fq30& a, const Fq30& b, uint32_t (&T)[26]) {
     }
     T[25] = (uint32_t)acc;
 }
-// (a*b + c*d) * 2^-390 mod p; needs a*b + c*d < 2^780; result < p + (a*b + c*d) / 2^390.
+// (a*b + c*d) * 2^-390 mod p; needs a*b + c*d < (2^390 - p) 2^390 (as fq30_mul); result < p + (a*b + c*d) / 2^390.
 // The digit sums are < 2^31 (T[25]: < 2^32 by the value bound), which fq30_redc takes as they are.
 TY_HD Fq30 fq30_mul2_add(const Fq30& a, const Fq30& b, const Fq30& c, const Fq30& d) {
     uint32_t T[26], U[26];

@@ -13,7 +13,8 @@
 // Montgomery digit is just the negated low limb (no multiplication by -r^-1).  Additions and subtractions are
 // limb-wise without carry propagation, followed by one parallel carry step.
 //
-// Bounds (checked by tests/test_gpu_ntt.py through whole-transform equality with the oracle at every size):
+// Bounds (checked primitive by primitive at their limits against Python integers by tests/test_gpu_arith.py, and end to end
+// by tests/test_gpu_ntt.py through whole-transform equality with the oracle at every size):
 //   * limbs 0..7 of every operand of fr30_mul are <= 2^30 + 3, limb 8 < 2^29; twiddles are exact (limbs < 2^30, < 2r).
 //     Column sum <= 9 * (2^30 + 3) * 2^30 + (2^30 - 1) * sum_j r_j + carry, with sum_j r_j = 4.91 * 2^30:
 //     < 13.92 * 2^60 < 2^64.
@@ -116,7 +117,9 @@ __device__ __forceinline__ Fr30 fr30_add(const Fr30& a, const Fr30& b) {
     for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] + b.v[i];
     return fr30_norm(r);
 }
-// x - y + 2^12 r (y < 2^12 r), carry step included
+// x - y + 2^12 r, carry step included.  Limbs 0..7 of x and y <= 2^30 + 3, and y_8 <= x_8 + (limb 8 of 2^12 r) - 2: the
+// bias lends 2^31 down from limb 8, so a larger y_8 wraps it.  Every y < 2^12 r - 2^241 meets that for any x; y < 2^12 r
+// alone does not (x = 0, y = 2^12 r - 1 wraps in every lazy form).
 __device__ __forceinline__ Fr30 fr30_sub(const Fr30& a, const Fr30& b) {
     Fr30 r;
 #pragma unroll
