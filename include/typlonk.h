@@ -84,8 +84,12 @@ int typlonk_srs_download(typlonk_ctx* ctx, uint32_t srs_id, size_t offset, size_
  * terms over this SRS then let all windows share ONE bucket set: no cross-window doublings on the
  * host, fewer windows, fewer bucket additions.  Results are unchanged bit for bit.  Setup-time cost: T*c Jacobian doublings + ONE shared inversion per point
  * (plus T * len * 48 bytes of scratch for the duration of the call; TYPLONK_ERR_OOM if either allocation is refused).
- * An MSM length the table-mode sort cannot handle (more than 2^22 terms with 20-bit windows) silently takes the
- * plain path over the same SRS: precomputation never turns a valid MSM into an error. */
+ * The sort sees an MSM one chunk at a time (queued MSMs in chunks of <= 2^20 terms), so table mode holds for MSMs of any
+ * length up to len; an MSM whose largest chunk the table-mode sort cannot handle silently takes the plain path over the
+ * same SRS: precomputation never turns a valid MSM into an error.  1 <= len <= 2^25, and every gather index
+ * j * len + i (j < T, i < len) must stay below 2^31 (bit 31 carries the sign): T * len <= 2^31, which every window
+ * 14..20 meets at 2^25 points.  Any other length returns TYPLONK_ERR_LENGTH.
+ * HBM: T * len * 128 bytes for the tables (c = 20: 26.0 GiB at 2^24 + 3 points, 13.0 GiB at 2^23 + 3). */
 #define TYPLONK_TABLES_AUTO_MIN_LEN 16384
 int typlonk_srs_precompute(typlonk_ctx* ctx, uint32_t srs_id, uint32_t window_bits);
 /* Multi-GPU: declare that this entry holds bases [first_index, first_index + len) of a total_len-point SRS
@@ -198,9 +202,19 @@ int typlonk_ntt_fr_batch_devptr(typlonk_ctx* ctx, void* const* d_data, size_t co
  * the three commitments of SlicedPoly<3> are MSMs of [0,n), [n,2n), [2n,3n)), the rest is zero.
  * The schoolbook products of the reference are replaced by a 4n coset NTT: identical result
  * whenever the constraint numerator vanishes on the domain (every valid witness). */
-/* The prover-side entry points (quotient, grand product, open, the rounds, typlonk_prove) take 1 <= log_n <= 22 -- the
- * sizes the parity suite covers (BASELINE config 5 is 2^22 rows); larger domains return TYPLONK_ERR_DOMAIN / _LENGTH. */
-#define TYPLONK_MAX_PROVER_LOG_N 22
+/* The prover-side entry points (quotient, grand product, the rounds, typlonk_prove) take 1 <= log_n <= 24 -- up to 2^24
+ * rows, a 2^26-point quotient domain, on one GPU; larger domains return TYPLONK_ERR_DOMAIN / _LENGTH.
+ * HBM a context keeps after a proof of n = 2^log_n rows (grow-only workspaces, released by typlonk_free; 32 B per Fr):
+ *                                        n = 2^22   n = 2^23   n = 2^24
+ *   circuit cache (9 x 4n + 11 n Fr)       5.9 GiB   11.8 GiB   23.5 GiB   per typlonk_circuit_load
+ *   quot_ext (5 x 4n Fr)                   2.5 GiB    5.0 GiB   10.0 GiB
+ *   prover_mem (19 n Fr)                   2.4 GiB    4.8 GiB    9.5 GiB
+ *   ops_tmp (4 n + n / 2048 + 8 Fr)        0.5 GiB    1.0 GiB    2.0 GiB   (grand product)
+ *   ntt_scratch (a 2^25 / 2^26 batch)      1.0 GiB    1.0 GiB    2.0 GiB
+ *   SRS of n + 3 points with c = 20 tables 6.5 GiB   13.0 GiB   26.0 GiB   (13 x 128 B per point)
+ *   total                                 18.8 GiB   36.5 GiB   73.0 GiB   plus twiddle / coset tables and MSM workspaces
+ * (typlonk_srs_precompute itself needs another (T - 1) x 48 B per point while it runs: 9.0 GiB at 2^24 + 3.) */
+#define TYPLONK_MAX_PROVER_LOG_N 24
 typedef struct typlonk_quotient_args {
     const typlonk_buf* wires[3];
     const typlonk_buf* z;
@@ -231,7 +245,7 @@ int typlonk_grand_product_dev(typlonk_ctx* ctx, const typlonk_buf* const wires[3
 /* ---- open(): the polynomial half of kzg::KzgScheme::open (/root/reference/kzg/src/lib.rs:55-61).
  * poly: m coefficients starting at `offset` of a device vector.  y_out <- p(z) (Horner, :57); when
  * q_out is not NULL it receives the m - 1 coefficients of (p - p(z)) / (X - z) (:58-61), ready for
- * typlonk_msm_g1_dev (:62).  q_out must not alias poly.  1 <= m <= 2^22.  Blocks for the 32-byte result. */
+ * typlonk_msm_g1_dev (:62).  q_out must not alias poly.  1 <= m <= 2^25.  Blocks for the 32-byte result. */
 int typlonk_open_dev(typlonk_ctx* ctx, const typlonk_buf* poly, size_t offset, size_t m, const uint64_t z[4],
                      typlonk_buf* q_out, uint64_t y_out[4]);
 /* out[i] = sum_k scalars[k] * polys[k][i] for i < n, plus `constant` (may be NULL) on coefficient 0: the
@@ -248,7 +262,7 @@ int typlonk_lincomb_dev(typlonk_ctx* ctx, const typlonk_buf* const* polys, const
  *   round2  beta, gamma (:111) -> grand product Z (:119), iNTT (:127), [Z] (:129)
  *   round3  alpha, zeta (:133-136) -> quotient (:139), openings of a, b, c, Z at zeta and Z at zeta*w (:147-163),
  *           linearisation polynomial r and its opening (:165-175), [t_lo], [t_mid], [t_hi] (:181)
- * The circuit id comes from typlonk_circuit_load; the SRS must hold > n points.  n <= 2^22. */
+ * The circuit id comes from typlonk_circuit_load; the SRS must hold > n points.  n <= 2^24. */
 typedef struct typlonk_prover typlonk_prover;
 typedef struct typlonk_proof_tail {
     uint64_t t_xy[3][12];   /* quotient slice commitments                                   */

@@ -10,9 +10,23 @@ from bench import fr_mont_limbs
 log_n = int(os.environ.get("LOG_N", "20"))
 n = 1 << log_n
 ctx = typlonk_amd.Context(0)
+t0 = time.perf_counter()
 sid = ctx.srs_generate(fr_mont_limbs(2), n + 3)
+t1 = time.perf_counter()
 ctx.srs_precompute(sid, 20)
+t2 = time.perf_counter()
+load_s = []   # typlonk_circuit_load alone (it returns once the coset transforms are done), inside the chain's set-up
+_load = ctx.circuit_load
+def _timed_load(*a):
+    t = time.perf_counter()
+    r = _load(*a)
+    load_s.append(time.perf_counter() - t)
+    return r
+ctx.circuit_load = _timed_load
 chain = SquaringChain(ctx, log_n)
+t3 = time.perf_counter()
+print(f"setup log_n={log_n}: srs_generate {(t1 - t0) * 1e3:.0f} ms ({n + 3} points), srs_precompute(c=20) {(t2 - t1) * 1e3:.0f} ms, "
+      f"circuit_load {sum(load_s) * 1e3:.0f} ms (squaring chain with witness {(t3 - t2) * 1e3:.0f} ms)", flush=True)
 host = os.environ.get("HOST", "0") == "1"
 cols = [b.download() for b in chain.wire_evals] if host else None
 run = (lambda: ctx.prove_native_host(sid, chain.circuit, cols, None, chain.cosets)) if host else \

@@ -60,7 +60,8 @@ void launch_product_scan(const Fr* in, uint64_t n, int reverse, Fr* block_scratc
 void launch_fr_inv(const Fr* in, Fr* out, hipStream_t s);   // out[0] = in[0]^-1 on the device (one wavefront)
 void launch_gp_finish(const Fr* nprefix, const Fr* dsuffix, const Fr* inv_total /* device */, uint64_t n, Fr* z, hipStream_t s);
 
-// open(): y = p(z) and q = (p - y)/(X - z) in one suffix scan; m <= 2^22 coefficients, q may be null
+// open(): y = p(z) and q = (p - y)/(X - z) in one suffix scan; q may be null; blocks: max(2048, ceil(m/2048)) + 1 Fr
+// (the carries of more than 2048 workgroups are scanned in rounds of 2048 by the single-workgroup top stage)
 void launch_open(const Fr* c, uint64_t m, const Fr& z, Fr* q, Fr* blocks, Fr* y, hipStream_t s);
 struct LincombArgs {
     const Fr* poly[12];
@@ -71,7 +72,7 @@ struct LincombArgs {
     uint32_t terms;
 };
 void launch_lincomb(const LincombArgs& a, hipStream_t s);
-// count <= 8 openings (quotients[k] != null: y and (p - y)/(X - z)) or evaluations (null) of polynomials of m <= 2^22
+// count <= 8 openings (quotients[k] != null: y and (p - y)/(X - z)) or evaluations (null) of polynomials of m
 // coefficients, each at z0 (zsel[k] = 0) or z1 (1), in three launches; blocks: 8 * ceil(m/2048) Fr; ys[k]: device scalar
 void launch_open_multi(const Fr* const* polys, Fr* const* quotients, Fr* const* ys, const uint8_t* zsel, uint32_t count,
                        uint64_t m, const Fr& z0, const Fr& z1, Fr* blocks, hipStream_t s);

@@ -48,8 +48,34 @@ SegShape msm_seg_shape(size_t m, uint32_t c, uint32_t W, uint32_t nsets, bool ta
             (uint64_t)W * m < (1ull << 31);
     return sh;
 }
-// can a full-length MSM over a len-point SRS run in table mode with c-bit windows?  (the longest MSM is the worst case)
-bool msm_table_shape_ok(size_t len, uint32_t c, uint32_t T) { return msm_seg_shape(len, c, T, 1, true).ok; }
+// Chunks of an m-term MSM (msm_chunks): chunk k = terms [cut(k), cut(k + 1)), equal shares, or (first != 0) a first chunk
+// of that many terms and equal shares of the rest
+struct MsmChunks {
+    uint32_t nch = 1;
+    size_t first = 0;
+    size_t cut(size_t m, uint32_t k) const {
+        if (k == 0) return 0;
+        const size_t step = first ? (m - first + nch - 2) / (nch - 1) : (m + nch - 1) / nch;
+        return std::min(m, first ? first + (size_t)(k - 1) * step : (size_t)k * step);
+    }
+    size_t largest(size_t m) const {
+        size_t big = 0;
+        for (uint32_t k = 0; k < nch; ++k) big = std::max(big, cut(m, k + 1) - cut(m, k));
+        return big;
+    }
+};
+// a queued table-mode MSM of more than 2^20 terms runs in chunks of <= 2^20 terms (see msm_chunks)
+static uint32_t queued_table_chunks(size_t m) { return m > ((size_t)1 << 20) ? (uint32_t)((m + ((size_t)1 << 20) - 1) >> 20) : 1u; }
+// Can MSMs over a len-point SRS run in table mode with c-bit windows and T tables?  Every gather index j * len + i
+// (j < T, i < len) must leave bit 31 free for the sign (msm_sort.hip), and the shortest table-mode MSM -- len / 4 terms,
+// in the chunks a queued MSM of that length takes -- must have a sort shape.
+bool msm_table_srs_ok(size_t len, uint32_t c, uint32_t T) {
+    if ((uint64_t)T * len > (1ull << 31)) return false;
+    const size_t m = std::max<size_t>(len / 4, 1);
+    MsmChunks ch;
+    ch.nch = queued_table_chunks(m);
+    return msm_seg_shape(ch.largest(m), c, T, 1, true).ok;
+}
 
 void write_affine_out(const G1Affine& a, uint64_t out_xy[12], uint8_t* out_inf) {
     uint32_t w[12];
@@ -74,6 +100,44 @@ static bool overlap_host_first(const typlonk_ctx* ctx, bool standalone, const ui
     return standalone && h_scalars && nch == 2 && !ctx->msm_chunks && m >= ((size_t)1 << 20);
 }
 
+MsmChunks msm_chunks(const typlonk_ctx* ctx, size_t m, bool tables, bool standalone, const uint64_t* h_scalars) {
+    // Chunks of terms.  A stand-alone MSM (nothing else in flight to hide behind) is cut into chunks that all add into
+    // the SAME buckets: while chunk k is accumulated on the MSM's stream, chunk k + 1 is sorted on the workspace's side
+    // stream, so only the first chunk's sort (and the last one's reduction) stay exposed.  Later chunks start from the
+    // stored buckets (192 B read + written per bucket and chunk -- noise next to the additions).  Bit-identical
+    // results: group addition is commutative and the output is the canonical affine point.
+    MsmChunks ch;
+    if (standalone) {
+        // measured (tools/msm_chunks.py, profiles/r02_msm_chunks.jsonl): the overlapped sort is not free -- it competes
+        // with the accumulation for issue slots -- and chunks of ~2^19 terms are the best grain: 2 chunks at 2^20
+        // (2.76 -> 2.68 ms), 4 at 2^21 (5.09 -> 4.81), 8 at 2^22 (9.92 -> 8.99); below 2^20 one chunk wins
+        // (scalars still on the host: two chunks from 2^19 terms on, so that half of the copy hides -- 1.68 -> 1.57 ms at 2^19;
+        // neutral at 2^18, a loss at 2^17: profiles/r06_ab_host_scalar_path.txt, call W)
+        ch.nch = ctx->msm_chunks ? (uint32_t)ctx->msm_chunks
+                                 : (m >= (1u << 20) ? (uint32_t)std::min<size_t>(m >> 19, MSM_MAX_CHUNKS)
+                                                    : (h_scalars && m >= (1u << 19) ? 2u : 1u));
+        while (ch.nch > 1 && m / ch.nch < 4096) --ch.nch;
+    } else if (tables) {
+        // A queued MSM (a batch, a prover round) of more than 2^20 terms: chunks of <= 2^20 terms one after the other on the
+        // MSM's own stream, all adding into the same buckets.  Not for overlap (the other lanes provide that) but for the
+        // sort's shape: above 2^20 terms a level-1 entry has too few bits left for the low bucket bits, the segment count
+        // passes 8192 and the sort falls back to the three-launch scan and the direct scatter (rounds 1-5: every
+        // commitment of a 2^22-row proof).  Not capped at MSM_MAX_CHUNKS (which sizes the overlap events of a stand-alone
+        // MSM): these chunks run in stream order, so a 2^24-term commitment is 16 chunks of the same shape as at 2^20.
+        ch.nch = queued_table_chunks(m);
+    }
+    // chunk k = terms [cut(k), cut(k + 1)): equal shares, or a first chunk of its own size and equal shares of the rest:
+    //  * scalars in HOST memory (typlonk_msm_g1): the first chunk's copy over PCIe is the exposed one, so it is 2^18 terms (8 MB)
+    //    instead of 2^19 and there is one chunk more -- 2.73-2.75 -> 2.59-2.65 ms per 2^20-term commitment
+    //    (profiles/r06_ab_host_scalar_path.txt, calls U and V); device-resident scalars keep equal chunks (an unequal first
+    //    chunk loses there: profiles/r06_ab_first_chunk_and_rc2.txt).
+    if (overlap_host_first(ctx, standalone, h_scalars, ch.nch, m)) {
+        ch.first = (size_t)1 << 18;
+        ch.nch = std::min<uint32_t>(ch.nch + 1, MSM_MAX_CHUNKS);
+    }
+    return ch;
+}
+
 // Launch every kernel of one m-term MSM (m > 0, validated by the caller) on `stream` using workspace
 // `ws`, ending with the asynchronous copy of the W window sums into ws.host_wins.
 // h_scalars != NULL: the scalars are still on the HOST (typlonk_msm_g1: the reference's commit() hands over a Vec<Fr>); every
@@ -86,10 +150,16 @@ int msm_enqueue(typlonk_ctx* ctx, MsmWs& ws, hipStream_t stream, const SrsEntry&
     uint32_t c, W;
     msm_shape(m, &c, &W);
     // fixed-base tables: every window reads its own pre-shifted copy of the base, so all windows share
-    // one bucket set (plus a separate set for a thin top window) and no cross-window doublings remain
-    // (typlonk_srs_precompute refuses shapes the table-mode sort cannot handle; the check here keeps a plain MSM
-    // possible should one slip through)
-    const bool tables = srs.table_T != 0 && m >= srs.len / 4 && srs.len <= (1u << 23) && msm_seg_shape(m, srs.table_c, srs.table_T, 1, true).ok;
+    // one bucket set (plus a separate set for a thin top window) and no cross-window doublings remain.  The sort sees one
+    // chunk at a time, with chunk-local term indices, so the shape of the LARGEST chunk decides (typlonk_srs_precompute
+    // refuses SRS shapes the table-mode sort cannot handle; the check here keeps a plain MSM possible should one slip through)
+    MsmChunks chunks;
+    bool tables = false;
+    if (srs.table_T != 0 && m >= srs.len / 4 && (uint64_t)srs.table_T * srs.len <= (1ull << 31)) {
+        chunks = msm_chunks(ctx, m, true, standalone, h_scalars);
+        tables = msm_seg_shape(chunks.largest(m), srs.table_c, srs.table_T, 1, true).ok;
+    }
+    if (!tables) chunks = msm_chunks(ctx, m, false, standalone, h_scalars);
     if (tables) {
         c = srs.table_c;
         W = srs.table_T;
@@ -109,42 +179,8 @@ int msm_enqueue(typlonk_ctx* ctx, MsmWs& ws, hipStream_t stream, const SrsEntry&
     if ((uint64_t)W * m >= (1ull << 31)) return fail(ctx, TYPLONK_ERR_LENGTH, "MSM too large for 32-bit entry indices");
     const uint32_t scan_blocks = (uint32_t)((nb + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK);
 
-    // Chunks of terms.  A stand-alone MSM (nothing else in flight to hide behind) is cut into chunks that all add into
-    // the SAME buckets: while chunk k is accumulated on the MSM's stream, chunk k + 1 is sorted on the workspace's side
-    // stream, so only the first chunk's sort (and the last one's reduction) stay exposed.  Later chunks start from the
-    // stored buckets (192 B read + written per bucket and chunk -- noise next to the additions).  Bit-identical
-    // results: group addition is commutative and the output is the canonical affine point.
-    uint32_t nch = 1;
-    if (standalone) {
-        // measured (tools/msm_chunks.py, profiles/r02_msm_chunks.jsonl): the overlapped sort is not free -- it competes
-        // with the accumulation for issue slots -- and chunks of ~2^19 terms are the best grain: 2 chunks at 2^20
-        // (2.76 -> 2.68 ms), 4 at 2^21 (5.09 -> 4.81), 8 at 2^22 (9.92 -> 8.99); below 2^20 one chunk wins
-        // (scalars still on the host: two chunks from 2^19 terms on, so that half of the copy hides -- 1.68 -> 1.57 ms at 2^19;
-        // neutral at 2^18, a loss at 2^17: profiles/r06_ab_host_scalar_path.txt, call W)
-        nch = ctx->msm_chunks ? (uint32_t)ctx->msm_chunks
-                              : (m >= (1u << 20) ? (uint32_t)std::min<size_t>(m >> 19, MSM_MAX_CHUNKS)
-                                                 : (h_scalars && m >= (1u << 19) ? 2u : 1u));
-        while (nch > 1 && m / nch < 4096) --nch;
-    } else if (tables && m > ((size_t)1 << 20)) {
-        // A queued MSM (a batch, a prover round) of more than 2^20 terms: chunks of <= 2^20 terms one after the other on the
-        // MSM's own stream, all adding into the same buckets.  Not for overlap (the other lanes provide that) but for the
-        // sort's shape: above 2^20 terms a level-1 entry has too few bits left for the low bucket bits, the segment count
-        // passes 8192 and the sort falls back to the three-launch scan and the direct scatter (rounds 1-5: every
-        // commitment of a 2^22-row proof).
-        nch = (uint32_t)std::min<size_t>((m + ((size_t)1 << 20) - 1) >> 20, MSM_MAX_CHUNKS);
-    }
-    // chunk k = terms [cut(k), cut(k + 1)): equal shares, or a first chunk of its own size and equal shares of the rest:
-    //  * scalars in HOST memory (typlonk_msm_g1): the first chunk's copy over PCIe is the exposed one, so it is 2^18 terms (8 MB)
-    //    instead of 2^19 and there is one chunk more -- 2.73-2.75 -> 2.59-2.65 ms per 2^20-term commitment
-    //    (profiles/r06_ab_host_scalar_path.txt, calls U and V); device-resident scalars keep equal chunks (an unequal first
-    //    chunk loses there: profiles/r06_ab_first_chunk_and_rc2.txt).
-    size_t first = 0;
-    if (overlap_host_first(ctx, standalone, h_scalars, nch, m)) {
-        first = (size_t)1 << 18;
-        nch = std::min<uint32_t>(nch + 1, MSM_MAX_CHUNKS);
-    }
-    const size_t step = first ? (m - first + nch - 2) / (nch - 1) : (m + nch - 1) / nch;
-    auto cut = [&](uint32_t k) { return k == 0 ? (size_t)0 : std::min(m, first ? first + (size_t)(k - 1) * step : (size_t)k * step); };
+    const uint32_t nch = chunks.nch;
+    auto cut = [&](uint32_t k) { return chunks.cut(m, k); };
     hipStream_t s = ws.stream;
     int rc;
     const bool overlap = nch > 1 && standalone;   // chunk k + 1 sorted on the side stream while chunk k accumulates
@@ -615,16 +651,17 @@ int typlonk_srs_precompute(typlonk_ctx* ctx, uint32_t srs_id, uint32_t window_bi
     if (window_bits < 14 || window_bits > 20) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "window_bits must be 0 (auto) or 14..20");
     SrsEntry& e = it->second;
     if (e.table_T) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "tables already built for this SRS");
-    if (e.len == 0 || e.len > (1u << 23)) return fail(ctx, TYPLONK_ERR_LENGTH, "tables need 1 <= len <= 2^23");
+    if (e.len == 0 || e.len > ((size_t)1 << 25)) return fail(ctx, TYPLONK_ERR_LENGTH, "tables need 1 <= len <= 2^25");
     HIPCHK(hipSetDevice(ctx->device));
     // centred scalars (|k| < 2^254) save a window -- and a table -- for c = 17 (15 instead of 16) and c = 15
     const bool centred = msm_windows(window_bits, true) < msm_windows(window_bits, false);
     const uint32_t T = msm_windows(window_bits, centred);
-    // An MSM whose length has no table-mode sort shape (m > 2^22 with 20-bit windows: 23 index bits leave too few low
-    // bucket bits for the LDS level of the sort) simply takes the plain path over table 0, which IS the SRS
-    // (msm_enqueue) -- a set-up call that is supposed to be speed-only never turns a valid MSM into an error.  Only a
-    // window for which not even the shortest table-mode MSM (len / 4 terms) could be sorted is refused.
-    if (!msm_table_shape_ok(std::max<size_t>(e.len / 4, 1), window_bits, T))
+    // The sort sees one chunk at a time (msm_chunks), so MSMs of any length up to len run in table mode; one whose largest
+    // chunk had no table-mode sort shape (more than 2^22 terms with 20-bit windows: 23 index bits leave too few low bucket
+    // bits for the LDS level of the sort) would simply take the plain path over table 0, which IS the SRS (msm_enqueue) --
+    // a set-up call that is supposed to be speed-only never turns a valid MSM into an error.  Refused: an SRS whose gather
+    // indices would reach bit 31, and a window for which not even the shortest table-mode MSM (len / 4 terms) could be sorted.
+    if (!msm_table_srs_ok(e.len, window_bits, T))
         return fail(ctx, TYPLONK_ERR_LENGTH, "fixed-base tables with this window are not supported for an SRS of this length");
     uint32_t* big = nullptr;
     HIPCHK(hipMalloc((void**)&big, (size_t)T * e.len * PT_WORDS * 4));

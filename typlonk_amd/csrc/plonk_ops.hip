@@ -189,20 +189,35 @@ __global__ __launch_bounds__(256) void open_block_kernel(OpenArgs a) {
     const Fr g0 = horner_block(a.c, a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow, 0, lds, loc, &ci);
     if (threadIdx.x == 0) p_st(a.blocks + blockIdx.x, g0);
 }
-// single workgroup: carries between workgroups, C_b = A_b + z^2048 C_{b+1}; blocks[b] <- C_{b+1}
-// (the value of H at the end of workgroup b); up to 2048 workgroups
+// single workgroup: carries between workgroups, C_b = A_b + z^2048 C_{b+1}; blocks[b] <- C_{b+1} (the value of H at the
+// end of workgroup b); returns C_0 = p(z).  Rounds of 2048 entries from the high end, each seeded with the C its upper
+// neighbour ended on: horner_block then carries the seed across the round with (z^2048)^2048 = z^(2^22), so any number of
+// workgroups is one launch of the same kernel (m <= 2^22: one round from a zero seed, as before).  A third scan level
+// would cost two more launches at every size for at most 8 serial rounds of ~3 us at m = 2^25.
+__device__ __forceinline__ Fr open_top_rounds(Fr* blocks, uint32_t nblk, const Fr* zpow, bool store, Fr* lds) {
+    Fr loc[8], ci;
+    Fr run = Fr::zero();
+    const Fr zb = zpow[11];
+    for (uint32_t r = (nblk + 2047) / 2048; r-- > 0;) {
+        const uint64_t base = (uint64_t)r * 2048;
+        const Fr c0 = horner_block(blocks, nblk, base, run, zpow, 11, lds, loc, &ci);
+        if (store) {
+            // recompute the local chain from the true carry-in and store, for every entry, H of the NEXT entry
+            Fr h = ci;
+            const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
+            for (int e = 7; e >= 0; --e) {
+                if (s0 + e < nblk) p_st(blocks + s0 + e, h);
+                h = fe_add(loc[e], fe_mul(zb, h));
+            }
+        }
+        run = c0;
+        __syncthreads();   // the next round's horner_block overwrites the LDS this one's lds[0] / carries came from
+    }
+    return run;
+}
 __global__ __launch_bounds__(256) void open_top_kernel(OpenArgs a, uint32_t nblk) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    horner_block(a.blocks, nblk, 0, Fr::zero(), a.zpow, 11, lds, loc, &ci);
-    // recompute the local chain from the true carry-in and store, for every entry, H of the NEXT entry
-    const Fr zb = a.zpow[11];
-    Fr h = ci;
-    const uint64_t s0 = (uint64_t)threadIdx.x * 8;
-    for (int e = 7; e >= 0; --e) {
-        if (s0 + e < nblk) p_st(a.blocks + s0 + e, h);
-        h = fe_add(loc[e], fe_mul(zb, h));
-    }
+    open_top_rounds(a.blocks, nblk, a.zpow, true, lds);
 }
 // sweep 2: seeded with the true carry; writes q and y
 __global__ __launch_bounds__(256) void open_finish_kernel(OpenArgs a) {
@@ -246,22 +261,10 @@ __global__ __launch_bounds__(256) void open_multi_block_kernel(OpenMultiArgs a) 
 }
 __global__ __launch_bounds__(256) void open_multi_top_kernel(OpenMultiArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
     const uint32_t k = blockIdx.x;
-    const Fr* zp = a.zpow[a.zsel[k]];
-    Fr* blocks = a.blocks + (uint64_t)k * a.nblk;
-    const Fr y = horner_block(blocks, a.nblk, 0, Fr::zero(), zp, 11, lds, loc, &ci);
-    if (!a.q[k]) {
-        if (threadIdx.x == 0) p_st(a.y[k], y);  // p(z) = sum_b A_b (z^2048)^b: an evaluation is complete here
-        return;
-    }
-    const Fr zb = zp[11];
-    Fr h = ci;
-    const uint64_t s0 = (uint64_t)threadIdx.x * 8;
-    for (int e = 7; e >= 0; --e) {
-        if (s0 + e < a.nblk) p_st(blocks + s0 + e, h);
-        h = fe_add(loc[e], fe_mul(zb, h));
-    }
+    const bool store = a.q[k] != nullptr;
+    const Fr y = open_top_rounds(a.blocks + (uint64_t)k * a.nblk, a.nblk, a.zpow[a.zsel[k]], store, lds);
+    if (!store && threadIdx.x == 0) p_st(a.y[k], y);  // p(z) = sum_b A_b (z^2048)^b: an evaluation is complete here
 }
 __global__ __launch_bounds__(256) void open_multi_finish_kernel(OpenMultiArgs a) {
     __shared__ Fr lds[256];

@@ -39,7 +39,7 @@ int quotient_extend_batch(typlonk_ctx* ctx, Fr* const* e, const Fr* const* src, 
 int typlonk_circuit_load(typlonk_ctx* ctx, const typlonk_buf* const selectors[5], const typlonk_buf* const sigma[3],
                          uint32_t log_n, uint32_t* circuit_id) {
     if (!ctx || !selectors || !sigma || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 22");
+    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
     HIPCHK(hipSetDevice(ctx->device));
     const uint64_t n = 1ull << log_n, n4 = 4 * n;
     const typlonk_buf* in[8] = {selectors[0], selectors[1], selectors[2], selectors[3], selectors[4],
@@ -113,7 +113,7 @@ int typlonk_quotient_dev(typlonk_ctx* ctx, const typlonk_quotient_args* args, ui
 
 namespace {
 int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out, uint32_t extended) {
-    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 22");
+    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
     HIPCHK(hipSetDevice(ctx->device));
     const uint64_t n = 1ull << log_n, n4 = 4 * n;
     const uint32_t log4 = log_n + 2;
@@ -213,7 +213,7 @@ int typlonk_grand_product_dev(typlonk_ctx* ctx, const typlonk_buf* const wires[3
                               uint32_t log_n, typlonk_buf* z_evals_out) {
     if (!ctx || !wires || !sigma || !beta || !gamma || !cosets || !z_evals_out)
         return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    if (log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "grand product needs log_n <= 22");
+    if (log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "grand product needs log_n <= 24");
     HIPCHK(hipSetDevice(ctx->device));
     const uint64_t n = 1ull << log_n;
     for (int i = 0; i < 3; ++i)
@@ -269,15 +269,17 @@ int typlonk_open_dev(typlonk_ctx* ctx, const typlonk_buf* poly, size_t offset, s
                      typlonk_buf* q_out, uint64_t y_out[4]) {
     if (!ctx || !poly || !z || !y_out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     if (m < 1) return fail(ctx, TYPLONK_ERR_LENGTH, "open needs at least 1 coefficient (kzg/src/lib.rs:58)");
-    if (m > (1u << 22)) return fail(ctx, TYPLONK_ERR_LENGTH, "open supports up to 2^22 coefficients");
+    if (m > ((size_t)1 << (TYPLONK_MAX_PROVER_LOG_N + 1))) return fail(ctx, TYPLONK_ERR_LENGTH, "open supports up to 2^25 coefficients");
     if (offset > poly->n || m > poly->n - offset) return fail(ctx, TYPLONK_ERR_RANGE, "range outside buffer");
     if (q_out && q_out->n < m - 1) return fail(ctx, TYPLONK_ERR_RANGE, "q_out shorter than m - 1");
     if (q_out && q_out->d == poly->d) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "q_out must not alias poly");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure(ctx, ctx->ops_tmp, (2048 + 8) * sizeof(Fr));
+    // one carry per 2048-coefficient workgroup (at least 2048 slots: the layout of m <= 2^22), then the result
+    const size_t nblk = std::max<size_t>((m + 2047) / 2048, 2048);
+    int rc = ensure(ctx, ctx->ops_tmp, (nblk + 8) * sizeof(Fr));
     if (rc) return rc;
     Fr* blocks = (Fr*)ctx->ops_tmp.p;
-    Fr* y_dev = blocks + 2048;
+    Fr* y_dev = blocks + nblk;
     Fr zz;
     memcpy(zz.v, z, 32);
     launch_open(poly->d + offset, m, zz, q_out ? q_out->d : nullptr, blocks, y_dev, ctx->stream);
@@ -348,15 +350,15 @@ int prover_extend(typlonk_prover* p, int k, const Fr* coeffs) {
     if (!rc) p->extended |= 1u << k;
     return rc;
 }
-// Scratch of the prover's openings: 8*2048 per-workgroup carries in ops_tmp, and 16 result slots.
+// Scratch of the prover's openings: 8 * max(2048, n / 2048) per-workgroup carries in ops_tmp, and 16 result slots.
 // The slots are only ever WRITTEN by kernels (p(z) of an opening) and read by the host, so they live in pinned host memory the
 // kernels store into directly: a fetch is one stream synchronisation, no copy.  (Device slots + hipMemcpyAsync into a stack
 // array -- pageable, so staged by the runtime -- left the GPU idle for ~170 us before the linearisation and ~120 us before
 // round 3's commitments, profiles/r06_prove_timeline.txt 15.50-15.67 and 15.89-16.02 ms.)
-constexpr size_t PROVER_EVAL_BLOCKS = 8 * 2048;
+constexpr size_t PROVER_EVAL_BLOCKS = 8 * 2048;   // n <= 2^22
 int prover_ops_tmp(typlonk_prover* p, Fr** blocks, Fr** slots) {
     typlonk_ctx* ctx = p->ctx;
-    int rc = ensure(ctx, ctx->ops_tmp, PROVER_EVAL_BLOCKS * sizeof(Fr));
+    int rc = ensure(ctx, ctx->ops_tmp, std::max<size_t>(PROVER_EVAL_BLOCKS, 8 * ((p->n + 2047) / 2048)) * sizeof(Fr));
     if (rc) return rc;
     if (!ctx->eval_slots_host) HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
     *blocks = (Fr*)ctx->ops_tmp.p;
@@ -432,7 +434,7 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     const uint64_t n = 1ull << log_n;
     int rc = msm_validate(ctx, srs_id, n, &srs);  // every committed polynomial has <= n coefficients
     if (rc) return rc;
-    if (n > (1u << 22)) return fail(ctx, TYPLONK_ERR_LENGTH, "prover supports up to 2^22 rows");
+    if (log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_LENGTH, "prover supports up to 2^24 rows");
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
     rc = ensure(ctx, ctx->prover_mem, (uint64_t)19 * n * sizeof(Fr));  // 3+3+1+1+4+6+1 vectors, kept across proofs
     if (rc) return rc;
