@@ -253,6 +253,14 @@ int typlonk_open_dev(typlonk_ctx* ctx, const typlonk_buf* poly, size_t offset, s
  * terms <= 12; every polys[k] holds >= n elements; out may alias none of them.  Stream-ordered. */
 int typlonk_lincomb_dev(typlonk_ctx* ctx, const typlonk_buf* const* polys, const uint64_t (*scalars)[4], size_t terms,
                         const uint64_t* constant, size_t n, typlonk_buf* out);
+/* out[(p * n_points + k) * 4 ..] = polys[p](points[k]) = sum_{i<m} polys[p][i] * points[k]^i, the value of
+ * DensePolynomial::evaluate (ark-poly, reached from permutation/src/lib.rs:165-176 and plonk/src/proof.rs:205-210).
+ * 1 <= m <= 2^25 coefficients from `offset` of each buffer; 1 <= count <= 16; n_points >= 1 (any count, processed in
+ * tiles).  Results are canonical Montgomery Fr, as typlonk_open_dev's y_out.  Blocks for the result.
+ * A point that is not a canonical residue (limbs >= r) returns TYPLONK_ERR_INVALID_ARG.  Workspace (grow-only): the points,
+ * the results and at most 128 MiB of per-chunk partial sums. */
+int typlonk_poly_eval_dev(typlonk_ctx* ctx, const typlonk_buf* const* polys, size_t count, size_t offset, size_t m,
+                          const uint64_t (*points)[4], size_t n_points, uint64_t* out);
 
 /* ---- the prover's device-side flow: plonk::proof::prove (/root/reference/plonk/src/proof.rs:26-57, 96-194)
  * split at its two Fiat-Shamir squeezes (challenges.rs is CPU-side and out of scope, so the caller
@@ -333,6 +341,44 @@ int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
 /* The transcript alone (host-only, no GPU): digest `count` commitments (C-ABI form) in order and squeeze
  * n_challenges Fr elements (4 Montgomery limbs each) -- ChallengeGenerator::with_digest(..).generate_challenges::<N>(). */
 int typlonk_transcript_challenges(const uint64_t* xy, const uint8_t* inf, size_t count, size_t n_challenges, uint64_t* out);
+
+/* ---- verify(): plonk::proof::verify (plonk/src/proof.rs:195-281, 441-503) on the device + host ------------------
+ * [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3]: the commitments of the eight per-circuit polynomials
+ * typlonk_circuit_load keeps (CircuitEntry::coef), one batch of eight MSMs over srs_id (>= n points, no shard set).
+ * Computed once per (circuit, srs) and cached with the circuit; GateConstrains::fixed_commitments (builder.rs) and
+ * CompiledPermutation::sigma_commitments (permutation/src/lib.rs:178-194).  An SRS shorter than n returns
+ * TYPLONK_ERR_LENGTH, a sharded one (typlonk_srs_set_shard) TYPLONK_ERR_INVALID_ARG. */
+int typlonk_circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[8][12], uint8_t inf[8]);
+
+/* `count` proofs of one circuit.  ok[k] = 1 iff proof k is accepted.
+ *   proofs   typlonk_prove's output; beta / gamma / alpha in it are ignored and recomputed from the commitments with the
+ *            transcript (proof.rs:236-246); zeta is the proof's evaluation_point and must equal the recomputed one (:212-214).
+ *   pi       pi[k] / pi_len[k]: host Fr column of proof k's public inputs, zero-padded to n by the library (either array or
+ *            entry may be NULL / 0 = all zero; pi_len[k] > n -> TYPLONK_ERR_LENGTH).  PI(zeta) = interpolate(pi).evaluate(zeta)
+ *            is a barycentric sum on the host for pi_len <= 2048, else an inverse NTT and typlonk_poly_eval_dev.
+ *   g2s_xy   [s]G2 as x.c0 x.c1 y.c0 y.c1 (24 limbs; Srs::g2s_ref, kzg/src/srs.rs); not on the twist -> TYPLONK_ERR_INVALID_ARG.
+ *            G2 is the fixed generator, and so is G1 in every KZG check (kzg/src/lib.rs:77); the linearisation's constant
+ *            term uses SRS point 0 (scheme.identity()).
+ *   flags    TYPLONK_VERIFY_PI_AS_PROVER: subtract PI(zeta), as the prover adds it to r (proof.rs:401-402).  Default: the
+ *            reference's sign (:497-502), with which the reference rejects its own honest proofs whenever PI(zeta) != 0.
+ * Per proof, on the host: the challenges, zeta, r(zeta) = 0 (:234-235) and that all 13 points lie on the curve (an in-memory
+ * arkworks point is trusted by the reference; garbage is rejected here rather than paired).  Such a proof gets ok = 0 and
+ * stays out of the rest.  On the device: sigma_1(zeta_k), sigma_2(zeta_k) for every proof in one typlonk_poly_eval_dev.
+ * The six KZG checks e(W_j, [s]G2 - z_j G2) = e(C_j - y_j G, G2) of every proof are folded with weights rho^(6k + j + 1)
+ * into e(sum rho_j W_j, [s]G2) * e(-sum rho_j (C_j + z_j W_j) + (sum rho_j y_j) G, G2) = 1: two MSMs on the device (the
+ * linearisation commitment expanded into its 11 bases) and ONE host pairing product for a batch that is all valid.
+ * rho = Blake2b-512 of the batch (n, [s]G2, the circuit's commitments, every proof's points, evaluations and PI(zeta),
+ * the flags) read as a little-endian integer mod r: deterministic.  When the fold fails it is bisected with the same
+ * weights, so every verdict is the per-proof decision of the reference (up to the fold's soundness error, <= 6 count / r);
+ * b bad proofs cost at most 2 b ceil(log2 count) + 1 pairing products.  Single GPU: a sharded SRS returns
+ * TYPLONK_ERR_INVALID_ARG.  Returns an error only for bad arguments or device failures; a bad proof is ok[k] = 0.
+ * count = 0 is a no-op.  With profiling on (typlonk_set_profiling), typlonk_profile_get reports the host wall time of the
+ * stages: "verify_host", "verify_eval", "verify_msm", "verify_pairing", then "verify_folds" -- the number of
+ * pairing products, a count, not milliseconds. */
+#define TYPLONK_VERIFY_PI_AS_PROVER 1u
+int typlonk_verify(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t g2s_xy[24],
+                   const uint64_t cosets[3][4], const typlonk_proof* proofs, size_t count,
+                   const uint64_t* const* pi, const size_t* pi_len, uint32_t flags, uint8_t* ok);
 
 /* ---- device-resident Fr vectors (so an iNTT result feeds an MSM without crossing PCIe) ---------- */
 int typlonk_buf_alloc(typlonk_ctx* ctx, size_t n_elems, typlonk_buf** out);

@@ -12,6 +12,7 @@
 //!                               plonk/src/proof.rs:50,106,115,125,128  plonk/src/builder.rs:85
 //!   * `Backend::load_circuit` + `Backend::prove`
 //!                               replace the body of `plonk::proof::prove`           plonk/src/proof.rs:96-194
+//!   * `Backend::verify_batch`   replaces `plonk::proof::verify` for a batch          plonk/src/proof.rs:195-281
 //!
 //! Data crosses the boundary in arkworks' own in-memory form (`Fp256.0 .0`: 4 LE u64 limbs of the Montgomery residue;
 //! `Fp384.0 .0`: 6), so nothing is converted -- coordinates are copied limb-wise because `GroupAffine` is `repr(Rust)`.
@@ -26,6 +27,8 @@ use std::ptr;
 
 pub type G1Point = G1Affine;
 pub type Poly = DensePolynomial<Fr>;
+/// `TYPLONK_VERIFY_PI_AS_PROVER` of include/typlonk.h (a flag of `typlonk_verify`)
+pub const VERIFY_PI_AS_PROVER: u32 = 1;
 
 /// One HIP device + stream + workspaces (`typlonk_ctx`).  It holds a raw pointer, so it is neither `Send` nor `Sync`
 /// -- and therefore neither is anything that embeds it (`kzg::srs::Srs`, `plonk::CompiledCircuit` after the patches):
@@ -301,6 +304,28 @@ impl Backend {
                                     k.as_ptr(), out.as_mut_ptr())
         });
         unsafe { out.assume_init() }
+    }
+
+    /// `plonk::proof::verify` (plonk/src/proof.rs:195-281) for a batch of `prove` outputs of one circuit
+    /// (`typlonk_verify`): one pairing product for a batch that is all valid, bisected down to the bad proofs otherwise.
+    /// `g2s` = [s]G2 as x.c0 x.c1 y.c0 y.c1 limbs; `public_inputs` empty or one column per proof (an empty column = all
+    /// zero); `pi_as_prover` subtracts PI(zeta) as the prover adds it (the default is the reference's sign, :497-502).
+    /// Returns one verdict per proof.
+    pub fn verify_batch(&self, srs: SrsHandle, circuit: CircuitHandle, g2s: &[u64; 24], cosets: [Fr; 3],
+                        proofs: &[ffi::TyplonkProof], public_inputs: &[Vec<Fr>], pi_as_prover: bool) -> Vec<bool> {
+        assert!(public_inputs.is_empty() || public_inputs.len() == proofs.len(), "one public-input column per proof");
+        let cols: Vec<Vec<u64>> = public_inputs.iter().map(|c| c.iter().flat_map(|e| fr_limbs(e)).collect()).collect();
+        let pis: Vec<*const u64> = cols.iter().map(|c| if c.is_empty() { ptr::null() } else { c.as_ptr() }).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|c| c.len()).collect();
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut ok = vec![0u8; proofs.len().max(1)];
+        self.check(unsafe {
+            ffi::typlonk_verify(self.ctx, srs.id, circuit.id, g2s.as_ptr(), k.as_ptr(), proofs.as_ptr(), proofs.len(),
+                                if pis.is_empty() { ptr::null() } else { pis.as_ptr() },
+                                if lens.is_empty() { ptr::null() } else { lens.as_ptr() },
+                                if pi_as_prover { VERIFY_PI_AS_PROVER } else { 0 }, ok.as_mut_ptr())
+        });
+        ok[..proofs.len()].iter().map(|&b| b != 0).collect()
     }
 
     // ---- multi-GPU: one process per GPU, RCCL inside the library --------------------------------------------------

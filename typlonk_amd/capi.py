@@ -30,7 +30,9 @@ SYMBOLS = [
     "typlonk_version",
     "typlonk_comm_available", "typlonk_comm_unique_id", "typlonk_comm_init", "typlonk_comm_destroy", "typlonk_comm_info", "typlonk_comm_fold_g1",
     "typlonk_msm_g1_sharded_devptr", "typlonk_msm_g1_sharded_batch_devptr", "typlonk_g1_fold_records_host",
+    "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify",
 ]
+VERIFY_PI_AS_PROVER = 1
 
 
 class TyplonkError(RuntimeError):
@@ -133,6 +135,10 @@ def load_library() -> C.CDLL:
     lib.typlonk_grand_product_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), u64p, u64p, C.POINTER((C.c_uint64 * 4) * 3),
                                               C.c_uint32, vp]
     lib.typlonk_open_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, u64p, vp, u64p]
+    lib.typlonk_poly_eval_dev.argtypes = [vp, C.POINTER(vp), C.c_size_t, C.c_size_t, C.c_size_t, u64p, C.c_size_t, u64p]
+    lib.typlonk_circuit_commitments.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u8p]
+    lib.typlonk_verify.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof),
+                                   C.c_size_t, C.POINTER(u64p), C.POINTER(C.c_size_t), C.c_uint32, u8p]
     lib.typlonk_lincomb_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64 * 4), C.c_size_t, u64p, C.c_size_t, vp]
     lib.typlonk_prover_round1.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp), vp, C.POINTER(vp),
                                           C.POINTER((C.c_uint64 * 12) * 3), C.POINTER(C.c_uint8 * 3)]
@@ -490,6 +496,71 @@ class Context:
         self._chk(self.lib.typlonk_open_dev(self.h, poly.handle, offset, m, _u64p(zz), q_out.handle if q_out else None,
                                             _u64p(y)))
         return y
+
+    def poly_eval_dev(self, polys, m: int, points, offset: int = 0) -> np.ndarray:
+        """typlonk_poly_eval_dev: (len(polys), len(points), 4) u64 -- polys[p] (DeviceBuffers, m coefficients from `offset`)
+        evaluated at every point (4-limb Montgomery arrays)"""
+        ptrs = (C.c_void_p * max(len(polys), 1))(*[b.handle.value for b in polys])
+        pts = np.ascontiguousarray(_as_u64(points, 4))
+        out = np.zeros((max(len(polys), 1), max(pts.shape[0], 1), 4), dtype=np.uint64)
+        self._chk(self.lib.typlonk_poly_eval_dev(self.h, ptrs, len(polys), offset, m, _u64p(pts), pts.shape[0], _u64p(out)))
+        return out
+
+    def circuit_commitments(self, sid: int, circuit: int):
+        """typlonk_circuit_commitments: [(xy[12], inf)] * 8 -- [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3]"""
+        xy = np.zeros((8, 12), dtype=np.uint64)
+        inf = np.zeros(8, dtype=np.uint8)
+        self._chk(self.lib.typlonk_circuit_commitments(self.h, sid, circuit, _u64p(xy), _u8p(inf)))
+        return [(xy[i].copy(), int(inf[i])) for i in range(8)]
+
+    @staticmethod
+    def proof_struct(d) -> "Proof":
+        """a prove_native dict -> typlonk_proof (beta / gamma / alpha are not needed by the verifier and stay zero)"""
+        pr = Proof()
+        for i, (xy, f) in enumerate(d["commit"]):
+            pr.commit_xy[i][:] = [int(v) for v in np.asarray(xy, dtype=np.uint64).reshape(12)]
+            pr.commit_inf[i] = int(f)
+        pr.z_xy[:] = [int(v) for v in np.asarray(d["z_commit"][0], dtype=np.uint64).reshape(12)]
+        pr.z_inf = int(d["z_commit"][1])
+        for i, (xy, f) in enumerate(d["t_commit"]):
+            pr.tail.t_xy[i][:] = [int(v) for v in np.asarray(xy, dtype=np.uint64).reshape(12)]
+            pr.tail.t_inf[i] = int(f)
+        for i, (xy, f) in enumerate(d["witness"]):
+            pr.tail.w_xy[i][:] = [int(v) for v in np.asarray(xy, dtype=np.uint64).reshape(12)]
+            pr.tail.w_inf[i] = int(f)
+        for i, e in enumerate(d["evals"]):
+            pr.tail.evals[i][:] = [int(v) for v in np.asarray(e, dtype=np.uint64).reshape(4)]
+        pr.zeta[:] = [int(v) for v in np.asarray(d["challenges"]["zeta"], dtype=np.uint64).reshape(4)]
+        return pr
+
+    def verify(self, sid: int, circuit: int, g2s_xy, cosets, proofs, pi=None, pi_as_prover: bool = False) -> np.ndarray:
+        """typlonk_verify: proofs = dicts as prove_native returns them (or Proof structs); g2s_xy = 24 limbs of [s]G2
+        (x.c0 x.c1 y.c0 y.c1); pi = None or one entry per proof, each None or an (l, 4) u64 column (l <= n, zero-padded).
+        Returns a bool array, True = accepted."""
+        k = len(proofs)
+        arr = (Proof * max(k, 1))()
+        for i, p in enumerate(proofs):
+            arr[i] = p if isinstance(p, Proof) else self.proof_struct(p)
+        g2 = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
+        ks = ((C.c_uint64 * 4) * 3)()
+        for i in range(3):
+            for j, limb in enumerate(np.asarray(cosets[i], dtype=np.uint64).reshape(4)):
+                ks[i][j] = int(limb)
+        keep, pip, lens = [], None, None
+        if pi is not None:
+            pip = (C.POINTER(C.c_uint64) * max(k, 1))()
+            lens = (C.c_size_t * max(k, 1))()
+            for i, col in enumerate(pi):
+                if col is None:
+                    continue
+                c = np.ascontiguousarray(_as_u64(col, 4))
+                keep.append(c)
+                pip[i] = _u64p(c)
+                lens[i] = c.shape[0]
+        ok = np.zeros(max(k, 1), dtype=np.uint8)
+        self._chk(self.lib.typlonk_verify(self.h, sid, circuit, _u64p(g2), C.byref(ks), arr, k, pip, lens,
+                                          VERIFY_PI_AS_PROVER if pi_as_prover else 0, _u8p(ok)))
+        return ok[:k].astype(bool)
 
     def lincomb_dev(self, polys, scalars, n: int, out: DeviceBuffer, constant=None):
         k = len(polys)

@@ -58,6 +58,12 @@ struct CircuitEntry {
     Fr* coef = nullptr;    // 8 * n  : coefficient copies of the selectors and sigmas (linearisation, sigma(zeta))
     Fr* sig_ev = nullptr;  // 3 * n  : sigma evaluations over the domain (grand product)
     uint32_t log_n = 0;
+    // typlonk_circuit_commitments: the eight commitments of `coef`, computed once per SRS id (ids are never reused)
+    struct Commitments {
+        uint64_t xy[8][12];
+        uint8_t inf[8];
+    };
+    std::map<uint32_t, Commitments> commitments;
 };
 
 struct ProfStage {
@@ -170,6 +176,7 @@ struct typlonk_ctx {
     bool msm_rc4 = false;          // always the four-launch row/column reduction
     // NTT
     tyh::DevBuf ntt_scratch, ntt_io, quot_ext, quot_tab, ops_tmp, prover_mem;
+    tyh::DevBuf eval_ws;           // typlonk_poly_eval_dev: points, results and chunk partials (poly_eval.hip)
     bool prover_busy = false;  // one proof in flight per context (the arena above is shared)
     int prover_rounds_active = 0;  // > 0 while a typlonk_prover_round* call is running (ProverRound)
     std::map<std::string, tyh::Table> tables;
@@ -325,6 +332,12 @@ struct MsmQueue {
     int submit(const Fr* d_scalars, size_t m, uint64_t* out_xy, uint8_t* out_inf, bool standalone = false);
     int wait_all();
 };
+
+// ---- poly_eval.hip / verify.hip ----------------------------------------------------------------------------------------
+// out[(p * n_points + k) * 4 ..] = polys[p](points[k]) over m coefficients each (device pointers; points / out on the host,
+// 4 Montgomery limbs per element).  Blocks for the result.
+int poly_eval_run(typlonk_ctx* ctx, const Fr* const* polys, size_t count, uint64_t m, const uint64_t* points, size_t n_points,
+                  uint64_t* out);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------
 void comm_release(typlonk_ctx* ctx);

@@ -640,6 +640,58 @@ class CompiledCircuit {
         return scheme.verify(r, proof.r, point) && proof.r.eval().is_zero();
     }
 
+    // The same decision for a batch through the C ABI (typlonk_verify): sigma and long public-input columns evaluated on the
+    // device, the six KZG checks of every proof folded into one pairing product, bisected when it fails.  result[k] is
+    // verify(proofs[k], public_inputs[k], pi_sign) -- the G2 generator is the fixed one (an Srs whose g2 was replaced with
+    // set_g2 is not supported).  public_inputs: empty, or one column per proof (each empty = all zero, at most n values).
+    std::vector<bool> verify_batch(const std::vector<Proof>& proofs, const std::vector<std::vector<Fr>>& public_inputs = {},
+                                   PublicInputSign pi_sign = PublicInputSign::AsReference) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        if (!public_inputs.empty() && public_inputs.size() != proofs.size())
+            throw std::runtime_error("one public-input column per proof");
+        std::vector<typlonk_proof> raw(proofs.size());
+        auto pt = [](const kzg::G1Point& g, uint64_t xy[12], uint8_t* inf) {
+            std::memcpy(xy, g.xy, 96);
+            *inf = g.infinity ? 1 : 0;
+        };
+        for (size_t k = 0; k < proofs.size(); ++k) {
+            const Proof& p = proofs[k];
+            typlonk_proof& r = raw[k];
+            std::memset(&r, 0, sizeof(r));
+            pt(p.a_commit.p, r.commit_xy[0], &r.commit_inf[0]);
+            pt(p.b_commit.p, r.commit_xy[1], &r.commit_inf[1]);
+            pt(p.c_commit.p, r.commit_xy[2], &r.commit_inf[2]);
+            pt(p.permutation.commitment.p, r.z_xy, &r.z_inf);
+            for (int i = 0; i < 3; ++i) pt(p.t[i].p, r.tail.t_xy[i], &r.tail.t_inf[i]);
+            const kzg::KzgOpening* op[6] = {&p.a, &p.b, &p.c, &p.permutation.z, &p.permutation.zw, &p.r};
+            for (int i = 0; i < 6; ++i) {
+                pt(op[i]->p, r.tail.w_xy[i], &r.tail.w_inf[i]);
+                std::memcpy(r.tail.evals[i], op[i]->y.limbs(), 32);
+            }
+            std::memcpy(r.zeta, p.evaluation_point.limbs(), 32);
+        }
+        uint64_t g2s[24];
+        const pairing::G2Affine& q = srs_.g2s();
+        std::memcpy(g2s, q.x.a.v, 48);
+        std::memcpy(g2s + 6, q.x.b.v, 48);
+        std::memcpy(g2s + 12, q.y.a.v, 48);
+        std::memcpy(g2s + 18, q.y.b.v, 48);
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        std::vector<const uint64_t*> pis(proofs.size(), nullptr);
+        std::vector<size_t> lens(proofs.size(), 0);
+        for (size_t k = 0; k < public_inputs.size(); ++k)
+            if (!public_inputs[k].empty()) {
+                pis[k] = public_inputs[k][0].limbs();
+                lens[k] = public_inputs[k].size();
+            }
+        std::vector<uint8_t> ok(proofs.size() + 1, 0);
+        check(typlonk_verify(c, srs_.id(), circuit_, g2s, ks, raw.data(), raw.size(), pis.data(), lens.data(),
+                             pi_sign == PublicInputSign::AsProver ? TYPLONK_VERIFY_PI_AS_PROVER : 0u, ok.data()),
+              c);
+        return std::vector<bool>(ok.begin(), ok.begin() + proofs.size());
+    }
+
    private:
     typlonk_buf* upload(const std::vector<Fr>& v) const {
         typlonk_ctx* c = srs_.ctx().raw();
