@@ -213,6 +213,9 @@ int typlonk_ntt_fr_batch_devptr(typlonk_ctx* ctx, void* const* d_data, size_t co
  *   ntt_scratch (a 2^25 / 2^26 batch)      1.0 GiB    1.0 GiB    2.0 GiB
  *   SRS of n + 3 points with c = 20 tables 6.5 GiB   13.0 GiB   26.0 GiB   (13 x 128 B per point)
  *   total                                 18.8 GiB   36.5 GiB   73.0 GiB   plus twiddle / coset tables and MSM workspaces
+ * typlonk_prove_batch keeps one wave's arena in prover_mem instead (39 n Fr per proof in flight, one proof per wave here):
+ *   prover_mem (39 n Fr)                   4.9 GiB    9.8 GiB   19.5 GiB   (quot_ext is not used by a batch)
+ *   ops_tmp (8 n / 2048 Fr) + slots        4 MiB      8 MiB     16 MiB
  * (typlonk_srs_precompute itself needs another (T - 1) x 48 B per point while it runs: 9.0 GiB at 2^24 + 3.) */
 #define TYPLONK_MAX_PROVER_LOG_N 24
 typedef struct typlonk_quotient_args {
@@ -338,6 +341,31 @@ int typlonk_prove(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const 
  * (128 MiB of uploads at 2^20 that a caller of typlonk_prove pays before the first kernel starts).  Same proof, bit for bit. */
 int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
                        const uint64_t* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out);
+/* ---- prove() for many witnesses of one circuit in one call, batched across proofs.
+ * out[k] is bit for bit what typlonk_prove (typlonk_prove_host) returns for witness k -- commitments, evaluations, openings
+ * and the four challenges; each proof keeps its own transcript.  Reference proof shape only (six openings).
+ *   wire_evals  count x 3 columns, proof-major (wire_evals[3 k + i] = column i of proof k), n = 2^log_n Fr each
+ *   pi_evals    count entries, or NULL (every public-input column zero); an entry may be NULL (that proof's column is zero)
+ *   status[k]   TYPLONK_OK, or TYPLONK_ERR_UNSATISFIED when r(zeta) != 0 for witness k: out[k] is filled exactly as
+ *               typlonk_prove fills it, and the other proofs are not affected
+ * The return value reports only bad arguments and device failures; count = 0 is a no-op.  Single GPU: a sharded SRS (or
+ * a context whose communicator would fold) returns TYPLONK_ERR_INVALID_ARG, an SRS shorter than n TYPLONK_ERR_LENGTH.  A
+ * call while a round-by-round prover (typlonk_prover_round1 .. typlonk_prover_free) is open is refused with
+ * TYPLONK_ERR_INVALID_ARG.
+ * The proofs run in waves of G = min(count, 64, max(1, 2^22 >> log_n)) -- 64 proofs at 2^16, 4 at 2^20, 1 from 2^22 on --,
+ * any count is accepted.  Every stage of a wave is batched across its proofs (transforms, grand products, openings, the
+ * quotient, the linearisation, each round's commitments), and the host waits three times per wave plus one final read.
+ * HBM kept after a batch (grow-only, per proof in flight, n = 2^log_n rows; 32 B per Fr):
+ *   prover_mem  39 n Fr per proof of a wave: the 19 n of typlonk_prove's arena + the 5 x 4n coset extensions
+ *               (2^16: 64 x 80 MiB = 5.0 GiB; 2^20: 4 x 1.2 GiB = 4.9 GiB; 2^22: 4.9 GiB; 2^24: 19.5 GiB)
+ *   ops_tmp     8 n / 2048 Fr per proof (the openings' carries); 16 pinned result slots per proof; ~200 KiB of tables */
+int typlonk_prove_batch(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
+                        const typlonk_buf* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
+                        int* status);
+/* The same with the columns in HOST memory (as typlonk_prove_host): wire_evals[3 k + i] and pi_evals[k] point at n Fr. */
+int typlonk_prove_batch_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
+                             const uint64_t* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
+                             int* status);
 /* The transcript alone (host-only, no GPU): digest `count` commitments (C-ABI form) in order and squeeze
  * n_challenges Fr elements (4 Montgomery limbs each) -- ChallengeGenerator::with_digest(..).generate_challenges::<N>(). */
 int typlonk_transcript_challenges(const uint64_t* xy, const uint8_t* inf, size_t count, size_t n_challenges, uint64_t* out);

@@ -306,6 +306,34 @@ impl Backend {
         unsafe { out.assume_init() }
     }
 
+    /// `prove` for many witnesses of one circuit in one call (`typlonk_prove_batch_host`, batched across proofs in waves):
+    /// `wire_evals[k]` and `public_inputs[k]` as for `prove` (`public_inputs` empty = every column zero).  Returns each
+    /// proof with its status: `TYPLONK_OK`, or `TYPLONK_ERR_UNSATISFIED` for a witness with r(zeta) != 0 (its proof is
+    /// filled all the same and will not verify) -- no panic for those.  Proof k equals `prove` on witness k, bit for bit.
+    pub fn prove_batch(&self, srs: SrsHandle, circuit: CircuitHandle, wire_evals: &[[&[Fr]; 3]], public_inputs: &[&[Fr]],
+                       cosets: [Fr; 3]) -> Vec<(ffi::TyplonkProof, i32)> {
+        assert!(public_inputs.is_empty() || public_inputs.len() == wire_evals.len(), "one public-input column per witness");
+        let n = 1usize << circuit.log_n;
+        let flat = |c: &[Fr]| -> Vec<u64> {
+            assert_eq!(c.len(), n);
+            c.iter().flat_map(|e| fr_limbs(e)).collect()
+        };
+        let w: Vec<Vec<u64>> = wire_evals.iter().flat_map(|cols| cols.iter().map(|c| flat(c))).collect();
+        let wp: Vec<*const u64> = w.iter().map(|c| c.as_ptr()).collect();
+        let pi: Vec<Option<Vec<u64>>> = public_inputs.iter()
+            .map(|c| if c.iter().all(|x| x.is_zero()) { None } else { Some(flat(c)) }).collect();
+        let pp: Vec<*const u64> = pi.iter().map(|c| c.as_ref().map_or(ptr::null(), |v| v.as_ptr())).collect();
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let count = wire_evals.len();
+        let mut out: Vec<ffi::TyplonkProof> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+        let mut status = vec![0i32; count];
+        self.check(unsafe {
+            ffi::typlonk_prove_batch_host(self.ctx, srs.id, circuit.id, wp.as_ptr(), if pp.is_empty() { ptr::null() } else { pp.as_ptr() },
+                                          count, k.as_ptr(), out.as_mut_ptr(), status.as_mut_ptr())
+        });
+        out.into_iter().zip(status).collect()
+    }
+
     /// `plonk::proof::verify` (plonk/src/proof.rs:195-281) for a batch of `prove` outputs of one circuit
     /// (`typlonk_verify`): one pairing product for a batch that is all valid, bisected down to the bad proofs otherwise.
     /// `g2s` = [s]G2 as x.c0 x.c1 y.c0 y.c1 limbs; `public_inputs` empty or one column per proof (an empty column = all

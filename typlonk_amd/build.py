@@ -4,7 +4,7 @@
   tests/cpp/hooks/libtyplonk_hip.so  the same library with the fault-injection hook (-DTYPLONK_TEST_HOOKS, tests only) -- hipcc
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
-  tests/cpp/test_{poly,kzg,plonk}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
+  tests/cpp/test_{poly,kzg,plonk,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
 Every target is rebuilt only when one of its sources is newer than the output.
 """
@@ -38,7 +38,7 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -147,7 +147,7 @@ def build_host_tests(force: bool = False) -> list[str]:
            os.path.join(CSRC, "ff.hpp"), os.path.join(CSRC, "fq30.hpp"), os.path.join(CSRC, "g1_host64.hpp"),
            os.path.join(CSRC, "transcript.hpp"), LIB]
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
-                 "test_comm_host", "test_comm_ranks_host", "test_verify_host"):
+                 "test_comm_host", "test_comm_ranks_host", "test_verify_host", "test_prove_batch_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
         if force or _stale(out, [src] + hdr):

@@ -30,7 +30,7 @@ SYMBOLS = [
     "typlonk_version",
     "typlonk_comm_available", "typlonk_comm_unique_id", "typlonk_comm_init", "typlonk_comm_destroy", "typlonk_comm_info", "typlonk_comm_fold_g1",
     "typlonk_msm_g1_sharded_devptr", "typlonk_msm_g1_sharded_batch_devptr", "typlonk_g1_fold_records_host",
-    "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify",
+    "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify", "typlonk_prove_batch", "typlonk_prove_batch_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 
@@ -149,6 +149,11 @@ def load_library() -> C.CDLL:
     lib.typlonk_prove.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp), vp, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof)]
     if hasattr(lib, "typlonk_prove_host") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
         lib.typlonk_prove_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(u64p), u64p, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof)]
+    if hasattr(lib, "typlonk_prove_batch") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_prove_batch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.c_size_t,
+                                            C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof), C.POINTER(C.c_int)]
+        lib.typlonk_prove_batch_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(u64p), C.POINTER(u64p), C.c_size_t,
+                                                 C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof), C.POINTER(C.c_int)]
     lib.typlonk_transcript_challenges.argtypes = [u64p, u8p, C.c_size_t, C.c_size_t, u64p]
     lib.typlonk_prover_free.argtypes = [vp]
     lib.typlonk_prover_free.restype = None
@@ -677,6 +682,52 @@ class Context:
             "evals": [np.array(t.evals[i], dtype=np.uint64) for i in range(6)],
             "challenges": {k: np.array(getattr(pr, k), dtype=np.uint64) for k in ("beta", "gamma", "alpha", "zeta")},
         }
+
+    @staticmethod
+    def _proof_dict(pr) -> dict:
+        t = pr.tail
+        return {
+            "commit": [(np.array(pr.commit_xy[i], dtype=np.uint64), int(pr.commit_inf[i])) for i in range(3)],
+            "z_commit": (np.array(pr.z_xy, dtype=np.uint64), int(pr.z_inf)),
+            "t_commit": [(np.array(t.t_xy[i], dtype=np.uint64), int(t.t_inf[i])) for i in range(3)],
+            "witness": [(np.array(t.w_xy[i], dtype=np.uint64), int(t.w_inf[i])) for i in range(6)],
+            "evals": [np.array(t.evals[i], dtype=np.uint64) for i in range(6)],
+            "challenges": {k: np.array(getattr(pr, k), dtype=np.uint64) for k in ("beta", "gamma", "alpha", "zeta")},
+        }
+
+    def prove_batch(self, sid: int, circuit: int, wire_evals, pi_evals, cosets):
+        """typlonk_prove_batch: wire_evals = one [a, b, c] list of DeviceBuffers per proof; pi_evals = None or one entry per
+        proof (a DeviceBuffer or None).  Returns (proofs, statuses): the dicts prove_native returns, and per proof OK or
+        ERR_UNSATISFIED (that proof's dict is filled all the same)."""
+        k = len(wire_evals)
+        w = (C.c_void_p * max(3 * k, 1))(*[b.handle.value for cols in wire_evals for b in cols])
+        pi = None
+        if pi_evals is not None:
+            pi = (C.c_void_p * max(k, 1))(*[b.handle.value if b is not None else None for b in pi_evals])
+        return self._prove_batch(self.lib.typlonk_prove_batch, sid, circuit, w, pi, k, cosets)
+
+    def prove_batch_host(self, sid: int, circuit: int, wire_evals_host, pi_evals_host, cosets):
+        """typlonk_prove_batch_host: the columns are (n, 4) u64 host arrays, one [a, b, c] list per proof; pi_evals_host =
+        None or one entry per proof (an array or None).  Same result as prove_batch."""
+        k = len(wire_evals_host)
+        keep = [np.ascontiguousarray(_as_u64(c, 4)) for cols in wire_evals_host for c in cols]
+        w = (C.POINTER(C.c_uint64) * max(3 * k, 1))(*[_u64p(c) for c in keep])
+        pi = None
+        if pi_evals_host is not None:
+            pis = [np.ascontiguousarray(_as_u64(c, 4)) if c is not None else None for c in pi_evals_host]
+            keep += [c for c in pis if c is not None]
+            pi = (C.POINTER(C.c_uint64) * max(k, 1))(*[_u64p(c) if c is not None else None for c in pis])
+        return self._prove_batch(self.lib.typlonk_prove_batch_host, sid, circuit, w, pi, k, cosets)
+
+    def _prove_batch(self, fn, sid, circuit, w, pi, k, cosets):
+        ks = ((C.c_uint64 * 4) * 3)()
+        for i in range(3):
+            for j, limb in enumerate(np.asarray(cosets[i], dtype=np.uint64).reshape(4)):
+                ks[i][j] = int(limb)
+        out = (Proof * max(k, 1))()
+        st = (C.c_int * max(k, 1))()
+        self._chk(fn(self.h, sid, circuit, w, pi, k, C.byref(ks), out, st))
+        return [self._proof_dict(out[i]) for i in range(k)], [int(st[i]) for i in range(k)]
 
     def circuit_load(self, log_n: int, selectors, sigma) -> int:
         sel = (C.c_void_p * 5)(*[b.handle.value for b in selectors])

@@ -121,7 +121,9 @@ void typlonk_destroy(typlonk_ctx* ctx) {
     }
     for (auto& kv : ctx->tables) (void)hipFree(kv.second.d);
     if (ctx->eval_slots_host) (void)hipHostFree(ctx->eval_slots_host);
-    for (DevBuf* b : {&ctx->srs_comb, &ctx->scal, &ctx->ntt_scratch, &ctx->ntt_io, &ctx->quot_ext, &ctx->quot_tab, &ctx->ops_tmp, &ctx->prover_mem, &ctx->eval_ws}) release(*b);
+    if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
+    for (DevBuf* b : {&ctx->srs_comb, &ctx->scal, &ctx->ntt_scratch, &ctx->ntt_io, &ctx->quot_ext, &ctx->quot_tab, &ctx->ops_tmp, &ctx->prover_mem, &ctx->eval_ws,
+                      &ctx->batch_tab}) release(*b);
     for (MsmWs& ws : ctx->ws) {
         for (SortBufs& sb : ws.sb)
             for (DevBuf* b : sb.all()) release(*b);

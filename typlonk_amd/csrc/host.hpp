@@ -4,6 +4,7 @@
 //   msm_host.hip  MSM staging (sort / accumulate / reduce launches, lanes of a batch, host finish) + SRS + typlonk_msm_*
 //   comm.hip      RCCL exchange behind the C ABI
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove
+//   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -168,7 +169,8 @@ struct typlonk_ctx {
     // 0.419 -> 0.464 ms per MSM -- so the switch sits below the shard size; from 2^19 on the chain is never worse and
     // 2^20 needs it.  -1 = by term count (MSM_CHAIN_MIN_TERMS), 0 / 1 = TYPLONK_MSM_CHAIN.
     int msm_chain = -1;
-    tyh::Fr* eval_slots_host = nullptr;  // 16 pinned, device-visible result slots (prover_ops_tmp)
+    tyh::Fr* eval_slots_host = nullptr;  // pinned, device-visible result slots: 16 (prover_ops_tmp), 16 per proof of a wave
+    size_t eval_slots_cap = 0;           // (typlonk_prove_batch grows them)
     int msm_chunks = 0;            // chunks of a stand-alone MSM (0 = choose by length)
     int msm_lanes = 0;             // lanes per bucket of the accumulation (0 = choose by bucket load)
     bool msm_scatter_staged = true;  // TYPLONK_MSM_SCATTER=direct: level 1 of the bucket sort writes every entry straight to global
@@ -177,6 +179,8 @@ struct typlonk_ctx {
     // NTT
     tyh::DevBuf ntt_scratch, ntt_io, quot_ext, quot_tab, ops_tmp, prover_mem;
     tyh::DevBuf eval_ws;           // typlonk_poly_eval_dev: points, results and chunk partials (poly_eval.hip)
+    tyh::DevBuf batch_tab;         // typlonk_prove_batch: per-proof scalars and item tables of a wave (device copy of batch_host)
+    void* batch_host = nullptr;    // pinned staging of batch_tab (PROVE_BATCH_TAB_BYTES)
     bool prover_busy = false;  // one proof in flight per context (the arena above is shared)
     int prover_rounds_active = 0;  // > 0 while a typlonk_prover_round* call is running (ProverRound)
     std::map<std::string, tyh::Table> tables;
@@ -332,6 +336,15 @@ struct MsmQueue {
     int submit(const Fr* d_scalars, size_t m, uint64_t* out_xy, uint8_t* out_inf, bool standalone = false);
     int wait_all();
 };
+
+// ---- prover.hip: the linearisation polynomial r (proof.rs:376-439), shared by typlonk_prove and typlonk_prove_batch ------
+// What it needs of zeta alone: zeta^n, Z_H(zeta) = zeta^n - 1 and L0(zeta) (one host inversion).
+void lin_zeta_terms(const Fr& zeta, uint32_t log_n, Fr* zn, Fr* zh, Fr* l0z);
+// r = sum_k scalar[k] * poly_k + constant, the ten polynomials in this order: q_l q_r q_o q_m q_c, Z, sigma_2, t_lo, t_mid,
+// t_hi.  ev[0..4] = a, b, c, Z at zeta (Z(zeta) unused) and Z at zeta w; s0, s1 = sigma_0, sigma_1 at zeta; pi_z = PI(zeta).
+constexpr int LIN_TERMS = 10;
+void lin_scalars(const Fr* ev, const Fr& s0, const Fr& s1, const Fr& pi_z, const Fr& beta, const Fr& gamma, const Fr (&k)[3],
+                 const Fr& alpha, const Fr& zeta, const Fr& zn, const Fr& zh, const Fr& l0z, Fr* scalar /* LIN_TERMS */, Fr* constant);
 
 // ---- poly_eval.hip / verify.hip ----------------------------------------------------------------------------------------
 // out[(p * n_points + k) * 4 ..] = polys[p](points[k]) over m coefficients each (device pointers; points / out on the host,

@@ -12,22 +12,9 @@
 // the same field element the reference computes.
 #include "fr_inv.hpp"
 #include "launch.hpp"
+#include "scan_ops.hpp"
 
 namespace ty {
-
-__device__ __forceinline__ Fr p_ld(const Fr* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-__device__ __forceinline__ void p_st(Fr* p, const Fr& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 // num_j = prod_i (w_ij + beta k_i w^j + gamma),  den_j = prod_i (w_ij + beta sigma_ij + gamma)
 __global__ __launch_bounds__(256) void gp_terms_kernel(GrandProductArgs a) {
@@ -46,86 +33,14 @@ __global__ __launch_bounds__(256) void gp_terms_kernel(GrandProductArgs a) {
     p_st(a.den + j, den);
 }
 
-// ---- product scan over Fr: three launches, 2048 elements per workgroup (8 per thread) ----------------
-// reverse = 0: out[j] = prod_{k<j} in[k] (exclusive prefix);  reverse = 1: out[j] = prod_{k>=j} in[k]
-constexpr int PSCAN_PER_BLOCK = 2048;
-
-__device__ __forceinline__ uint64_t pscan_index(uint64_t pos, uint64_t n, int reverse) { return reverse ? n - 1 - pos : pos; }
-
+// ---- product scan over Fr: three launches, 2048 elements per workgroup (8 per thread); the bodies are in scan_ops.hpp
 __global__ __launch_bounds__(256) void pscan_block_kernel(const Fr* in, uint64_t n, int reverse, Fr* block_prod) {
-    __shared__ Fr red[256];
-    const uint64_t base = (uint64_t)blockIdx.x * PSCAN_PER_BLOCK + threadIdx.x * 8;
-    Fr p = Fr::one();
-    for (int e = 0; e < 8; ++e)
-        if (base + e < n) p = fe_mul(p, p_ld(in + pscan_index(base + e, n, reverse)));
-    red[threadIdx.x] = p;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] = fe_mul(red[threadIdx.x], red[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) p_st(block_prod + blockIdx.x, red[0]);
+    pscan_block(in, n, reverse, block_prod, blockIdx.x);
 }
-// single workgroup: exclusive scan of the block products in place (sequential over chunks of 256)
-__global__ __launch_bounds__(256) void pscan_top_kernel(Fr* block_prod, uint32_t nblocks) {
-    __shared__ Fr buf[256];
-    __shared__ Fr running;
-    if (threadIdx.x == 0) running = Fr::one();
-    __syncthreads();
-    for (uint32_t base = 0; base < nblocks; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const Fr v = i < nblocks ? p_ld(block_prod + i) : Fr::one();
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            Fr t = Fr::one();
-            if ((int)threadIdx.x >= off) t = buf[threadIdx.x - off];
-            __syncthreads();
-            buf[threadIdx.x] = fe_mul(buf[threadIdx.x], t);
-            __syncthreads();
-        }
-        // exclusive value = running * (inclusive of the previous lane)
-        Fr excl = running;
-        if (threadIdx.x > 0) excl = fe_mul(running, buf[threadIdx.x - 1]);
-        const Fr total = fe_mul(running, buf[255]);
-        if (i < nblocks) p_st(block_prod + i, excl);
-        __syncthreads();
-        if (threadIdx.x == 0) running = total;
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(256) void pscan_top_kernel(Fr* block_prod, uint32_t nblocks) { pscan_top(block_prod, nblocks); }
 __global__ __launch_bounds__(256) void pscan_finish_kernel(const Fr* in, uint64_t n, int reverse, const Fr* block_excl,
                                                            Fr* out) {
-    __shared__ Fr buf[256];
-    const uint64_t base = (uint64_t)blockIdx.x * PSCAN_PER_BLOCK + threadIdx.x * 8;
-    Fr v[8];
-    Fr p = Fr::one();
-    for (int e = 0; e < 8; ++e) {
-        v[e] = base + e < n ? p_ld(in + pscan_index(base + e, n, reverse)) : Fr::one();
-        p = fe_mul(p, v[e]);
-    }
-    buf[threadIdx.x] = p;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        Fr t = Fr::one();
-        if ((int)threadIdx.x >= off) t = buf[threadIdx.x - off];
-        __syncthreads();
-        buf[threadIdx.x] = fe_mul(buf[threadIdx.x], t);
-        __syncthreads();
-    }
-    Fr run = p_ld(block_excl + blockIdx.x);
-    if (threadIdx.x > 0) run = fe_mul(run, buf[threadIdx.x - 1]);
-    for (int e = 0; e < 8; ++e) {
-        if (base + e < n) {
-            if (reverse) {
-                run = fe_mul(run, v[e]);  // inclusive in scan order = product of in[k], k >= index
-                p_st(out + pscan_index(base + e, n, 1), run);
-            } else {
-                p_st(out + base + e, run);  // exclusive prefix
-                run = fe_mul(run, v[e]);
-            }
-        }
-    }
+    pscan_finish(in, n, reverse, block_excl, out, blockIdx.x);
 }
 
 // out[0] = in[0]^-1 (0 -> 0): one wavefront, every lane the same value -- the ONE inversion of a proof's grand product
@@ -141,37 +56,7 @@ __global__ __launch_bounds__(256) void gp_finish_kernel(const Fr* nprefix, const
     p_st(z + j, fe_mul(fe_mul(p_ld(nprefix + j), p_ld(dsuffix + j)), p_ld(inv_total)));
 }
 
-// ---- open(): H_j = c_j + z H_{j+1} (H_m = 0) for all j at once ------------------------------------------
-// y = p(z) = H_0 and (p - y) / (X - z) has coefficients q_{j-1} = H_j: Horner evaluation and synthetic
-// division are the same suffix recurrence.  A thread owns 8 consecutive coefficients, a workgroup
-// 2048; inside the workgroup the per-thread values are combined by a Hillis-Steele suffix scan with
-// ratio z^8 (multipliers z^(8*2^k) come precomputed as zpow[3+k]).  `seed` is the value of H at the END
-// of the workgroup's range (0 in the first sweep, the scanned carry in the second).
-__device__ __forceinline__ Fr horner_block(const Fr* c, uint64_t m, uint64_t base, const Fr& seed, const Fr* zpow,
-                                           int pow0, Fr* lds, Fr (&loc)[8], Fr* carry_in) {
-    // local Horner over [base + 8t, base + 8t + 8); the last thread starts from the seed
-    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
-    Fr h = (threadIdx.x == 255) ? seed : Fr::zero();
-    const Fr z = zpow[pow0];
-    for (int e = 7; e >= 0; --e) {
-        loc[e] = (s0 + e < m) ? p_ld(c + s0 + e) : Fr::zero();
-        h = fe_add(loc[e], fe_mul(z, h));
-    }
-    lds[threadIdx.x] = h;
-    __syncthreads();
-    // G_t = sum_{t' >= t} h_t' (z^8)^(t' - t)
-    for (int k = 0; k < 8; ++k) {
-        const int off = 1 << k;
-        Fr add = Fr::zero();
-        if ((int)threadIdx.x + off < 256) add = fe_mul(zpow[pow0 + 3 + k], lds[threadIdx.x + off]);
-        __syncthreads();
-        lds[threadIdx.x] = fe_add(lds[threadIdx.x], add);
-        __syncthreads();
-    }
-    // value of H just after this thread's range
-    *carry_in = (threadIdx.x == 255) ? seed : lds[threadIdx.x + 1];
-    return lds[0];
-}
+// ---- open(): H_j = c_j + z H_{j+1} (H_m = 0) for all j at once: horner_block (scan_ops.hpp) ----------------
 
 struct OpenArgs {
     const Fr* c;
@@ -188,32 +73,6 @@ __global__ __launch_bounds__(256) void open_block_kernel(OpenArgs a) {
     Fr loc[8], ci;
     const Fr g0 = horner_block(a.c, a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow, 0, lds, loc, &ci);
     if (threadIdx.x == 0) p_st(a.blocks + blockIdx.x, g0);
-}
-// single workgroup: carries between workgroups, C_b = A_b + z^2048 C_{b+1}; blocks[b] <- C_{b+1} (the value of H at the
-// end of workgroup b); returns C_0 = p(z).  Rounds of 2048 entries from the high end, each seeded with the C its upper
-// neighbour ended on: horner_block then carries the seed across the round with (z^2048)^2048 = z^(2^22), so any number of
-// workgroups is one launch of the same kernel (m <= 2^22: one round from a zero seed, as before).  A third scan level
-// would cost two more launches at every size for at most 8 serial rounds of ~3 us at m = 2^25.
-__device__ __forceinline__ Fr open_top_rounds(Fr* blocks, uint32_t nblk, const Fr* zpow, bool store, Fr* lds) {
-    Fr loc[8], ci;
-    Fr run = Fr::zero();
-    const Fr zb = zpow[11];
-    for (uint32_t r = (nblk + 2047) / 2048; r-- > 0;) {
-        const uint64_t base = (uint64_t)r * 2048;
-        const Fr c0 = horner_block(blocks, nblk, base, run, zpow, 11, lds, loc, &ci);
-        if (store) {
-            // recompute the local chain from the true carry-in and store, for every entry, H of the NEXT entry
-            Fr h = ci;
-            const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
-            for (int e = 7; e >= 0; --e) {
-                if (s0 + e < nblk) p_st(blocks + s0 + e, h);
-                h = fe_add(loc[e], fe_mul(zb, h));
-            }
-        }
-        run = c0;
-        __syncthreads();   // the next round's horner_block overwrites the LDS this one's lds[0] / carries came from
-    }
-    return run;
 }
 __global__ __launch_bounds__(256) void open_top_kernel(OpenArgs a, uint32_t nblk) {
     __shared__ Fr lds[256];

@@ -1,0 +1,619 @@
+// libtyplonk_hip.so -- typlonk_prove_batch: many witnesses of one circuit per call, batched across proofs.
+//
+// The proofs run in waves of G (include/typlonk.h).  A wave goes round by round like typlonk_prove (prover.hip), but every
+// stage is one launch sequence for the whole wave instead of one per proof: the transforms through ntt_run_batch, the grand
+// product, the openings, the quotient's pointwise kernel and the linearisation through the kernels below (the proof index in
+// blockIdx.y, per-proof scalars in a small device table), and each round's commitments in one MsmQueue.  The host waits
+// three times per wave -- after round 1's and round 2's commitments (the transcripts need them) and for round 3's
+// evaluations -- plus the final read, never once per proof.  Every proof keeps its own Fiat-Shamir transcript, and every
+// field operation is exact, so proof k is bit for bit what typlonk_prove returns for witness k.
+#include "fr_inv.hpp"
+#include "host.hpp"
+#include "scan_ops.hpp"
+#include "transcript.hpp"
+
+#include <cstddef>
+
+using namespace ty;
+using namespace tyh;
+
+namespace {
+
+constexpr uint32_t PB_MAX = 64;              // proofs per wave (the cap of typlonk.h)
+constexpr uint64_t PB_ROWS = 1ull << 22;     // and at most this many rows of all proofs of a wave together
+constexpr uint32_t PB_ITEMS = 8;             // round 3's openings / evaluations per proof
+constexpr uint32_t PB_QGROUP = 4;            // proofs one thread of the quotient kernel evaluates per point
+constexpr uint32_t PB_SLOTS = 16;            // pinned result slots per proof
+// per-proof arena of a wave, in units of n Fr: ev[3] co[3] pi z t(4) q[6] r | ext a b c Z PI (5 x 4)
+constexpr uint64_t PB_EV = 0, PB_CO = 3, PB_PI = 6, PB_Z = 7, PB_T = 8, PB_Q = 12, PB_R = 18, PB_EXT = 19, PB_STRIDE = 39;
+
+struct PbGp {          // round 2
+    Fr beta, gamma, kbeta[3];
+};
+struct PbQuot {        // round 3, quotient
+    Fr alpha, alpha2, beta, gamma;
+    uint32_t has_pi, pad[7];
+};
+struct PbLin {         // round 3, linearisation
+    Fr scalar[LIN_TERMS];
+    Fr constant;
+};
+struct PbItem {        // one opening (q != null) or evaluation at zpow[zi]
+    const Fr* c;
+    Fr* q;
+    Fr* y;
+    uint64_t zi;
+};
+// every table of a wave, staged in pinned memory (ctx->batch_host) and copied to ctx->batch_tab; each part is written once per
+// wave and copied once, so no host write can overtake a copy still in flight
+struct PbTables {
+    PbGp gp[PB_MAX];
+    PbQuot quot[PB_MAX];
+    PbLin lin[PB_MAX];
+    PbItem item[PB_MAX * PB_ITEMS];
+    PbItem ritem[PB_MAX];
+    Fr zpow[2 * PB_MAX][32];   // zeta_p^(2^k) at 2p, (zeta_p w)^(2^k) at 2p + 1
+};
+
+// ---- round 2: the grand product of every proof of the wave (plonk_ops.hip's kernels with a proof index) ---------------------
+struct PbGpArgs {
+    const Fr* ev;        // proof p's three columns: ev + p * stride + i * n
+    const Fr* sigma;     // the circuit's sigma evaluations (3 n), shared
+    const Fr* w_lo;
+    const Fr* w_hi;
+    Fr* tmp;             // num, den, nprefix, dsuffix of proof p: tmp + p * stride + {0, 1, 2, 3} n
+    Fr* blk;             // carries of the two scans (2 nblk) and the inverse of proof p: blk + p * stride
+    Fr* z;
+    const PbGp* gp;
+    uint64_t n, stride;
+    uint32_t w_h, nblk;
+};
+
+__global__ __launch_bounds__(256) void pb_gp_terms_kernel(PbGpArgs a) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.n) return;
+    const uint32_t p = blockIdx.y;
+    const PbGp& g = a.gp[p];
+    const Fr x = fe_mul(p_ld(a.w_lo + (j & ((1ull << a.w_h) - 1))), p_ld(a.w_hi + (j >> a.w_h)));
+    const Fr* ev = a.ev + p * a.stride;
+    Fr num = Fr::one(), den = Fr::one();
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const Fr wg = fe_add(p_ld(ev + i * a.n + j), g.gamma);
+        num = fe_mul(num, fe_add(wg, fe_mul(g.kbeta[i], x)));
+        den = fe_mul(den, fe_add(wg, fe_mul(g.beta, p_ld(a.sigma + i * a.n + j))));
+    }
+    Fr* t = a.tmp + p * a.stride;
+    p_st(t + j, num);
+    p_st(t + a.n + j, den);
+}
+// scan s = 2 p + d of the wave: d = 0 the exclusive prefix products of proof p's numerators, d = 1 the suffix products of
+// its denominators
+__global__ __launch_bounds__(256) void pb_pscan_block_kernel(PbGpArgs a) {
+    const uint32_t p = blockIdx.y >> 1, d = blockIdx.y & 1;
+    pscan_block(a.tmp + p * a.stride + d * a.n, a.n, (int)d, a.blk + p * a.stride + d * a.nblk, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void pb_pscan_top_kernel(PbGpArgs a) {
+    const uint32_t p = blockIdx.x >> 1, d = blockIdx.x & 1;
+    pscan_top(a.blk + p * a.stride + d * a.nblk, a.nblk);
+}
+__global__ __launch_bounds__(256) void pb_pscan_finish_kernel(PbGpArgs a) {
+    const uint32_t p = blockIdx.y >> 1, d = blockIdx.y & 1;
+    Fr* t = a.tmp + p * a.stride;
+    pscan_finish(t + d * a.n, a.n, (int)d, a.blk + p * a.stride + d * a.nblk, t + (2 + d) * a.n, blockIdx.x);
+}
+// the one inversion of every proof: S_0 = dsuffix[0]
+__global__ __launch_bounds__(64) void pb_fr_inv_kernel(PbGpArgs a) {
+    const uint32_t p = blockIdx.x;
+    const Fr x = fr_inv_divsteps(p_ld(a.tmp + p * a.stride + 3 * a.n));
+    if (threadIdx.x == 0) p_st(a.blk + p * a.stride + 2 * a.nblk, x);
+}
+__global__ __launch_bounds__(256) void pb_gp_finish_kernel(PbGpArgs a) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.n) return;
+    const uint32_t p = blockIdx.y;
+    const Fr* t = a.tmp + p * a.stride;
+    p_st(a.z + p * a.stride + j,
+         fe_mul(fe_mul(p_ld(t + 2 * a.n + j), p_ld(t + 3 * a.n + j)), p_ld(a.blk + p * a.stride + 2 * a.nblk)));
+}
+
+// ---- openings / evaluations of many polynomials of m coefficients, each at its own point (launch_open_multi for a wave) -----
+struct PbOpenArgs {
+    const PbItem* items;
+    const Fr* zpow;      // 32 powers z^(2^k) per point
+    Fr* blocks;          // nblk carries per item
+    uint64_t m;
+    uint32_t nblk;
+};
+__global__ __launch_bounds__(256) void pb_open_block_kernel(PbOpenArgs a) {
+    __shared__ Fr lds[256];
+    Fr loc[8], ci;
+    const PbItem it = a.items[blockIdx.y];
+    const Fr g0 = horner_block(it.c, a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow + it.zi * 32, 0, lds, loc, &ci);
+    if (threadIdx.x == 0) p_st(a.blocks + (uint64_t)blockIdx.y * a.nblk + blockIdx.x, g0);
+}
+__global__ __launch_bounds__(256) void pb_open_top_kernel(PbOpenArgs a) {
+    __shared__ Fr lds[256];
+    const PbItem it = a.items[blockIdx.x];
+    const bool store = it.q != nullptr;
+    const Fr y = open_top_rounds(a.blocks + (uint64_t)blockIdx.x * a.nblk, a.nblk, a.zpow + it.zi * 32, store, lds);
+    if (!store && threadIdx.x == 0) p_st(it.y, y);
+}
+__global__ __launch_bounds__(256) void pb_open_finish_kernel(PbOpenArgs a) {
+    __shared__ Fr lds[256];
+    Fr loc[8], ci;
+    const PbItem it = a.items[blockIdx.y];
+    if (!it.q) return;  // whole workgroup
+    const Fr* zp = a.zpow + it.zi * 32;
+    const uint64_t base = (uint64_t)blockIdx.x * 2048;
+    const Fr seed = p_ld(a.blocks + (uint64_t)blockIdx.y * a.nblk + blockIdx.x);
+    horner_block(it.c, a.m, base, seed, zp, 0, lds, loc, &ci);
+    const Fr z = zp[0];
+    Fr h = ci;
+    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
+    for (int e = 7; e >= 0; --e) {
+        const uint64_t i = s0 + e;
+        h = fe_add(loc[e], fe_mul(z, h));
+        if (i < a.m) {
+            if (i == 0) p_st(it.y, h);
+            else p_st(it.q + i - 1, h);
+        }
+    }
+}
+void pb_launch_open(const PbItem* items, uint32_t count, const Fr* zpow, uint64_t m, Fr* blocks, hipStream_t s) {
+    PbOpenArgs a{items, zpow, blocks, m, (uint32_t)((m + 2047) / 2048)};
+    hipLaunchKernelGGL(pb_open_block_kernel, dim3(a.nblk, count), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pb_open_top_kernel, dim3(count), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pb_open_finish_kernel, dim3(a.nblk, count), dim3(256), 0, s, a);
+}
+
+// ---- round 3: the quotient's pointwise kernel for a wave (quotient.hip's formula) ------------------------------------------
+// One thread owns one point of the 4n coset and PB_QGROUP proofs: the circuit's nine coset constants and x_i are loaded once
+// and serve every proof of the group (each proof alone re-read them at all 4n points).
+struct PbQuotArgs {
+    const Fr* ext;       // proof p's coset evaluations of a, b, c, Z, PI: ext + p * stride + k * n4
+    const Fr* cext;      // the circuit's: q_l q_r q_o q_m q_c sigma_0..2 L0 (9 x n4)
+    const Fr* w_lo;      // x_i = g w_{4n}^i = w_lo[i & mask] * gx_hi[i >> w_h]
+    const Fr* gx_hi;
+    Fr* t;               // proof p's pointwise quotient: t + p * stride
+    const PbQuot* pq;
+    uint64_t n4, stride;
+    uint32_t w_h, count, k0_is_one;
+    Fr k[3];
+    Fr zh_inv[4];
+};
+__global__ __launch_bounds__(256) void pb_quotient_kernel(PbQuotArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n4) return;
+    const uint64_t iw = (i + 4) & (a.n4 - 1);
+    Fr sel[5], sig[3];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) sel[k] = p_ld(a.cext + k * a.n4 + i);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sig[k] = p_ld(a.cext + (5 + k) * a.n4 + i);
+    const Fr l0 = p_ld(a.cext + 8 * a.n4 + i);
+    const Fr x = fe_mul(p_ld(a.w_lo + (i & ((1ull << a.w_h) - 1))), p_ld(a.gx_hi + (i >> a.w_h)));
+    const Fr zhi = a.zh_inv[i & 3];
+    const uint32_t p0 = blockIdx.y * PB_QGROUP, p1 = min(a.count, p0 + PB_QGROUP);
+    for (uint32_t p = p0; p < p1; ++p) {
+        const PbQuot& q = a.pq[p];
+        const Fr* e = a.ext + p * a.stride;
+        const Fr wa = p_ld(e + i), wb = p_ld(e + a.n4 + i), wc = p_ld(e + 2 * a.n4 + i);
+        const Fr z = p_ld(e + 3 * a.n4 + i), zw = p_ld(e + 3 * a.n4 + iw);
+        Fr line1 = fe_mul(sel[0], wa);
+        line1 = fe_add(line1, fe_mul(sel[1], wb));
+        line1 = fe_sub(line1, fe_mul(sel[2], wc));
+        line1 = fe_add(line1, fe_mul(fe_mul(sel[3], wa), wb));
+        line1 = fe_add(line1, sel[4]);
+        if (q.has_pi) line1 = fe_add(line1, p_ld(e + 4 * a.n4 + i));
+        const Fr bx = fe_mul(q.beta, x);
+        Fr l2 = fe_add(fe_add(wa, a.k0_is_one ? bx : fe_mul(a.k[0], bx)), q.gamma);
+        l2 = fe_mul(l2, fe_add(fe_add(wb, fe_mul(a.k[1], bx)), q.gamma));
+        l2 = fe_mul(l2, fe_add(fe_add(wc, fe_mul(a.k[2], bx)), q.gamma));
+        l2 = fe_mul(l2, z);
+        Fr l3 = fe_add(fe_add(wa, fe_mul(q.beta, sig[0])), q.gamma);
+        l3 = fe_mul(l3, fe_add(fe_add(wb, fe_mul(q.beta, sig[1])), q.gamma));
+        l3 = fe_mul(l3, fe_add(fe_add(wc, fe_mul(q.beta, sig[2])), q.gamma));
+        l3 = fe_mul(l3, zw);
+        const Fr l4 = fe_mul(fe_sub(z, Fr::one()), l0);
+        Fr t = fe_add(line1, fe_mul(q.alpha, fe_sub(l2, l3)));
+        t = fe_add(t, fe_mul(q.alpha2, l4));
+        p_st(a.t + p * a.stride + i, fe_mul(t, zhi));
+    }
+}
+
+// ---- round 3: r = sum_k scalar_k poly_k + constant for every proof (lincomb_kernel with per-proof terms) -------------------
+struct PbLinArgs {
+    const Fr* coef;      // the circuit's coefficient copies (8 n): q_l q_r q_o q_m q_c at 0..4, sigma_2 at 7
+    const Fr* z;         // proof p's Z: z + p * stride, its t: t + p * stride, its r: r + p * stride
+    const Fr* t;
+    Fr* r;
+    const PbLin* lin;
+    uint64_t n, stride;
+};
+__global__ __launch_bounds__(256) void pb_lincomb_kernel(PbLinArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t p = blockIdx.y;
+    const PbLin& l = a.lin[p];
+    const Fr* t = a.t + p * a.stride;
+    const Fr* polys[LIN_TERMS] = {a.coef, a.coef + a.n, a.coef + 2 * a.n, a.coef + 3 * a.n, a.coef + 4 * a.n,
+                                  a.z + p * a.stride, a.coef + 7 * a.n, t, t + a.n, t + 2 * a.n};
+    Fr acc = (i == 0) ? l.constant : Fr::zero();
+#pragma unroll
+    for (int k = 0; k < LIN_TERMS; ++k) acc = fe_add(acc, fe_mul(l.scalar[k], p_ld(polys[k] + i)));
+    p_st(a.r + p * a.stride + i, acc);
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+const uint64_t* coset_g(Fr* g_out) {
+    // the quotient's coset generator (prover.hip): Fr's multiplicative generator 7
+    static uint64_t limbs[4];
+    const Fr g = fr_from_u64(7);
+    memcpy(limbs, g.v, sizeof(limbs));
+    if (g_out) *g_out = g;
+    return limbs;
+}
+
+struct ColumnsIn {   // the caller's columns: device buffers or host arrays, proof-major
+    const typlonk_buf* const* wire_bufs;
+    const typlonk_buf* const* pi_bufs;
+    const uint64_t* const* wire_host;
+    const uint64_t* const* pi_host;
+    const void* wire(size_t k, int i) const { return wire_bufs ? (const void*)wire_bufs[3 * k + i]->d : (const void*)wire_host[3 * k + i]; }
+    const void* pi(size_t k) const {
+        if (wire_bufs) return pi_bufs && pi_bufs[k] ? (const void*)pi_bufs[k]->d : nullptr;
+        return pi_host ? (const void*)pi_host[k] : nullptr;
+    }
+    hipMemcpyKind kind() const { return wire_bufs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+};
+
+struct Wave {
+    typlonk_ctx* ctx;
+    const SrsEntry* srs;
+    const CircuitEntry* ce;
+    uint32_t log_n;
+    uint64_t n;
+    Fr* mem;          // proof p's arena: mem + p * PB_STRIDE * n
+    PbTables* host;   // pinned staging
+    PbTables* dev;
+    Fr* slots;        // PB_SLOTS per proof
+    Fr k[3];
+    Fr* at(uint32_t p, uint64_t off) const { return mem + ((uint64_t)p * PB_STRIDE + off) * n; }
+};
+
+int hip_rc(typlonk_ctx* ctx, hipError_t e) {
+    if (e == hipSuccess) return TYPLONK_OK;
+    return fail(ctx, e == hipErrorOutOfMemory ? TYPLONK_ERR_OOM : TYPLONK_ERR_HIP, hipGetErrorString(e));
+}
+// copy one part of the staged tables to the device, stream-ordered
+int upload(const Wave& w, const void* host_part, size_t bytes) {
+    const size_t off = (const char*)host_part - (const char*)w.host;
+    return hip_rc(w.ctx, hipMemcpyAsync((char*)w.dev + off, host_part, bytes, hipMemcpyHostToDevice, w.ctx->stream));
+}
+
+int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
+    typlonk_ctx* ctx = w.ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = w.n, n4 = 4 * n;
+    const uint32_t log_n = w.log_n, log4 = log_n + 2;
+    const uint64_t stride = PB_STRIDE * n;
+    const uint64_t* g_limbs = coset_g(nullptr);
+    int rc = TYPLONK_OK;
+    bool has_pi[PB_MAX];
+    for (uint32_t p = 0; p < G; ++p) has_pi[p] = in.pi(first + p) != nullptr;
+    auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
+
+    // ---- round 1: columns into the arena, a, b, c (and PI) by one batched inverse transform, 3G commitments ----
+    std::vector<Fr*> co, ext;
+    std::vector<const Fr*> ext_src;
+    for (uint32_t p = 0; p < G && !rc; ++p) {
+        for (int i = 0; i < 3 && !rc; ++i) {
+            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_EV + i), in.wire(first + p, i), n * sizeof(Fr), in.kind(), s));
+            if (!rc) rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_CO + i), w.at(p, PB_EV + i), n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+            co.push_back(w.at(p, PB_CO + i));
+        }
+        if (!rc && has_pi[p]) {
+            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_PI), in.pi(first + p), n * sizeof(Fr), in.kind(), s));
+            co.push_back(w.at(p, PB_PI));
+        }
+    }
+    if (!rc) rc = ntt_run_batch(ctx, co.data(), co.size(), log_n, 1, nullptr, /*sync=*/false);   // proof.rs:50, 105-106
+    if (rc) return rc;
+    // the commitments wait for this mark only: the coset extensions queued behind it run beside them
+    if (!ctx->batch_fence) HIPCHK(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->batch_fence, s));
+    for (uint32_t p = 0; p < G; ++p)
+        for (int k = 0; k < 5; ++k) {
+            if (k == 3 || (k == 4 && !has_pi[p])) continue;   // (Z is extended in round 2)
+            ext.push_back(w.at(p, PB_EXT) + k * n4);
+            ext_src.push_back(k < 3 ? w.at(p, PB_CO + k) : w.at(p, PB_PI));
+        }
+    rc = ntt_run_batch(ctx, ext.data(), ext.size(), log4, 0, g_limbs, /*sync=*/false, ext_src.data(), n);
+    {
+        MsmQueue q(ctx, w.srs, /*first_lane=*/1);
+        q.fence = ctx->batch_fence;
+        for (uint32_t p = 0; p < G && !rc; ++p)
+            for (int i = 0; i < 3 && !rc; ++i)
+                rc = q.submit(w.at(p, PB_CO + i), n, out[first + p].commit_xy[i], out[first + p].commit_inf + i);   // :107-110
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    // (beta, gamma) <- H([a], [b], [c]) of each proof                                        proof.rs:111
+    std::vector<ChallengeGenerator> tr(G);
+    uint64_t ch[8];
+    for (uint32_t p = 0; p < G; ++p) {
+        typlonk_proof& o = out[first + p];
+        for (int i = 0; i < 3; ++i) tr[p].digest(o.commit_xy[i], o.commit_inf[i]);
+        tr[p].generate(2, ch);
+        memcpy(o.beta, ch, 32);
+        memcpy(o.gamma, ch + 4, 32);
+        PbGp& g = w.host->gp[p];
+        memcpy(g.beta.v, o.beta, 32);
+        memcpy(g.gamma.v, o.gamma, 32);
+        for (int i = 0; i < 3; ++i) g.kbeta[i] = fe_mul(w.k[i], g.beta);
+    }
+
+    // ---- round 2: the grand products (:119-120), one batched inverse transform (:127-128), G commitments of [Z] (:129) ----
+    if ((rc = upload(w, w.host->gp, G * sizeof(PbGp)))) return rc;
+    {
+        PbGpArgs a{};
+        a.ev = w.at(0, PB_EV);
+        a.sigma = w.ce->sig_ev;
+        a.tmp = w.at(0, PB_T);
+        a.blk = w.at(0, PB_Q);
+        a.z = w.at(0, PB_Z);
+        a.gp = w.dev->gp;
+        a.n = n;
+        a.stride = stride;
+        a.nblk = (uint32_t)((n + PSCAN_PER_BLOCK - 1) / PSCAN_PER_BLOCK);
+        Table lo, hi;
+        const uint32_t lg = std::max<uint32_t>(log_n, 1);
+        if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(lg), fr_domain_root(lg), Fr::one(), lg, &lo, &hi, &a.w_h))) return rc;
+        a.w_lo = lo.d;
+        a.w_hi = hi.d;
+        const unsigned gx = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(pb_gp_terms_kernel, dim3(gx, G), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(pb_pscan_block_kernel, dim3(a.nblk, 2 * G), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(pb_pscan_top_kernel, dim3(2 * G), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(pb_pscan_finish_kernel, dim3(a.nblk, 2 * G), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(pb_fr_inv_kernel, dim3(G), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(pb_gp_finish_kernel, dim3(gx, G), dim3(256), 0, s, a);
+        if ((rc = lasterr())) return rc;
+    }
+    {
+        std::vector<Fr*> zs(G), zext(G);
+        std::vector<const Fr*> zsrc(G);
+        for (uint32_t p = 0; p < G; ++p) {
+            zs[p] = w.at(p, PB_Z);
+            zsrc[p] = zs[p];
+            zext[p] = w.at(p, PB_EXT) + 3 * n4;
+        }
+        if ((rc = ntt_run_batch(ctx, zs.data(), G, log_n, 1, nullptr, /*sync=*/false))) return rc;
+        HIPCHK(hipEventRecord(ctx->batch_fence, s));
+        rc = ntt_run_batch(ctx, zext.data(), G, log4, 0, g_limbs, /*sync=*/false, zsrc.data(), n);   // beside the commitments
+        MsmQueue q(ctx, w.srs, /*first_lane=*/1);
+        q.fence = ctx->batch_fence;
+        for (uint32_t p = 0; p < G && !rc; ++p) rc = q.submit(w.at(p, PB_Z), n, out[first + p].z_xy, &out[first + p].z_inf);
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    // (alpha, zeta) <- H([a], [b], [c], [Z])                                                    proof.rs:133-136
+    std::vector<Fr> zeta(G), alpha(G);
+    const Fr wn = fr_domain_root(log_n);
+    for (uint32_t p = 0; p < G; ++p) {
+        typlonk_proof& o = out[first + p];
+        tr[p].digest(o.z_xy, o.z_inf);
+        tr[p].generate(2, ch);
+        memcpy(o.alpha, ch, 32);
+        memcpy(o.zeta, ch + 4, 32);
+        memcpy(alpha[p].v, o.alpha, 32);
+        memcpy(zeta[p].v, o.zeta, 32);
+        PbQuot& q = w.host->quot[p];
+        q.alpha = alpha[p];
+        q.alpha2 = fe_sqr(alpha[p]);
+        q.beta = w.host->gp[p].beta;
+        q.gamma = w.host->gp[p].gamma;
+        q.has_pi = has_pi[p];
+        Fr* zp0 = w.host->zpow[2 * p];
+        Fr* zp1 = w.host->zpow[2 * p + 1];
+        zp0[0] = zeta[p];
+        zp1[0] = fe_mul(zeta[p], wn);
+        for (int k = 1; k < 32; ++k) {
+            zp0[k] = fe_sqr(zp0[k - 1]);
+            zp1[k] = fe_sqr(zp1[k - 1]);
+        }
+    }
+
+    // ---- round 3: openings (:147-163), quotient (:139-145), linearisation (:165-175), nine commitments per proof (:181) ----
+    const uint32_t nblk = (uint32_t)((n + 2047) / 2048);
+    Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
+    uint32_t nitems = 0;
+    for (uint32_t p = 0; p < G; ++p) {
+        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        auto item = [&](const Fr* c, Fr* q, int slot, uint32_t zi) { w.host->item[nitems++] = PbItem{c, q, y + slot, 2ull * p + zi}; };
+        for (int i = 0; i < 3; ++i) item(w.at(p, PB_CO + i), w.at(p, PB_Q + i), i, 0);
+        item(w.at(p, PB_Z), w.at(p, PB_Q + 3), 3, 0);
+        item(w.ce->coef + 5 * n, nullptr, 4, 0);             // sigma_0
+        item(w.ce->coef + 6 * n, nullptr, 5, 0);             // sigma_1
+        if (has_pi[p]) item(w.at(p, PB_PI), nullptr, 6, 0);
+        item(w.at(p, PB_Z), w.at(p, PB_Q + 4), 8, 1);        // Z at zeta * w
+    }
+    if ((rc = upload(w, w.host->quot, G * sizeof(PbQuot)))) return rc;
+    if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
+    if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
+    pb_launch_open(w.dev->item, nitems, &w.dev->zpow[0][0], n, blocks, s);
+    if ((rc = lasterr())) return rc;
+    {
+        PbQuotArgs a{};
+        Fr g;
+        coset_g(&g);
+        a.ext = w.at(0, PB_EXT);
+        a.cext = w.ce->ext;
+        a.t = w.at(0, PB_T);
+        a.pq = w.dev->quot;
+        a.n4 = n4;
+        a.stride = stride;
+        a.count = G;
+        Table lo, hi;
+        const Fr w4 = fr_domain_root(log4);
+        if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &a.w_h))) return rc;
+        a.w_lo = lo.d;
+        const uint64_t n_hi = 1ull << (log4 - a.w_h);
+        if ((rc = ensure(ctx, ctx->quot_tab, n_hi * sizeof(Fr)))) return rc;
+        launch_fr_scale(hi.d, n_hi, g, (Fr*)ctx->quot_tab.p, s);
+        a.gx_hi = (const Fr*)ctx->quot_tab.p;
+        // X^n - 1 on the coset: g^n iota^k - 1, iota = w_{4n}^n
+        Fr gn = g, iota = w4;
+        for (uint32_t i = 0; i < log_n; ++i) {
+            gn = fe_sqr(gn);
+            iota = fe_sqr(iota);
+        }
+        Fr cur = gn;
+        for (int k = 0; k < 4; ++k) {
+            a.zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
+            cur = fe_mul(cur, iota);
+        }
+        for (int k = 0; k < 3; ++k) a.k[k] = w.k[k];
+        a.k0_is_one = w.k[0] == Fr::one();
+        hipLaunchKernelGGL(pb_quotient_kernel, dim3((unsigned)((n4 + 255) / 256), (G + PB_QGROUP - 1) / PB_QGROUP), dim3(256), 0, s, a);
+        if ((rc = lasterr())) return rc;
+        std::vector<Fr*> ts(G);
+        for (uint32_t p = 0; p < G; ++p) ts[p] = w.at(p, PB_T);
+        if ((rc = ntt_run_batch(ctx, ts.data(), G, log4, 1, g_limbs, /*sync=*/false))) return rc;
+    }
+    // what the linearisation needs of zeta alone, while the kernels run; then ONE wait for every evaluation of the wave
+    std::vector<Fr> zn(G), zh(G), l0z(G);
+    for (uint32_t p = 0; p < G; ++p) lin_zeta_terms(zeta[p], log_n, &zn[p], &zh[p], &l0z[p]);
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t p = 0; p < G; ++p) {
+        const Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        const Fr ev[5] = {y[0], y[1], y[2], y[3], y[8]};
+        const Fr pi_z = has_pi[p] ? y[6] : Fr::zero();
+        PbLin& l = w.host->lin[p];
+        lin_scalars(ev, y[4], y[5], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha[p], zeta[p], zn[p], zh[p], l0z[p],
+                    l.scalar, &l.constant);
+        typlonk_proof_tail& t = out[first + p].tail;
+        for (int i = 0; i < 5; ++i) memcpy(t.evals[i], ev[i].v, 32);
+        w.host->ritem[p] = PbItem{w.at(p, PB_R), w.at(p, PB_Q + 5), w.slots + (uint64_t)p * PB_SLOTS + 9, 2ull * p};
+    }
+    if ((rc = upload(w, w.host->lin, G * sizeof(PbLin)))) return rc;
+    if ((rc = upload(w, w.host->ritem, G * sizeof(PbItem)))) return rc;
+    {
+        PbLinArgs a{w.ce->coef, w.at(0, PB_Z), w.at(0, PB_T), w.at(0, PB_R), w.dev->lin, n, stride};
+        hipLaunchKernelGGL(pb_lincomb_kernel, dim3((unsigned)((n + 255) / 256), G), dim3(256), 0, s, a);
+        if ((rc = lasterr())) return rc;
+    }
+    pb_launch_open(w.dev->ritem, G, &w.dev->zpow[0][0], n, blocks, s);   // r(zeta) and its witness (:175)
+    if ((rc = lasterr())) return rc;
+    {
+        HIPCHK(hipEventRecord(ctx->batch_fence, s));
+        MsmQueue q(ctx, w.srs, /*first_lane=*/0);
+        q.fence = ctx->batch_fence;
+        const size_t m[9] = {n - 1, n - 1, n - 1, n - 1, n - 1, n - 1, n, n, n > 3 ? n - 3 : 0};
+        for (uint32_t p = 0; p < G && !rc; ++p) {
+            typlonk_proof_tail& t = out[first + p].tail;
+            const Fr* polys[9] = {w.at(p, PB_Q), w.at(p, PB_Q + 1), w.at(p, PB_Q + 2), w.at(p, PB_Q + 3), w.at(p, PB_Q + 4),
+                                  w.at(p, PB_Q + 5), w.at(p, PB_T), w.at(p, PB_T + 1), w.at(p, PB_T + 2)};
+            for (int k = 0; k < 9 && !rc; ++k)
+                rc = k < 6 ? q.submit(polys[k], m[k], t.w_xy[k], t.w_inf + k) : q.submit(polys[k], m[k], t.t_xy[k - 6], t.t_inf + k - 6);
+        }
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t p = 0; p < G; ++p) {
+        const Fr rz = w.slots[(uint64_t)p * PB_SLOTS + 9];
+        memcpy(out[first + p].tail.evals[5], rz.v, 32);
+        // r(zeta) != 0: the witness does not satisfy the circuit (proof.rs:234-235), as typlonk_prove reports it
+        status[first + p] = rz.is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
+    }
+    return TYPLONK_OK;
+}
+
+struct BusyGuard {
+    typlonk_ctx* ctx;
+    ~BusyGuard() {
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->prover_busy = false;
+    }
+};
+
+int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsIn& in, size_t count,
+                     const uint64_t cosets[3][4], typlonk_proof* out, int* status) {
+    if (!ctx) return TYPLONK_ERR_INVALID_ARG;
+    if (count == 0) return TYPLONK_OK;
+    if (!cosets || !out || !status || !(in.wire_bufs || in.wire_host)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    auto ci = ctx->circuits.find(circuit_id);
+    if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
+    const uint32_t log_n = ci->second.log_n;
+    const uint64_t n = 1ull << log_n;
+    for (size_t k = 0; k < 3 * count; ++k) {
+        if (in.wire_bufs ? !in.wire_bufs[k] : !in.wire_host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
+        if (in.wire_bufs && in.wire_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
+    }
+    if (in.wire_bufs && in.pi_bufs)
+        for (size_t k = 0; k < count; ++k)
+            if (in.pi_bufs[k] && in.pi_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "public-input column shorter than n");
+    auto si = ctx->srs.find(srs_id);
+    if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
+    if (si->second.total_len || comm_folds(ctx, srs_id))
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG, "batched proving needs a whole SRS on one GPU, not a shard");
+    if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
+    if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t G = (uint32_t)std::min<uint64_t>({(uint64_t)count, PB_MAX, std::max<uint64_t>(1, PB_ROWS >> log_n)});
+    // the wave's workspaces: the per-proof arenas, the openings' carries, the result slots, the tables
+    int rc = ensure(ctx, ctx->prover_mem, (size_t)G * PB_STRIDE * n * sizeof(Fr));
+    if (!rc) rc = ensure(ctx, ctx->ops_tmp, (size_t)G * PB_ITEMS * ((n + 2047) / 2048) * sizeof(Fr));
+    if (!rc) rc = ensure(ctx, ctx->batch_tab, sizeof(PbTables));
+    if (rc) return rc;
+    if (ctx->eval_slots_cap < (size_t)G * PB_SLOTS) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->eval_slots_host) HIPCHK(hipHostFree(ctx->eval_slots_host));
+        ctx->eval_slots_host = nullptr;
+        ctx->eval_slots_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, (size_t)G * PB_SLOTS * sizeof(Fr)));
+        ctx->eval_slots_cap = (size_t)G * PB_SLOTS;
+    }
+    if (!ctx->batch_host) HIPCHK(hipHostMalloc(&ctx->batch_host, sizeof(PbTables)));
+    ctx->prover_busy = true;
+    BusyGuard busy{ctx};
+    ProfilingOff prof_off(ctx);
+    ProverRound in_round(ctx);
+    Wave w;
+    w.ctx = ctx;
+    w.srs = &si->second;
+    w.ce = &ci->second;
+    w.log_n = log_n;
+    w.n = n;
+    w.mem = (Fr*)ctx->prover_mem.p;
+    w.host = (PbTables*)ctx->batch_host;
+    w.dev = (PbTables*)ctx->batch_tab.p;
+    w.slots = ctx->eval_slots_host;
+    for (int i = 0; i < 3; ++i) memcpy(w.k[i].v, cosets[i], 32);
+    for (size_t first = 0; first < count && !rc; first += G) {
+        const uint32_t g = (uint32_t)std::min<size_t>(G, count - first);
+        rc = run_wave(w, in, first, g, out, status);
+    }
+    return rc;
+}
+
+}  // namespace
+
+int typlonk_prove_batch(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
+                        const typlonk_buf* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
+                        int* status) {
+    const ColumnsIn in{wire_evals, pi_evals, nullptr, nullptr};
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, count, cosets, out, status);
+}
+
+int typlonk_prove_batch_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
+                             const uint64_t* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
+                             int* status) {
+    const ColumnsIn in{nullptr, nullptr, wire_evals, pi_evals};
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, count, cosets, out, status);
+}

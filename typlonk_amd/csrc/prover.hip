@@ -360,7 +360,10 @@ int prover_ops_tmp(typlonk_prover* p, Fr** blocks, Fr** slots) {
     typlonk_ctx* ctx = p->ctx;
     int rc = ensure(ctx, ctx->ops_tmp, std::max<size_t>(PROVER_EVAL_BLOCKS, 8 * ((p->n + 2047) / 2048)) * sizeof(Fr));
     if (rc) return rc;
-    if (!ctx->eval_slots_host) HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
+    if (!ctx->eval_slots_host) {
+        HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
+        ctx->eval_slots_cap = 16;
+    }
     *blocks = (Fr*)ctx->ops_tmp.p;
     *slots = ctx->eval_slots_host;
     return TYPLONK_OK;
@@ -630,13 +633,7 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
             rc = quotient_run(ctx, &qa, log_n, &tb, p->extended);
         }
         // what the linearisation needs of zeta alone (one host inversion among it): while the kernels above run
-        for (uint32_t i = 0; i < log_n; ++i) zn = fe_sqr(zn);
-        zh = fe_sub(zn, one);  // evaluate_vanishing_polynomial(zeta)
-        {
-            // L0(zeta) = (zeta^n - 1) / (n (zeta - 1)); the polynomial (1/n) sum X^i evaluates to 1 at zeta = 1
-            const Fr zm1 = fe_sub(ze, one);
-            if (!zm1.is_zero()) l0z = fe_mul(zh, fe_inv(fe_mul(fr_from_u64(n), zm1)));
-        }
+        lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);
         if (!rc) rc = prover_fetch(p, host, 9);
         for (int i = 0; i < 4; ++i) ev[i] = host[i];
         ev[4] = host[8];
@@ -645,30 +642,12 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
         if (p->has_pi) pi_z = host[6];
     }
     if (!rc) {
-        const Fr &a = ev[0], &b = ev[1], &c = ev[2], &zwe = ev[4];
-        const Fr &beta = p->beta, &gamma = p->gamma;
-        const Fr bz = fe_mul(beta, ze);
-        Fr l2 = one;  // prod_i (w_i(zeta) + k_i beta zeta + gamma)
-        for (int i = 0; i < 3; ++i) l2 = fe_mul(l2, fe_add(fe_add(ev[i], fe_mul(p->k[i], bz)), gamma));
-        const Fr ab = fe_mul(fe_add(fe_add(a, fe_mul(beta, s0)), gamma), fe_add(fe_add(b, fe_mul(beta, s1)), gamma));
-        const Fr abz = fe_mul(ab, zwe);          // copy_permutation_ab * Z(zeta w)
-        const Fr al2 = fe_sqr(al);
         LincombArgs la{};
-        int k = 0;
-        auto term = [&](const Fr* poly, const Fr& sc) { la.poly[k] = poly; la.scalar[k] = sc; ++k; };
-        term(ce.coef + 0 * n, a);                                   // q_l a
-        term(ce.coef + 1 * n, b);                                   // q_r b
-        term(ce.coef + 2 * n, fe_neg(c));                           // - q_o c
-        term(ce.coef + 3 * n, fe_mul(a, b));                        // q_m a b
-        term(ce.coef + 4 * n, one);                                 // q_c
-        term(p->z, fe_add(fe_mul(al, l2), fe_mul(al2, l0z)));       // Z (alpha line2 + alpha^2 L0)
-        term(ce.coef + 7 * n, fe_neg(fe_mul(al, fe_mul(beta, abz))));  // - alpha beta sigma_2 AB Z(zw)
-        term(p->t, fe_neg(zh));                                     // - Z_H t_lo
-        term(p->t + n, fe_neg(fe_mul(zh, zn)));                     // - Z_H zeta^n t_mid
-        term(p->t + 2 * n, fe_neg(fe_mul(zh, fe_sqr(zn))));         // - Z_H zeta^2n t_hi
-        la.terms = (uint32_t)k;
-        // constant: PI(zeta) - alpha (gamma + c) AB Z(zw) - alpha^2 L0
-        la.constant = fe_sub(fe_sub(pi_z, fe_mul(al, fe_mul(fe_add(gamma, c), abz))), fe_mul(al2, l0z));
+        lin_scalars(ev, s0, s1, pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, la.scalar, &la.constant);
+        const Fr* polys[LIN_TERMS] = {ce.coef + 0 * n, ce.coef + 1 * n, ce.coef + 2 * n, ce.coef + 3 * n, ce.coef + 4 * n,
+                                      p->z, ce.coef + 7 * n, p->t, p->t + n, p->t + 2 * n};
+        for (int k = 0; k < LIN_TERMS; ++k) la.poly[k] = polys[k];
+        la.terms = LIN_TERMS;
         la.out = p->r;
         la.n = n;
         launch_lincomb(la, ctx->stream);
@@ -723,6 +702,43 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     return rc;
 }
 }  // namespace
+
+namespace tyh {
+void lin_zeta_terms(const Fr& zeta, uint32_t log_n, Fr* zn, Fr* zh, Fr* l0z) {
+    const Fr one = Fr::one();
+    Fr x = zeta;
+    for (uint32_t i = 0; i < log_n; ++i) x = fe_sqr(x);
+    *zn = x;
+    *zh = fe_sub(x, one);  // evaluate_vanishing_polynomial(zeta)
+    // L0(zeta) = (zeta^n - 1) / (n (zeta - 1)); the polynomial (1/n) sum X^i evaluates to 1 at zeta = 1
+    *l0z = one;
+    const Fr zm1 = fe_sub(zeta, one);
+    if (!zm1.is_zero()) *l0z = fe_mul(*zh, fe_inv(fe_mul(fr_from_u64(1ull << log_n), zm1)));
+}
+void lin_scalars(const Fr* ev, const Fr& s0, const Fr& s1, const Fr& pi_z, const Fr& beta, const Fr& gamma, const Fr (&k)[3],
+                 const Fr& al, const Fr& zeta, const Fr& zn, const Fr& zh, const Fr& l0z, Fr* sc, Fr* constant) {
+    const Fr one = Fr::one();
+    const Fr &a = ev[0], &b = ev[1], &c = ev[2], &zwe = ev[4];
+    const Fr bz = fe_mul(beta, zeta);
+    Fr l2 = one;  // prod_i (w_i(zeta) + k_i beta zeta + gamma)
+    for (int i = 0; i < 3; ++i) l2 = fe_mul(l2, fe_add(fe_add(ev[i], fe_mul(k[i], bz)), gamma));
+    const Fr ab = fe_mul(fe_add(fe_add(a, fe_mul(beta, s0)), gamma), fe_add(fe_add(b, fe_mul(beta, s1)), gamma));
+    const Fr abz = fe_mul(ab, zwe);          // copy_permutation_ab * Z(zeta w)
+    const Fr al2 = fe_sqr(al);
+    sc[0] = a;                                            // q_l a
+    sc[1] = b;                                            // q_r b
+    sc[2] = fe_neg(c);                                    // - q_o c
+    sc[3] = fe_mul(a, b);                                 // q_m a b
+    sc[4] = one;                                          // q_c
+    sc[5] = fe_add(fe_mul(al, l2), fe_mul(al2, l0z));     // Z (alpha line2 + alpha^2 L0)
+    sc[6] = fe_neg(fe_mul(al, fe_mul(beta, abz)));        // - alpha beta sigma_2 AB Z(zw)
+    sc[7] = fe_neg(zh);                                   // - Z_H t_lo
+    sc[8] = fe_neg(fe_mul(zh, zn));                       // - Z_H zeta^n t_mid
+    sc[9] = fe_neg(fe_mul(zh, fe_sqr(zn)));               // - Z_H zeta^2n t_hi
+    // constant: PI(zeta) - alpha (gamma + c) AB Z(zw) - alpha^2 L0
+    *constant = fe_sub(fe_sub(pi_z, fe_mul(al, fe_mul(fe_add(gamma, c), abz))), fe_mul(al2, l0z));
+}
+}  // namespace tyh
 
 int typlonk_prover_round3(typlonk_prover* p, const uint64_t alpha[4], const uint64_t zeta[4], typlonk_proof_tail* out) {
     if (!p || !alpha || !zeta || !out) return TYPLONK_ERR_INVALID_ARG;

@@ -22,6 +22,7 @@
 // does on the CPU (Horner, synthetic division) is done on the CPU here too, with the library's own
 // Fr arithmetic (csrc/ff.hpp).  Nothing here touches the oracle.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -544,6 +545,43 @@ class CompiledCircuit {
         for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
         const uint64_t* wc[3] = {advice[0][0].limbs(), advice[1][0].limbs(), advice[2][0].limbs()};
         check(typlonk_prove_host(c, srs_.id(), circuit_, wc, public_inputs.empty() ? nullptr : public_inputs[0].limbs(), ks, &raw), c);
+        return from_raw(raw);
+    }
+
+    // prove() for many witnesses in one call (typlonk_prove_batch_host, batched across proofs in waves): advice[k] and
+    // public_inputs[k] (empty = the all-zero column; the vector itself may be empty) as for prove().  proofs[k] equals
+    // prove(advice[k], public_inputs[k]); status[k] is TYPLONK_OK or TYPLONK_ERR_UNSATISFIED (a witness that does not
+    // satisfy the circuit: its proof is filled all the same and will not verify) -- no throw for those.
+    std::vector<Proof> prove_batch(const std::vector<std::array<std::vector<Fr>, 3>>& advice,
+                                   const std::vector<std::vector<Fr>>& public_inputs, std::vector<int>* status) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        const size_t count = advice.size();
+        if (!public_inputs.empty() && public_inputs.size() != count) throw std::runtime_error("one public-input column per witness");
+        std::vector<const uint64_t*> wc(3 * count), pc(count, nullptr);
+        for (size_t k = 0; k < count; ++k) {
+            for (int i = 0; i < 3; ++i) {
+                if (advice[k][i].size() != n_) throw std::runtime_error("witness column must hold n values");
+                wc[3 * k + i] = advice[k][i][0].limbs();
+            }
+            if (!public_inputs.empty() && !public_inputs[k].empty()) {
+                if (public_inputs[k].size() != n_) throw std::runtime_error("public-input column must hold n values");
+                pc[k] = public_inputs[k][0].limbs();
+            }
+        }
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        std::vector<typlonk_proof> raw(count);
+        std::vector<int> st(count, TYPLONK_OK);
+        check(typlonk_prove_batch_host(c, srs_.id(), circuit_, wc.data(), pc.data(), count, ks, raw.data(), st.data()), c);
+        std::vector<Proof> out;
+        out.reserve(count);
+        for (const typlonk_proof& r : raw) out.push_back(from_raw(r));
+        if (status) *status = st;
+        return out;
+    }
+
+    // typlonk_proof (the C ABI's form) -> Proof
+    static Proof from_raw(const typlonk_proof& raw) {
         Proof p;
         auto pt = [](const uint64_t xy[12], uint8_t inf) {
             kzg::G1Point g;
