@@ -408,6 +408,90 @@ int typlonk_verify(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const
                    const uint64_t cosets[3][4], const typlonk_proof* proofs, size_t count,
                    const uint64_t* const* pi, const size_t* pi_len, uint32_t flags, uint8_t* ok);
 
+/* ---- the COMPACT proof shape: batched KZG openings, a transcript that binds the statement, an O(1) verifier ----------
+ * A shape this library defines (the reference's own to-do, /root/reference/README.md:4, "opening batching"); the reference
+ * shape above is unchanged.  9 MSMs per proof instead of 13, and the verifier needs a verifying key, not the circuit.
+ * Encodings: Fr = 32 bytes, little-endian canonical integer; a G1 point = the 96 bytes of serialize_unchecked that
+ * typlonk_prove's transcript hashes; integers little-endian; H(x) = Blake2b-512(x) read as a little-endian integer mod r.
+ * sigma_1..3 = the circuit's sigma polynomials in typlonk_circuit_commitments order; w = the domain root; G = the fixed G1
+ * generator; P0 = SRS point 0.
+ *   statement  vk_bytes = u32 log_n || k_0 || k_1 || k_2 || [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3] || P0
+ *              d0 = Blake2b-512("typlonk/compact/v1" || vk_bytes || u64 pi_len || pi_0 .. pi_{pi_len-1})
+ *              The statement is exactly the pi_len public values; rows pi_len.. of the public-input column are zero.
+ *   transcript T starts as d0; each challenge is H(T || label), the label one ASCII byte:
+ *              T ||= [a] [b] [c]                                   beta = H(T || 'b'), gamma = H(T || 'g')
+ *              T ||= [Z]                                           alpha = H(T || 'a')
+ *              T ||= [t_lo] [t_mid] [t_hi]                         zeta = H(T || 'z')
+ *              T ||= a(z) b(z) c(z) Z(z) Z(z w) sigma_1(z) sigma_2(z)   v = H(T || 'v')
+ *              The quotient is committed BEFORE zeta is drawn (the reference hashes only [a] [b] [c] [Z], so a prover holding
+ *              any witness may pick t = N(zeta) / Z_H(zeta) and pass its verifier; here t is bound first).
+ *   proof      a, b, c, Z, t, r exactly as typlonk_prove computes them (r with +PI(zeta)), and
+ *              F = a + v b + v^2 c + v^3 Z + v^4 r + v^5 sigma_1 + v^6 sigma_2,
+ *              W_z = [(F - F(z)) / (X - z)],  W_zw = [(Z - Z(z w)) / (X - z w)]  (typlonk_prove's Z-at-zeta*w witness).
+ *              With the same challenges W_z = round4_batched(v).w[0] + v^5 [q_s1] + v^6 [q_s2], q_si = (sigma_i - sigma_i(z)) / (X - z).
+ *              r(zeta) is not sent: it is 0 for a satisfying witness.
+ *   verifier   per proof: the 9 points on the curve and the 7 scalars canonical (else ok = 0, kept out of the fold); the five
+ *              challenges; zeta^n != 1; PI(zeta) (barycentric on the host up to 2048 values, else inverse NTT +
+ *              typlonk_poly_eval_dev); [r] expanded into its 11 bases as typlonk_verify does with TYPLONK_VERIFY_PI_AS_PROVER,
+ *              sigma_1(z), sigma_2(z) from the proof; then, with y_F = a + v b + v^2 c + v^3 Z(z) + v^5 sigma_1(z) + v^6 sigma_2(z)
+ *              and F_C = [a] + v [b] + v^2 [c] + v^3 [Z] + v^4 [r] + v^5 [sigma_1] + v^6 [sigma_2]:
+ *                e(W_z, [s]G2) = e(F_C - y_F G + z W_z, G2)      e(W_zw, [s]G2) = e([Z] - Z(z w) G + z w W_zw, G2)
+ *   fold       weights rho^(2k + j + 1), rho = H("typlonk/compact/fold/v1" || vk_bytes || [s]G2 as its 24 limbs || per proof
+ *              its 9 points and 7 evaluations || per proof PI(zeta), 0 for a proof the host checks rejected): two device MSMs
+ *              (2K bases; 9K + 10: per proof a, b, c, Z, t x 3, W_z, W_zw, shared the 8 commitments, P0, G) and ONE host
+ *              pairing product for a batch that is all valid; a failed fold is bisected as typlonk_verify bisects it. */
+typedef struct typlonk_vk {
+    uint32_t log_n;
+    uint64_t cosets[3][4];       /* k_0 k_1 k_2 */
+    uint64_t commit_xy[8][12];   /* [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3] */
+    uint8_t commit_inf[8];
+    uint64_t srs0_xy[12];        /* P0 */
+    uint8_t srs0_inf;
+    uint64_t g2s_xy[24];         /* [s]G2: x.c0 x.c1 y.c0 y.c1 */
+} typlonk_vk;
+typedef struct typlonk_proof_compact {
+    uint64_t commit_xy[3][12];   /* [a] [b] [c] */
+    uint8_t commit_inf[3];
+    uint64_t z_xy[12];           /* [Z] */
+    uint8_t z_inf;
+    uint64_t t_xy[3][12];        /* [t_lo] [t_mid] [t_hi] */
+    uint8_t t_inf[3];
+    uint64_t w_xy[2][12];        /* W_z, W_zw */
+    uint8_t w_inf[2];
+    uint64_t evals[7][4];        /* a(z) b(z) c(z) Z(z) Z(z w) sigma_1(z) sigma_2(z) */
+    uint64_t beta[4], gamma[4], alpha[4], zeta[4], v[4];   /* for the caller; the verifier recomputes them */
+} typlonk_proof_compact;
+/* The verifying key of a loaded circuit: the cached typlonk_circuit_commitments (one batch of eight MSMs the first time per
+ * (circuit, SRS)), SRS point 0, the cosets and [s]G2.  A g2s that is not on the twist returns TYPLONK_ERR_INVALID_ARG; SRS
+ * errors as for typlonk_circuit_commitments. */
+int typlonk_circuit_vk(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4],
+                       const uint64_t g2s_xy[24], typlonk_vk* vk);
+/* One compact proof.  wire_evals as for typlonk_prove; pi: a buffer of >= pi_len elements of which only the first pi_len are
+ * read (may be NULL when pi_len = 0), brought to the host once for d0.  The first compact proof of a (circuit, SRS) pair
+ * computes the circuit commitments for d0 (a one-time cost, cached with the circuit).  Rounds 1 and 2 run as in typlonk_prove;
+ * round 3 queues the quotient once alpha is known and waits for its three commitments before it draws zeta.
+ * Returns TYPLONK_ERR_UNSATISFIED (with `out` completely filled) when r(zeta) != 0; TYPLONK_ERR_INVALID_ARG for a sharded SRS
+ * or while a round-by-round prover is open; TYPLONK_ERR_DOMAIN above 2^24 rows; TYPLONK_ERR_LENGTH when pi_len > n or the
+ * SRS is shorter than n. */
+int typlonk_prove_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
+                          const typlonk_buf* pi, size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out);
+/* The same with the columns in HOST memory (uploaded column by column beside round 1, as typlonk_prove_host): wire_evals[i]
+ * holds `rows` Fr elements, and rows must equal the circuit's n (else TYPLONK_ERR_LENGTH); pi holds pi_len values. */
+int typlonk_prove_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
+                               size_t rows, const uint64_t* pi, size_t pi_len, const uint64_t cosets[3][4],
+                               typlonk_proof_compact* out);
+/* `count` compact proofs against one verifying key: ok[k] = 1 iff proof k is accepted.  No SRS and no loaded circuit are
+ * needed.  pi[k] / pi_len[k] as for typlonk_verify (pi_len[k] > n -> TYPLONK_ERR_LENGTH).  A vk point off the curve (or a
+ * g2s off the twist, a log_n outside 1..24) returns TYPLONK_ERR_INVALID_ARG / TYPLONK_ERR_DOMAIN; a bad proof gets ok = 0;
+ * count = 0 is a no-op.  Profiling stages as typlonk_verify's; "verify_eval" appears only when a PI column is longer than
+ * 2048 values. */
+int typlonk_verify_compact(typlonk_ctx* ctx, const typlonk_vk* vk, const typlonk_proof_compact* proofs, size_t count,
+                           const uint64_t* const* pi, const size_t* pi_len, uint8_t* ok);
+/* The compact transcript alone (host-only, no GPU): beta, gamma, alpha, zeta, v of `proof` (4 Montgomery limbs each) from
+ * its points and evaluations, the vk and the public inputs.  pi_len > 2^log_n returns TYPLONK_ERR_LENGTH. */
+int typlonk_compact_challenges(const typlonk_vk* vk, const typlonk_proof_compact* proof, const uint64_t* pi, size_t pi_len,
+                               uint64_t out[5][4]);
+
 /* ---- device-resident Fr vectors (so an iNTT result feeds an MSM without crossing PCIe) ---------- */
 int typlonk_buf_alloc(typlonk_ctx* ctx, size_t n_elems, typlonk_buf** out);
 int typlonk_buf_free(typlonk_ctx* ctx, typlonk_buf* buf);

@@ -13,6 +13,8 @@
 //!   * `Backend::load_circuit` + `Backend::prove`
 //!                               replace the body of `plonk::proof::prove`           plonk/src/proof.rs:96-194
 //!   * `Backend::verify_batch`   replaces `plonk::proof::verify` for a batch          plonk/src/proof.rs:195-281
+//!   * `Backend::prove_compact` / `verifying_key` / `verify_compact`
+//!                               the compact proof shape of include/typlonk.h (batched openings; no counterpart there)
 //!
 //! Data crosses the boundary in arkworks' own in-memory form (`Fp256.0 .0`: 4 LE u64 limbs of the Montgomery residue;
 //! `Fp384.0 .0`: 6), so nothing is converted -- coordinates are copied limb-wise because `GroupAffine` is `repr(Rust)`.
@@ -352,6 +354,51 @@ impl Backend {
                                 if pis.is_empty() { ptr::null() } else { pis.as_ptr() },
                                 if lens.is_empty() { ptr::null() } else { lens.as_ptr() },
                                 if pi_as_prover { VERIFY_PI_AS_PROVER } else { 0 }, ok.as_mut_ptr())
+        });
+        ok[..proofs.len()].iter().map(|&b| b != 0).collect()
+    }
+
+    // ---- the compact proof shape (include/typlonk.h): batched openings, a transcript that binds the statement ----------
+    /// The verifying key of a loaded circuit (`typlonk_circuit_vk`): all `verify_compact` needs, on any backend.
+    pub fn verifying_key(&self, srs: SrsHandle, circuit: CircuitHandle, cosets: [Fr; 3], g2s: &[u64; 24]) -> ffi::TyplonkVk {
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut vk = std::mem::MaybeUninit::<ffi::TyplonkVk>::zeroed();
+        self.check(unsafe { ffi::typlonk_circuit_vk(self.ctx, srs.id, circuit.id, k.as_ptr(), g2s.as_ptr(), vk.as_mut_ptr()) });
+        unsafe { vk.assume_init() }
+    }
+
+    /// A compact proof (`typlonk_prove_compact_host`): `wire_evals` as for `prove`; `public_inputs` = the statement's public
+    /// values themselves (at most n, not padded: their number is part of the statement).  Panics on an unsatisfied witness.
+    pub fn prove_compact(&self, srs: SrsHandle, circuit: CircuitHandle, wire_evals: [&[Fr]; 3], public_inputs: &[Fr],
+                         cosets: [Fr; 3]) -> ffi::TyplonkProofCompact {
+        let rows = wire_evals[0].len();   // the library checks it against the circuit's n
+        assert!(wire_evals.iter().all(|c| c.len() == rows), "three columns of equal length");
+        let flat = |c: &[Fr]| -> Vec<u64> { c.iter().flat_map(|e| fr_limbs(e)).collect() };
+        let w: Vec<Vec<u64>> = wire_evals.iter().map(|c| flat(c)).collect();
+        let wp: [*const u64; 3] = [w[0].as_ptr(), w[1].as_ptr(), w[2].as_ptr()];
+        let pi = flat(public_inputs);
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut out = std::mem::MaybeUninit::<ffi::TyplonkProofCompact>::zeroed();
+        self.check(unsafe {
+            ffi::typlonk_prove_compact_host(self.ctx, srs.id, circuit.id, wp.as_ptr(), rows,
+                                            if pi.is_empty() { ptr::null() } else { pi.as_ptr() }, public_inputs.len(),
+                                            k.as_ptr(), out.as_mut_ptr())
+        });
+        unsafe { out.assume_init() }
+    }
+
+    /// `typlonk_verify_compact`: a batch of compact proofs against a verifying key; needs no SRS and no circuit on this
+    /// backend.  `public_inputs`: empty, or one list of public values per proof.
+    pub fn verify_compact(&self, vk: &ffi::TyplonkVk, proofs: &[ffi::TyplonkProofCompact], public_inputs: &[Vec<Fr>]) -> Vec<bool> {
+        assert!(public_inputs.is_empty() || public_inputs.len() == proofs.len(), "one public-input list per proof");
+        let cols: Vec<Vec<u64>> = public_inputs.iter().map(|c| c.iter().flat_map(|e| fr_limbs(e)).collect()).collect();
+        let pis: Vec<*const u64> = cols.iter().map(|c| if c.is_empty() { ptr::null() } else { c.as_ptr() }).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|c| c.len()).collect();
+        let mut ok = vec![0u8; proofs.len().max(1)];
+        self.check(unsafe {
+            ffi::typlonk_verify_compact(self.ctx, vk, proofs.as_ptr(), proofs.len(),
+                                        if pis.is_empty() { ptr::null() } else { pis.as_ptr() },
+                                        if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, ok.as_mut_ptr())
         });
         ok[..proofs.len()].iter().map(|&b| b != 0).collect()
     }

@@ -31,6 +31,7 @@ SYMBOLS = [
     "typlonk_comm_available", "typlonk_comm_unique_id", "typlonk_comm_init", "typlonk_comm_destroy", "typlonk_comm_info", "typlonk_comm_fold_g1",
     "typlonk_msm_g1_sharded_devptr", "typlonk_msm_g1_sharded_batch_devptr", "typlonk_g1_fold_records_host",
     "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify", "typlonk_prove_batch", "typlonk_prove_batch_host",
+    "typlonk_circuit_vk", "typlonk_prove_compact", "typlonk_prove_compact_host", "typlonk_verify_compact", "typlonk_compact_challenges",
 ]
 VERIFY_PI_AS_PROVER = 1
 
@@ -70,6 +71,116 @@ class Proof(C.Structure):
     _fields_ = [("commit_xy", (C.c_uint64 * 12) * 3), ("commit_inf", C.c_uint8 * 3), ("z_xy", C.c_uint64 * 12),
                 ("z_inf", C.c_uint8), ("tail", ProofTail), ("beta", C.c_uint64 * 4), ("gamma", C.c_uint64 * 4),
                 ("alpha", C.c_uint64 * 4), ("zeta", C.c_uint64 * 4)]
+
+
+class Vk(C.Structure):
+    """typlonk_vk: the verifying key of the compact proof shape"""
+    _fields_ = [("log_n", C.c_uint32), ("cosets", (C.c_uint64 * 4) * 3), ("commit_xy", (C.c_uint64 * 12) * 8),
+                ("commit_inf", C.c_uint8 * 8), ("srs0_xy", C.c_uint64 * 12), ("srs0_inf", C.c_uint8), ("g2s_xy", C.c_uint64 * 24)]
+
+
+class ProofCompact(C.Structure):
+    """typlonk_proof_compact"""
+    _fields_ = [("commit_xy", (C.c_uint64 * 12) * 3), ("commit_inf", C.c_uint8 * 3), ("z_xy", C.c_uint64 * 12),
+                ("z_inf", C.c_uint8), ("t_xy", (C.c_uint64 * 12) * 3), ("t_inf", C.c_uint8 * 3), ("w_xy", (C.c_uint64 * 12) * 2),
+                ("w_inf", C.c_uint8 * 2), ("evals", (C.c_uint64 * 4) * 7), ("beta", C.c_uint64 * 4), ("gamma", C.c_uint64 * 4),
+                ("alpha", C.c_uint64 * 4), ("zeta", C.c_uint64 * 4), ("v", C.c_uint64 * 4)]
+
+
+COMPACT_CHALLENGES = ("beta", "gamma", "alpha", "zeta", "v")
+
+
+def compact_dict(pr: ProofCompact) -> dict:
+    """typlonk_proof_compact -> {"commit": [(xy, inf)] * 3, "z_commit", "t_commit": [...] * 3, "witness": [W_zeta, W_zeta_w],
+    "evals": 7 x 4 limbs (a b c Z(zeta) Z(zeta w) sigma_1 sigma_2), "challenges": beta gamma alpha zeta v}"""
+    pt = lambda xy, f: (np.array(xy, dtype=np.uint64), int(f))   # noqa: E731
+    return {
+        "commit": [pt(pr.commit_xy[i], pr.commit_inf[i]) for i in range(3)],
+        "z_commit": pt(pr.z_xy, pr.z_inf),
+        "t_commit": [pt(pr.t_xy[i], pr.t_inf[i]) for i in range(3)],
+        "witness": [pt(pr.w_xy[i], pr.w_inf[i]) for i in range(2)],
+        "evals": [np.array(pr.evals[i], dtype=np.uint64) for i in range(7)],
+        "challenges": {k: np.array(getattr(pr, k), dtype=np.uint64) for k in COMPACT_CHALLENGES},
+    }
+
+
+def compact_struct(d) -> ProofCompact:
+    """the inverse of compact_dict (a dict without "challenges" leaves them zero: the verifier recomputes them)"""
+    if isinstance(d, ProofCompact):
+        return d
+    pr = ProofCompact()
+
+    def put(dst, val, k):
+        dst[:] = [int(v) for v in np.asarray(val, dtype=np.uint64).reshape(k)]
+
+    for i, (xy, f) in enumerate(d["commit"]):
+        put(pr.commit_xy[i], xy, 12)
+        pr.commit_inf[i] = int(f)
+    put(pr.z_xy, d["z_commit"][0], 12)
+    pr.z_inf = int(d["z_commit"][1])
+    for i, (xy, f) in enumerate(d["t_commit"]):
+        put(pr.t_xy[i], xy, 12)
+        pr.t_inf[i] = int(f)
+    for i, (xy, f) in enumerate(d["witness"]):
+        put(pr.w_xy[i], xy, 12)
+        pr.w_inf[i] = int(f)
+    for i, e in enumerate(d["evals"]):
+        put(pr.evals[i], e, 4)
+    for k, val in d.get("challenges", {}).items():
+        put(getattr(pr, k), val, 4)
+    return pr
+
+
+def vk_from(log_n: int, cosets, commitments, srs0, g2s_xy) -> Vk:
+    """a typlonk_vk from its parts: cosets = 3 x 4 limbs, commitments = [(xy, inf)] * 8, srs0 = (xy, inf), g2s_xy = 24 limbs"""
+    vk = Vk()
+    vk.log_n = log_n
+    for i in range(3):
+        vk.cosets[i][:] = [int(v) for v in np.asarray(cosets[i], dtype=np.uint64).reshape(4)]
+    for i, (xy, f) in enumerate(commitments):
+        vk.commit_xy[i][:] = [int(v) for v in np.asarray(xy, dtype=np.uint64).reshape(12)]
+        vk.commit_inf[i] = int(f)
+    vk.srs0_xy[:] = [int(v) for v in np.asarray(srs0[0], dtype=np.uint64).reshape(12)]
+    vk.srs0_inf = int(srs0[1])
+    vk.g2s_xy[:] = [int(v) for v in np.asarray(g2s_xy, dtype=np.uint64).reshape(24)]
+    return vk
+
+
+def _cosets_arg(cosets):
+    ks = ((C.c_uint64 * 4) * 3)()
+    for i in range(3):
+        for j, limb in enumerate(np.asarray(cosets[i], dtype=np.uint64).reshape(4)):
+            ks[i][j] = int(limb)
+    return ks
+
+
+def _pi_arg(pi, k: int):
+    """None or one (l, 4) column (or None) per proof -> (keep-alive list, u64** or None, size_t* or None)"""
+    if pi is None:
+        return [], None, None
+    keep = []
+    pip = (C.POINTER(C.c_uint64) * max(k, 1))()
+    lens = (C.c_size_t * max(k, 1))()
+    for i, col in enumerate(pi):
+        if col is None:
+            continue
+        c = np.ascontiguousarray(_as_u64(col, 4))
+        keep.append(c)
+        pip[i] = _u64p(c)
+        lens[i] = c.shape[0]
+    return keep, pip, lens
+
+
+def compact_challenges(vk: Vk, proof, pi=None):
+    """typlonk_compact_challenges (host-only): [beta, gamma, alpha, zeta, v] of a compact proof (dict or struct), 4 limbs each"""
+    lib = load_library()
+    pr = compact_struct(proof)
+    col = np.ascontiguousarray(_as_u64(pi, 4)) if pi is not None else np.zeros((0, 4), dtype=np.uint64)
+    out = ((C.c_uint64 * 4) * 5)()
+    rc = lib.typlonk_compact_challenges(C.byref(vk), C.byref(pr), _u64p(col) if col.shape[0] else None, col.shape[0], out)
+    if rc:
+        raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
+    return [np.array(out[i], dtype=np.uint64) for i in range(5)]
 
 
 _lib = None
@@ -155,6 +266,16 @@ def load_library() -> C.CDLL:
         lib.typlonk_prove_batch_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(u64p), C.POINTER(u64p), C.c_size_t,
                                                  C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Proof), C.POINTER(C.c_int)]
     lib.typlonk_transcript_challenges.argtypes = [u64p, u8p, C.c_size_t, C.c_size_t, u64p]
+    if hasattr(lib, "typlonk_prove_compact") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_circuit_vk.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), u64p, C.POINTER(Vk)]
+        lib.typlonk_prove_compact.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp), vp, C.c_size_t,
+                                              C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(ProofCompact)]
+        lib.typlonk_prove_compact_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(u64p), C.c_size_t, u64p, C.c_size_t,
+                                                   C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(ProofCompact)]
+        lib.typlonk_verify_compact.argtypes = [vp, C.POINTER(Vk), C.POINTER(ProofCompact), C.c_size_t, C.POINTER(u64p),
+                                               C.POINTER(C.c_size_t), u8p]
+        lib.typlonk_compact_challenges.argtypes = [C.POINTER(Vk), C.POINTER(ProofCompact), u64p, C.c_size_t,
+                                                   C.POINTER(C.c_uint64 * 4)]
     lib.typlonk_prover_free.argtypes = [vp]
     lib.typlonk_prover_free.restype = None
     lib.typlonk_circuit_load.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -565,6 +686,65 @@ class Context:
         ok = np.zeros(max(k, 1), dtype=np.uint8)
         self._chk(self.lib.typlonk_verify(self.h, sid, circuit, _u64p(g2), C.byref(ks), arr, k, pip, lens,
                                           VERIFY_PI_AS_PROVER if pi_as_prover else 0, _u8p(ok)))
+        return ok[:k].astype(bool)
+
+    # ---- the compact proof shape (include/typlonk.h, typlonk_prove_compact) ----------------------------------------------
+    def circuit_vk(self, sid: int, circuit: int, cosets, g2s_xy) -> Vk:
+        """typlonk_circuit_vk: the verifying key (the cached circuit commitments, SRS point 0, the cosets, [s]G2)"""
+        vk = Vk()
+        g2 = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
+        self._chk(self.lib.typlonk_circuit_vk(self.h, sid, circuit, C.byref(_cosets_arg(cosets)), _u64p(g2), C.byref(vk)))
+        return vk
+
+    def _prove_compact(self, rc: int, pr: ProofCompact) -> dict:
+        """a compact_dict; TYPLONK_ERR_UNSATISFIED raises with the filled proof attached as .proof"""
+        d = compact_dict(pr)
+        if rc == ERR_UNSATISFIED:
+            err = TyplonkError(rc, self.lib.typlonk_strerror(rc).decode() + ": " + self.lib.typlonk_last_error(self.h).decode())
+            err.proof = d
+            raise err
+        self._chk(rc)
+        return d
+
+    def prove_compact(self, sid: int, circuit: int, wire_evals, pi=None, pi_len: int | None = None, cosets=None) -> dict:
+        """typlonk_prove_compact: wire_evals = [a, b, c] DeviceBuffers; pi = a DeviceBuffer of >= pi_len public values (pi_len
+        defaults to its length) or None.  Returns compact_dict(proof)."""
+        w = (C.c_void_p * 3)(*[b.handle.value for b in wire_evals])
+        if pi_len is None:
+            pi_len = pi.n if pi is not None else 0
+        pr = ProofCompact()
+        rc = self.lib.typlonk_prove_compact(self.h, sid, circuit, w, pi.handle if pi is not None else None, pi_len,
+                                            C.byref(_cosets_arg(cosets)), C.byref(pr))
+        return self._prove_compact(rc, pr)
+
+    def prove_compact_host(self, sid: int, circuit: int, wire_evals_host, pi=None, cosets=None) -> dict:
+        """typlonk_prove_compact_host: three (n, 4) u64 host columns of equal length, pi = None or an (l, 4) column of l public
+        values.  The row count is passed on and checked against the circuit's n by the library."""
+        cols = [np.ascontiguousarray(w, dtype=np.uint64) for w in wire_evals_host]
+        if len(cols) != 3 or any(c.ndim != 2 or c.shape[1] != 4 or c.shape != cols[0].shape for c in cols):
+            raise ValueError("prove_compact_host needs three (rows, 4) uint64 columns of equal length")
+        w = (C.POINTER(C.c_uint64) * 3)(*[_u64p(c) for c in cols])
+        pic = None
+        if pi is not None:
+            pic = np.ascontiguousarray(pi, dtype=np.uint64)
+            if pic.ndim != 2 or pic.shape[1] != 4:
+                raise ValueError("pi must be an (l, 4) uint64 column")
+        pr = ProofCompact()
+        rc = self.lib.typlonk_prove_compact_host(self.h, sid, circuit, w, cols[0].shape[0],
+                                                 _u64p(pic) if pic is not None and pic.shape[0] else None,
+                                                 pic.shape[0] if pic is not None else 0, C.byref(_cosets_arg(cosets)), C.byref(pr))
+        return self._prove_compact(rc, pr)
+
+    def verify_compact(self, vk: Vk, proofs, pi=None) -> np.ndarray:
+        """typlonk_verify_compact: proofs = compact dicts (or ProofCompact structs); pi = None or one entry per proof, each
+        None or an (l, 4) column of its public values.  Needs no SRS and no loaded circuit.  Returns a bool array."""
+        k = len(proofs)
+        arr = (ProofCompact * max(k, 1))()
+        for i, p in enumerate(proofs):
+            arr[i] = compact_struct(p)
+        keep, pip, lens = _pi_arg(pi, k)  # noqa: F841 (keep: the columns stay alive across the call)
+        ok = np.zeros(max(k, 1), dtype=np.uint8)
+        self._chk(self.lib.typlonk_verify_compact(self.h, C.byref(vk), arr, k, pip, lens, _u8p(ok)))
         return ok[:k].astype(bool)
 
     def lincomb_dev(self, polys, scalars, n: int, out: DeviceBuffer, constant=None):

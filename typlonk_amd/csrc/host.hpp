@@ -5,6 +5,7 @@
 //   comm.hip      RCCL exchange behind the C ABI
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
+//   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -351,6 +352,10 @@ void lin_scalars(const Fr* ev, const Fr& s0, const Fr& s1, const Fr& pi_z, const
 // 4 Montgomery limbs per element).  Blocks for the result.
 int poly_eval_run(typlonk_ctx* ctx, const Fr* const* polys, size_t count, uint64_t m, const uint64_t* points, size_t n_points,
                   uint64_t* out);
+// the eight commitments of a circuit over a whole SRS (>= n points): computed on first use per (circuit, SRS), then cached
+int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const CircuitEntry::Commitments** out);
+// a verifying key without [s]G2 (zero): log_n, cosets, the eight commitments, SRS point 0
+int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4], typlonk_vk* vk);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------
 void comm_release(typlonk_ctx* ctx);

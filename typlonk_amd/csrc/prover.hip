@@ -3,6 +3,7 @@
 // fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #include "host.hpp"
 #include "transcript.hpp"
+#include "compact_transcript.hpp"
 
 using namespace ty;
 using namespace tyh;
@@ -401,6 +402,7 @@ namespace {
 struct ColumnSrc {
     const Fr* dev = nullptr;
     const uint64_t* host = nullptr;
+    uint64_t rows = ~0ull;   // rows read from dev / host (the compact shape's public inputs); the rest of the n are zero
     bool present() const { return dev || host; }
 };
 int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnSrc (&wires)[3], const ColumnSrc& pi,
@@ -473,6 +475,12 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     // column, each right before that column's transform and commitment are queued, so column i + 1 crosses PCIe while column i
     // is being transformed, sorted and accumulated
     auto fetch = [&](Fr* dst, const ColumnSrc& c) -> int {
+        if (c.rows < n) {
+            hipError_t e = c.dev ? hipMemcpyAsync(dst, c.dev, c.rows * sizeof(Fr), hipMemcpyDeviceToDevice, s)
+                                 : hipMemcpyAsync(dst, c.host, c.rows * sizeof(Fr), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemsetAsync(dst + c.rows, 0, (n - c.rows) * sizeof(Fr), s);
+            return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
+        }
         if (c.dev) return d2d(dst, c.dev);
         const hipError_t e = hipMemcpyAsync(dst, c.host, n * sizeof(Fr), hipMemcpyHostToDevice, s);
         return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
@@ -891,6 +899,242 @@ int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typ
     return rc;
 }
 }  // namespace
+
+// ================================================================================================
+// The compact shape (include/typlonk.h, typlonk_prove_compact): rounds 1 and 2 as in typlonk_prove, then round 3 in the
+// compact transcript's order -- the quotient is committed before zeta is drawn, sigma_1(zeta) and sigma_2(zeta) are sent, and
+// every opening at zeta is one witness of F = a + v b + v^2 c + v^3 Z + v^4 r + v^5 sigma_1 + v^6 sigma_2.
+namespace {
+int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al, typlonk_proof_compact* out) {
+    typlonk_ctx* ctx = p->ctx;
+    if (p->round != 2) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "round3 must follow round2");
+    HIPCHK(hipSetDevice(ctx->device));
+    auto cit = ctx->circuits.find(p->circuit);
+    if (cit == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "circuit was freed during the proof");
+    const CircuitEntry& ce = cit->second;
+    const uint64_t n = p->n;
+    const uint32_t log_n = p->log_n;
+    ProfilingOff prof_off(ctx);  // stage events are per call
+    ProverRound in_round(ctx);
+    const SrsEntry* srs = nullptr;
+    int rc = msm_validate(ctx, p->srs_id, n, &srs);
+    if (rc) return rc;
+    if (!ctx->batch_fence) HIPCHK(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+    // the queue outlives every early return (its destructor-side wait below): the MSMs write into `out`
+    MsmQueue q(ctx, srs, /*first_lane=*/0);
+    struct WaitAll {
+        MsmQueue& q;
+        ~WaitAll() { (void)q.wait_all(); }
+    } wait_guard{q};
+    auto record_fence = [&]() -> int {
+        const hipError_t he = hipEventRecord(ctx->batch_fence, ctx->stream);
+        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        q.fence = ctx->batch_fence;   // the lanes wait for what is queued NOW, not for later work on the context's stream
+        return TYPLONK_OK;
+    };
+    // ---- the quotient (proof.rs:139-145) as soon as alpha is known; its three slices (:181) committed behind a fence ----
+    {
+        typlonk_buf b[5] = {{p->co[0], n}, {p->co[1], n}, {p->co[2], n}, {p->z, n}, {p->pi, n}};
+        typlonk_buf tb{p->t, 4 * n};
+        typlonk_quotient_args qa{};
+        for (int i = 0; i < 3; ++i) qa.wires[i] = &b[i];
+        qa.z = &b[3];
+        qa.public_inputs = p->has_pi ? &b[4] : nullptr;
+        memcpy(qa.alpha, al.v, 32);
+        memcpy(qa.beta, p->beta.v, 32);
+        memcpy(qa.gamma, p->gamma.v, 32);
+        for (int i = 0; i < 3; ++i) memcpy(qa.cosets[i], p->k[i].v, 32);
+        qa.circuit = p->circuit;
+        rc = quotient_run(ctx, &qa, log_n, &tb, p->extended);
+    }
+    if (!rc) rc = record_fence();
+    if (!rc) {
+        const Fr* polys[3] = {p->t, p->t + n, p->t + 2 * n};
+        const size_t m[3] = {n, n, n > 3 ? n - 3 : 0};
+        for (int k = 0; k < 3 && !rc; ++k) rc = q.submit(polys[k], m[k], out->t_xy[k], out->t_inf + k);
+    }
+    {
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    // ---- zeta binds the quotient ----
+    for (int i = 0; i < 3; ++i) tr.point(out->t_xy[i], out->t_inf[i]);
+    const Fr ze = tr.squeeze('z');
+    const Fr zw = fe_mul(ze, fr_domain_root(log_n));
+    // ---- a, b, c, Z, sigma_1, sigma_2, PI at zeta and Z at zeta*w with its quotient: one launch_open_multi, one fetch.
+    // Result slots 0..6 = the seven evaluations of the proof in order, 7 = PI(zeta) ----
+    Fr host[8];
+    Fr zn, zh, l0z;
+    {
+        Fr *blocks = nullptr, *slots = nullptr;
+        rc = prover_ops_tmp(p, &blocks, &slots);
+        if (rc) return rc;
+        const Fr* polys[8];
+        Fr* quots[8];
+        Fr* ys[8];
+        uint8_t zsel[8];
+        uint32_t cnt = 0;
+        auto item = [&](const Fr* poly, Fr* quot, int slot, uint8_t at) {
+            polys[cnt] = poly;
+            quots[cnt] = quot;
+            ys[cnt] = slots + slot;
+            zsel[cnt++] = at;
+        };
+        for (int i = 0; i < 3; ++i) item(p->co[i], nullptr, i, 0);
+        item(p->z, nullptr, 3, 0);
+        item(ce.coef + 5 * n, nullptr, 5, 0);             // sigma_1
+        item(ce.coef + 6 * n, nullptr, 6, 0);             // sigma_2
+        if (p->has_pi) item(p->pi, nullptr, 7, 0);
+        item(p->z, p->q[4], 4, 1);                        // Z at zeta * w, with its quotient
+        launch_open_multi(polys, quots, ys, zsel, cnt, n, ze, zw, blocks, ctx->stream);
+        const hipError_t he = hipGetLastError();
+        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);   // while the kernels run
+        rc = prover_fetch(p, host, 8);
+        if (rc) return rc;
+    }
+    const Fr pi_z = p->has_pi ? host[7] : Fr::zero();
+    for (int i = 0; i < 7; ++i) {
+        memcpy(out->evals[i], host[i].v, 32);
+        tr.scalar(out->evals[i]);
+    }
+    const Fr v = tr.squeeze('v');
+    memcpy(out->zeta, ze.v, 32);
+    memcpy(out->v, v.v, 32);
+    // ---- r (proof.rs:376-439, with +PI(zeta) as typlonk_prove); r(zeta) lands in slot 0 and is read after the commitments ----
+    {
+        LincombArgs la{};
+        lin_scalars(host, host[5], host[6], pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, la.scalar, &la.constant);
+        const Fr* polys[LIN_TERMS] = {ce.coef + 0 * n, ce.coef + 1 * n, ce.coef + 2 * n, ce.coef + 3 * n, ce.coef + 4 * n,
+                                      p->z, ce.coef + 7 * n, p->t, p->t + n, p->t + 2 * n};
+        for (int k = 0; k < LIN_TERMS; ++k) la.poly[k] = polys[k];
+        la.terms = LIN_TERMS;
+        la.out = p->r;
+        la.n = n;
+        launch_lincomb(la, ctx->stream);
+        const hipError_t he = hipGetLastError();
+        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+    }
+    rc = prover_open_async(p, p->r, n, ze, nullptr, 0);
+    // ---- F as one 7-term combination in q[1], its witness polynomial in q[0] (q[0..3] are free in this shape) ----
+    if (!rc) {
+        LincombArgs fa{};
+        const Fr* polys[7] = {p->co[0], p->co[1], p->co[2], p->z, p->r, ce.coef + 5 * n, ce.coef + 6 * n};
+        Fr pw = Fr::one();
+        for (int i = 0; i < 7; ++i) {
+            fa.poly[i] = polys[i];
+            fa.scalar[i] = pw;
+            pw = fe_mul(pw, v);
+        }
+        fa.terms = 7;
+        fa.constant = Fr::zero();
+        fa.out = p->q[1];
+        fa.n = n;
+        launch_lincomb(fa, ctx->stream);
+        const hipError_t he = hipGetLastError();
+        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+    }
+    if (!rc) rc = prover_open_async(p, p->q[1], n, ze, p->q[0], 1);   // F(zeta) itself is not needed
+    // ---- W_zeta and W_zeta_w in one queue ----
+    if (!rc) rc = record_fence();
+    if (!rc) rc = q.submit(p->q[0], n - 1, out->w_xy[0], out->w_inf + 0);
+    if (!rc) rc = q.submit(p->q[4], n - 1, out->w_xy[1], out->w_inf + 1);
+    {
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    Fr rz;
+    if (!rc) rc = prover_fetch(p, &rz, 1);   // (every lane has been waited for: this returns at once)
+    if (rc) return rc;
+    p->round = 3;
+    if (!rz.is_zero())
+        return fail(ctx, TYPLONK_ERR_UNSATISFIED, "r(zeta) != 0: the witness does not satisfy the circuit");
+    return TYPLONK_OK;
+}
+
+// rows: the host form's column length (must be n), SIZE_MAX for the device form
+int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
+                       const uint64_t* const* wire_host, size_t rows, const typlonk_buf* pi_buf, const uint64_t* pi_host,
+                       size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
+    auto ci = ctx->circuits.find(circuit_id);
+    if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
+    const uint32_t log_n = ci->second.log_n;
+    if (log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "prover supports up to 2^24 rows");
+    const uint64_t n = 1ull << log_n;
+    auto si = ctx->srs.find(srs_id);
+    if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
+    if (si->second.total_len) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "compact proofs need a whole SRS, not a shard");
+    if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
+    if (pi_len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
+    if (!wire_bufs && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
+    ColumnSrc w[3], pi;
+    for (int i = 0; i < 3; ++i) {
+        if (wire_bufs) {
+            if (!wire_bufs[i] || wire_bufs[i]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
+            w[i].dev = wire_bufs[i]->d;
+        } else {
+            w[i].host = wire_host[i];
+        }
+    }
+    if (pi_len) {
+        if (pi_buf && pi_buf->n < pi_len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
+        pi.dev = pi_buf ? pi_buf->d : nullptr;
+        pi.host = pi_host;
+        pi.rows = pi_len;
+    }
+    memset(out, 0, sizeof(*out));
+    // the statement: the circuit's commitments (one batch of eight MSMs the first time per circuit and SRS, then cached), P0,
+    // and the pi_len public values -- brought to the host once in the device form
+    typlonk_vk vk;
+    int rc = circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
+    if (rc) return rc;
+    std::vector<uint64_t> pi_vals;
+    const uint64_t* piv = pi_host;
+    if (pi.dev) {
+        pi_vals.resize(4 * pi_len);
+        HIPCHK(hipMemcpyAsync(pi_vals.data(), pi.dev, pi_len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        piv = pi_vals.data();
+    }
+    uint8_t d0[64];
+    compact_statement_digest(vk, piv, pi_len, d0);
+    typlonk_prover* p = nullptr;
+    rc = prover_round1_impl(ctx, srs_id, circuit_id, w, pi, &p, out->commit_xy, out->commit_inf);
+    if (rc) return rc;
+    CompactTranscript tr(d0);
+    for (int i = 0; i < 3; ++i) tr.point(out->commit_xy[i], out->commit_inf[i]);
+    const Fr beta = tr.squeeze('b'), gamma = tr.squeeze('g');
+    memcpy(out->beta, beta.v, 32);
+    memcpy(out->gamma, gamma.v, 32);
+    rc = typlonk_prover_round2(p, out->beta, out->gamma, cosets, out->z_xy, &out->z_inf);
+    if (!rc) {
+        tr.point(out->z_xy, out->z_inf);
+        const Fr alpha = tr.squeeze('a');
+        memcpy(out->alpha, alpha.v, 32);
+        rc = prover_round3_compact(p, tr, alpha, out);
+    }
+    typlonk_prover_free(p);
+    return rc;
+}
+}  // namespace
+
+int typlonk_prove_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
+                          const typlonk_buf* pi, size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
+    if (!ctx || !wire_evals || !cosets || !out || (pi_len && !pi)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    return prove_compact_impl(ctx, srs_id, circuit_id, wire_evals, nullptr, SIZE_MAX, pi, nullptr, pi_len, cosets, out);
+}
+
+int typlonk_prove_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
+                               size_t rows, const uint64_t* pi, size_t pi_len, const uint64_t cosets[3][4],
+                               typlonk_proof_compact* out) {
+    if (!ctx || !wire_evals || !cosets || !out || (pi_len && !pi)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    for (int i = 0; i < 3; ++i)
+        if (!wire_evals[i]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
+    return prove_compact_impl(ctx, srs_id, circuit_id, nullptr, wire_evals, rows, nullptr, pi, pi_len, cosets, out);
+}
 
 void typlonk_prover_free(typlonk_prover* p) {
     if (!p) return;

@@ -709,11 +709,7 @@ class CompiledCircuit {
             std::memcpy(r.zeta, p.evaluation_point.limbs(), 32);
         }
         uint64_t g2s[24];
-        const pairing::G2Affine& q = srs_.g2s();
-        std::memcpy(g2s, q.x.a.v, 48);
-        std::memcpy(g2s + 6, q.x.b.v, 48);
-        std::memcpy(g2s + 12, q.y.a.v, 48);
-        std::memcpy(g2s + 18, q.y.b.v, 48);
+        g2s_limbs(g2s);
         uint64_t ks[3][4];
         for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
         std::vector<const uint64_t*> pis(proofs.size(), nullptr);
@@ -730,7 +726,43 @@ class CompiledCircuit {
         return std::vector<bool>(ok.begin(), ok.begin() + proofs.size());
     }
 
+    // ---- the compact proof shape (include/typlonk.h): batched openings, a transcript that binds the statement ----
+    // The verifying key: all typlonk_verify_compact needs instead of this object (log n, the cosets, the eight commitments,
+    // SRS point 0 and the SRS's [s]G2).
+    typlonk_vk verifying_key() const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        uint64_t g2s[24], ks[3][4];
+        g2s_limbs(g2s);
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        typlonk_vk vk;
+        check(typlonk_circuit_vk(c, srs_.id(), circuit_, ks, g2s, &vk), c);
+        return vk;
+    }
+    // A compact proof (typlonk_prove_compact_host): `advice` as for prove(); `public_inputs` = the statement's public values
+    // themselves (at most n, not padded: their number is part of the statement).  A witness that does not satisfy the circuit
+    // throws, as prove() does.
+    typlonk_proof_compact prove_compact(const std::vector<Fr> (&advice)[3], const std::vector<Fr>& public_inputs = {}) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        for (int i = 0; i < 3; ++i)
+            if (advice[i].size() != n_) throw std::runtime_error("witness column must hold n values");
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        const uint64_t* wc[3] = {advice[0][0].limbs(), advice[1][0].limbs(), advice[2][0].limbs()};
+        typlonk_proof_compact out;
+        check(typlonk_prove_compact_host(c, srs_.id(), circuit_, wc, n_, public_inputs.empty() ? nullptr : public_inputs[0].limbs(),
+                                         public_inputs.size(), ks, &out),
+              c);
+        return out;
+    }
+
    private:
+    void g2s_limbs(uint64_t g2s[24]) const {
+        const pairing::G2Affine& q = srs_.g2s();
+        std::memcpy(g2s, q.x.a.v, 48);
+        std::memcpy(g2s + 6, q.x.b.v, 48);
+        std::memcpy(g2s + 12, q.y.a.v, 48);
+        std::memcpy(g2s + 18, q.y.b.v, 48);
+    }
     typlonk_buf* upload(const std::vector<Fr>& v) const {
         typlonk_ctx* c = srs_.ctx().raw();
         typlonk_buf* b = nullptr;
@@ -749,6 +781,23 @@ class CompiledCircuit {
     uint32_t circuit_ = 0;
     poly::DensePolynomial sigma_polys_[3];
 };
+
+// typlonk_verify_compact: compact proofs against a verifying key, on any context -- it needs no SRS and no loaded circuit.
+// public_inputs: empty, or one list of public values per proof (each empty = none).  result[k] = proof k is accepted.
+inline std::vector<bool> verify_compact(const Context& ctx, const typlonk_vk& vk, const std::vector<typlonk_proof_compact>& proofs,
+                                        const std::vector<std::vector<Fr>>& public_inputs = {}) {
+    if (!public_inputs.empty() && public_inputs.size() != proofs.size()) throw std::runtime_error("one public-input list per proof");
+    std::vector<const uint64_t*> pis(proofs.size(), nullptr);
+    std::vector<size_t> lens(proofs.size(), 0);
+    for (size_t k = 0; k < public_inputs.size(); ++k)
+        if (!public_inputs[k].empty()) {
+            pis[k] = public_inputs[k][0].limbs();
+            lens[k] = public_inputs[k].size();
+        }
+    std::vector<uint8_t> ok(proofs.size() + 1, 0);
+    check(typlonk_verify_compact(ctx.raw(), &vk, proofs.data(), proofs.size(), pis.data(), lens.data(), ok.data()), ctx.raw());
+    return std::vector<bool>(ok.begin(), ok.begin() + proofs.size());
+}
 
 }  // namespace plonk
 }  // namespace typlonk
