@@ -4,6 +4,8 @@
   tests/cpp/hooks/libtyplonk_hip.so  the same library with the fault-injection hook (-DTYPLONK_TEST_HOOKS, tests only) -- hipcc
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
+  tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
+  tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
 Every target is rebuilt only when one of its sources is newer than the output.
@@ -139,6 +141,28 @@ def build_device_arith(force: bool = False) -> str:
     return out
 
 
+def build_fq30_pair_host(force: bool = False) -> str:
+    """tests/cpp/libfq30_pair_host.so: fq30_mul_pair / fq30_sqr_pair / fq30_mul2_add as the host compiles them"""
+    src = os.path.join(ROOT, "tests", "cpp", "fq30_pair_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "libfq30_pair_host.so")
+    deps = [src, os.path.join(ROOT, "tests", "cpp", "fq30_pair_harness.hpp"), os.path.join(CSRC, "ff.hpp"), os.path.join(CSRC, "fq30.hpp")]
+    if force or _stale(out, deps):
+        _run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out])
+    return out
+
+
+def build_device_pair(force: bool = False) -> str:
+    """tests/cpp/libdevice_pair.so: the same functions' device code (the interleaved chains of fq30_pair.hpp) behind an
+    element-wise test kernel.  Test-only; the flags are build_hip()'s."""
+    src = os.path.join(ROOT, "tests", "cpp", "device_pair.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_pair.so")
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
+    hdrs.append(os.path.join(ROOT, "tests", "cpp", "fq30_pair_harness.hpp"))
+    if force or _stale(out, [src] + hdrs):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
 def build_host_tests(force: bool = False) -> list[str]:
     """test binaries of the C++ host mirror (typlonk_amd/host/typlonk_host.hpp), linked to the HIP library"""
     outs = []
@@ -172,6 +196,8 @@ def build_all(force: bool = False) -> None:
     build_hip_test_hooks(force)
     build_host_shim(force)
     build_device_arith(force)
+    build_fq30_pair_host(force)
+    build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)
 

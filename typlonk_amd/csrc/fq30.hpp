@@ -297,14 +297,55 @@ TY_HD void fq30_mul_wide(const Fq30& a, const Fq30& b, uint32_t (&T)[26]) {
     }
     T[25] = (uint32_t)acc;
 }
+// ---- paired products: two independent multiplications as two interleaved column chains -------------------------------
+// On the device every column of the two chains is one inline-asm statement (fq30_pair.hpp, written by
+// tools/gen_fq30_pair.py) in which the mads of chain A and chain B alternate, each chain accumulating in place from its
+// shifted carry: each chain's mad fills the other's wait slot, and no column needs a fresh accumulator merged by a 64-bit
+// add.  Order of the terms and carry capture per chain are fq30_mulsqr_fused's, so the bounds, the contract and the
+// result digits are those of two fq30_mul_fused / fq30_sqr_fused calls, which is what the host build runs.
+#if defined(__HIP_DEVICE_COMPILE__)
+#include "fq30_pair.hpp"
+#endif
+
+// ab = a*b*2^-390, cd = c*d*2^-390 (each as fq30_mul)
+TY_HD void fq30_mul_pair(const Fq30& a, const Fq30& b, const Fq30& c, const Fq30& d, Fq30& ab, Fq30& cd) {
+    Fq30 x, y;
+#if defined(__HIP_DEVICE_COMPILE__)
+    fq30_mul_pair_dev(a, b, c, d, x, y);
+#else
+    x = fq30_mul_fused(a, b);
+    y = fq30_mul_fused(c, d);
+#endif
+    ab = x;
+    cd = y;
+}
+// aa = a*a*2^-390, cc = c*c*2^-390 (each as fq30_sqr)
+TY_HD void fq30_sqr_pair(const Fq30& a, const Fq30& c, Fq30& aa, Fq30& cc) {
+    Fq30 x, y;
+#if defined(__HIP_DEVICE_COMPILE__)
+    fq30_sqr_pair_dev(a, c, x, y);
+#else
+    x = fq30_sqr_fused(a);
+    y = fq30_sqr_fused(c);
+#endif
+    aa = x;
+    cc = y;
+}
+
 // (a*b + c*d) * 2^-390 mod p; needs a*b + c*d < (2^390 - p) 2^390 (as fq30_mul); result < p + (a*b + c*d) / 2^390.
-// The digit sums are < 2^31 (T[25]: < 2^32 by the value bound), which fq30_redc takes as they are.
+// The digit sums are < 2^31 (T[25]: < 2^32 by the value bound), which fq30_redc takes as they are.  On the device the two
+// wide products are one pair of interleaved chains (fq30_pair.hpp); the digits are the same.
 TY_HD Fq30 fq30_mul2_add(const Fq30& a, const Fq30& b, const Fq30& c, const Fq30& d) {
-    uint32_t T[26], U[26];
+    uint32_t T[26];
+#if defined(__HIP_DEVICE_COMPILE__)
+    fq30_mul_wide_pair_dev(a, b, c, d, T);
+#else
+    uint32_t U[26];
     fq30_mul_wide(a, b, T);
     fq30_mul_wide(c, d, U);
 #pragma unroll
     for (int k = 0; k < 26; ++k) T[k] += U[k];
+#endif
     return fq30_redc(T);
 }
 

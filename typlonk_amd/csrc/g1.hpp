@@ -68,11 +68,11 @@ TY_HD Fq30 g1_y3(const Fq30& r, const Fq30& t, const Fq30& y, const Fq30& w) {
 TY_HD G1Xyzz g1_dbl_affine(const Fq30& x, const Fq30& y) {
     G1Xyzz r;
     const Fq30 u = fq30_mulk_lazy<2>(y);                               // < 2.2
-    const Fq30 v = fq30_sqr(u);                                        // m(2.2,2.2) < 1.01
+    Fq30 v, xx, w, s;
+    fq30_sqr_pair(u, x, v, xx);                                        // v: m(2.2,2.2) < 1.01, xx: m(1.1,1.1) < 1.01
     if (fq30_is_zero_mod(v)) return G1Xyzz::inf();                     // y = 0: order-2 point (none on G1)
-    const Fq30 w = fq30_mul(u, v);                                     // < 1.01
-    const Fq30 s = fq30_mul(x, v);                                     // < 1.01
-    const Fq30 m = fq30_mulk_lazy<3>(fq30_sqr(x));                     // 3 * 1.01 < 3.1
+    fq30_mul_pair(u, v, x, v, w, s);                                   // w, s < 1.01
+    const Fq30 m = fq30_mulk_lazy<3>(xx);                              // 3 * 1.01 < 3.1
     r.x = fq30_sub_lazy<3>(fq30_sqr(m), fq30_mulk_lazy<2>(s));         // m(3.1,3.1) + 3 < 4.1   (2s < 2.1 <= 3)
     const Fq30 t = fq30_sub_lazy<5>(s, r.x);                           // 1.01 + 5 < 6.1         (X3 < 4.1 <= 5)
     r.y = g1_y3(m, t, y, w);                                           // < 3.1   (split: m(3.1,6.1) + 2; merged: 1 + (3.1*6.1 + 4*1.01)/630)
@@ -86,16 +86,15 @@ TY_HD G1Xyzz g1_dbl(const G1Xyzz& p) {
     if (p.is_inf()) return G1Xyzz::inf();
     G1Xyzz r;
     const Fq30 u = fq30_mulk_lazy<2>(p.y);                             // < 6.4
-    const Fq30 v = fq30_sqr(u);                                        // m(6.4,6.4) < 1.07
+    Fq30 v, xx, w, s;
+    fq30_sqr_pair(u, p.x, v, xx);                                      // v: m(6.4,6.4) < 1.07, xx: m(5.1,5.1) < 1.05
     if (fq30_is_zero_mod(v)) return G1Xyzz::inf();
-    const Fq30 w = fq30_mul(u, v);                                     // m(6.4,1.07) < 1.02
-    const Fq30 s = fq30_mul(p.x, v);                                   // m(5.1,1.07) < 1.01
-    const Fq30 m = fq30_mulk_lazy<3>(fq30_sqr(p.x));                   // 3 * m(5.1,5.1) < 3.2
+    fq30_mul_pair(u, v, p.x, v, w, s);                                 // w: m(6.4,1.07) < 1.02, s: m(5.1,1.07) < 1.01
+    const Fq30 m = fq30_mulk_lazy<3>(xx);                              // 3 * 1.05 < 3.2
     r.x = fq30_sub_lazy<3>(fq30_sqr(m), fq30_mulk_lazy<2>(s));         // m(3.2,3.2) + 3 < 4.1
     const Fq30 t = fq30_sub_lazy<5>(s, r.x);                           // < 6.1
     r.y = g1_y3(m, t, p.y, w);                                         // < 3.1   (Y < 3.2 <= 4)
-    r.zz = fq30_mul(v, p.zz);                                          // < 1.01
-    r.zzz = fq30_mul(w, p.zzz);                                        // < 1.01
+    fq30_mul_pair(v, p.zz, w, p.zzz, r.zz, r.zzz);                     // < 1.01 each
     return r;
 }
 
@@ -109,27 +108,25 @@ TY_HD void g1_madd_xy(G1Xyzz& acc, const Fq30& qx, const Fq30& qy) {
         acc.zzz = fq30_one();
         return;
     }
-    const Fq30 u2 = fq30_mul(qx, acc.zz);                              // < 1.01
-    const Fq30 s2 = fq30_mul(qy, acc.zzz);                             // < 1.01
+    Fq30 u2, s2, pp, rr, ppp, q;
+    fq30_mul_pair(qx, acc.zz, qy, acc.zzz, u2, s2);                    // < 1.01 each
     const Fq30 p = fq30_sub_lazy<6>(u2, acc.x);                        // 1.01 + 6 < 7.1   (X1 < 5.1 <= 6)
     const Fq30 r = fq30_sub_lazy<4>(s2, acc.y);                        // 1.01 + 4 < 5.1   (Y1 < 3.2 <= 4)
-    const Fq30 pp = fq30_sqr(p);                                       // m(7.1,7.1) < 1.09
+    fq30_sqr_pair(p, r, pp, rr);                                       // pp: m(7.1,7.1) < 1.09, rr: m(5.1,5.1) < 1.05
     if (fq30_is_zero_mod(pp)) {                                        // P = 0  <=>  same x
-        if (fq30_is_zero_mod(fq30_sqr(r))) {                           // and same y: doubling
+        if (fq30_is_zero_mod(rr)) {                                    // and same y: doubling
             acc = g1_dbl_affine(qx, qy);
         } else {
             acc = G1Xyzz::inf();
         }
         return;
     }
-    const Fq30 ppp = fq30_mul(p, pp);                                  // m(7.1,1.09) < 1.02
-    const Fq30 q = fq30_mul(acc.x, pp);                                // m(5.1,1.09) < 1.01
-    const Fq30 x3 = fq30_sub2_lazy<4>(fq30_sqr(r), ppp, fq30_mulk_lazy<2>(q));  // m(5.1,5.1) + 4 < 5.1  (ppp + 2q < 3.1 <= 4)
+    fq30_mul_pair(p, pp, acc.x, pp, ppp, q);                           // ppp: m(7.1,1.09) < 1.02, q: m(5.1,1.09) < 1.01
+    const Fq30 x3 = fq30_sub2_lazy<4>(rr, ppp, fq30_mulk_lazy<2>(q));  // 1.05 + 4 < 5.1  (ppp + 2q < 3.1 <= 4)
     const Fq30 t = fq30_sub_lazy<6>(q, x3);                            // 1.01 + 6 < 7.1
     acc.y = g1_y3(r, t, acc.y, ppp);                                   // < 3.1   (split: m(5.1,7.1) + 2; merged: 1 + (5.1*7.1 + 4*1.02)/630 < 1.07)
     acc.x = x3;
-    acc.zz = fq30_mul(acc.zz, pp);                                     // < 1.01
-    acc.zzz = fq30_mul(acc.zzz, ppp);                                  // < 1.01
+    fq30_mul_pair(acc.zz, pp, acc.zzz, ppp, acc.zz, acc.zzz);          // < 1.01 each
 }
 
 // acc += (neg ? -q : q)
@@ -143,25 +140,23 @@ TY_HD void g1_madd(G1Xyzz& acc, const G1Affine& q, bool neg) {
 TY_HD G1Xyzz g1_add(const G1Xyzz& a, const G1Xyzz& b) {
     if (a.is_inf()) return b;
     if (b.is_inf()) return a;
-    const Fq30 u1 = fq30_mul(a.x, b.zz);                               // m(5.1,1.1) < 1.01
-    const Fq30 u2 = fq30_mul(b.x, a.zz);                               // < 1.01
-    const Fq30 s1 = fq30_mul(a.y, b.zzz);                              // < 1.01
-    const Fq30 s2 = fq30_mul(b.y, a.zzz);                              // < 1.01
+    Fq30 u1, u2, s1, s2, pp, rr, ppp, q, zz12, zzz12;
+    fq30_mul_pair(a.x, b.zz, b.x, a.zz, u1, u2);                       // m(5.1,1.1) < 1.01 each
+    fq30_mul_pair(a.y, b.zzz, b.y, a.zzz, s1, s2);                     // < 1.01 each
     const Fq30 p = fq30_sub_lazy<2>(u2, u1);                           // < 3.1
     const Fq30 r = fq30_sub_lazy<2>(s2, s1);                           // < 3.1
-    const Fq30 pp = fq30_sqr(p);                                       // < 1.02
+    fq30_sqr_pair(p, r, pp, rr);                                       // < 1.02 each
     if (fq30_is_zero_mod(pp)) {
-        if (fq30_is_zero_mod(fq30_sqr(r))) return g1_dbl(a);
+        if (fq30_is_zero_mod(rr)) return g1_dbl(a);
         return G1Xyzz::inf();
     }
-    const Fq30 ppp = fq30_mul(p, pp);                                  // < 1.01
-    const Fq30 q = fq30_mul(u1, pp);                                   // < 1.01
+    fq30_mul_pair(p, pp, u1, pp, ppp, q);                              // < 1.01 each
     G1Xyzz o;
-    o.x = fq30_sub2_lazy<4>(fq30_sqr(r), ppp, fq30_mulk_lazy<2>(q));   // m(3.1,3.1) + 4 < 5.1
+    o.x = fq30_sub2_lazy<4>(rr, ppp, fq30_mulk_lazy<2>(q));            // m(3.1,3.1) + 4 < 5.1
     const Fq30 t = fq30_sub_lazy<6>(q, o.x);                           // < 7.1
     o.y = g1_y3(r, t, s1, ppp);                                        // < 3.1   (s1 < 1.01 <= 4)
-    o.zz = fq30_mul(fq30_mul(a.zz, b.zz), pp);                         // < 1.01
-    o.zzz = fq30_mul(fq30_mul(a.zzz, b.zzz), ppp);                     // < 1.01
+    fq30_mul_pair(a.zz, b.zz, a.zzz, b.zzz, zz12, zzz12);              // < 1.01 each
+    fq30_mul_pair(zz12, pp, zzz12, ppp, o.zz, o.zzz);                  // < 1.01 each
     return o;
 }
 
