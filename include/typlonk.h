@@ -343,7 +343,8 @@ int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
                        const uint64_t* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out);
 /* ---- prove() for many witnesses of one circuit in one call, batched across proofs.
  * out[k] is bit for bit what typlonk_prove (typlonk_prove_host) returns for witness k -- commitments, evaluations, openings
- * and the four challenges; each proof keeps its own transcript.  Reference proof shape only (six openings).
+ * and the four challenges; each proof keeps its own transcript.  The reference proof shape (six openings); the compact
+ * shape has typlonk_prove_batch_compact below.
  *   wire_evals  count x 3 columns, proof-major (wire_evals[3 k + i] = column i of proof k), n = 2^log_n Fr each
  *   pi_evals    count entries, or NULL (every public-input column zero); an entry may be NULL (that proof's column is zero)
  *   status[k]   TYPLONK_OK, or TYPLONK_ERR_UNSATISFIED when r(zeta) != 0 for witness k: out[k] is filled exactly as
@@ -358,7 +359,7 @@ int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
  * HBM kept after a batch (grow-only, per proof in flight, n = 2^log_n rows; 32 B per Fr):
  *   prover_mem  39 n Fr per proof of a wave: the 19 n of typlonk_prove's arena + the 5 x 4n coset extensions
  *               (2^16: 64 x 80 MiB = 5.0 GiB; 2^20: 4 x 1.2 GiB = 4.9 GiB; 2^22: 4.9 GiB; 2^24: 19.5 GiB)
- *   ops_tmp     8 n / 2048 Fr per proof (the openings' carries); 16 pinned result slots per proof; ~200 KiB of tables */
+ *   ops_tmp     8 n / 2048 Fr per proof (the openings' carries); 16 pinned result slots per proof; ~230 KiB of tables */
 int typlonk_prove_batch(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
                         const typlonk_buf* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
                         int* status);
@@ -480,6 +481,38 @@ int typlonk_prove_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id
 int typlonk_prove_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
                                size_t rows, const uint64_t* pi, size_t pi_len, const uint64_t cosets[3][4],
                                typlonk_proof_compact* out);
+/* ---- typlonk_prove_compact for many witnesses of one circuit in one call, batched across proofs.
+ * out[k] is bit for bit what typlonk_prove_compact (typlonk_prove_compact_host) returns for witness k -- the 9 points, the 7
+ * evaluations and the five challenges.  Each proof has its own transcript, started from its own statement digest d0: the vk
+ * bytes are shared by the batch, pi_len[k] and the public values are proof k's.
+ *   wire_evals  count x 3 columns, proof-major, as for typlonk_prove_batch
+ *   pi          count entries, or NULL; entry k is a buffer of >= pi_len[k] values of which only the first pi_len[k] are read
+ *               (it may be NULL when pi_len[k] = 0).  The values of a whole wave are brought to the host behind one wait.
+ *   pi_len      count entries, or NULL (= all 0)
+ *   status[k]   TYPLONK_OK, or TYPLONK_ERR_UNSATISFIED when r(zeta) != 0 for witness k: out[k] is completely filled, as
+ *               typlonk_prove_compact fills it, and the other proofs are not affected
+ * The return value reports only bad arguments and device failures; count = 0 is a no-op.  TYPLONK_ERR_INVALID_ARG: a null
+ * argument, an unknown circuit or SRS, a null wire column, pi_len[k] != 0 with pi or pi[k] NULL, a sharded SRS or a context
+ * whose communicator would fold, a round-by-round prover open on the context.  TYPLONK_ERR_RANGE: a wire buffer shorter than n
+ * or a pi buffer shorter than pi_len[k].  TYPLONK_ERR_LENGTH: pi_len[k] > n, an SRS shorter than n.  TYPLONK_ERR_DOMAIN:
+ * log_n > TYPLONK_MAX_PROVER_LOG_N.  A refused call leaves `out` and the context as they were.
+ * The first call for a (circuit, SRS) pair computes the eight circuit commitments for d0 once, through the cache of
+ * typlonk_circuit_commitments -- not per proof or per wave.
+ * Waves as typlonk_prove_batch: G = min(count, 64, max(1, 2^22 >> log_n)) proofs, every stage batched across them, in the
+ * compact transcript's order: rounds 1 and 2 as there; then the quotient of every proof once every alpha is known and the 3G
+ * commitments [t_lo] [t_mid] [t_hi] in one queue, which the host waits for before it draws any zeta; the evaluations of the
+ * wave in one launch sequence and one wait; r and F of every proof from one fused kernel (a thread owns a coefficient and four
+ * proofs: the circuit's eight coefficient vectors are read once per group, r is not read back to form F); F's opening and
+ * r(zeta); the 2G commitments W_z, W_zw in one queue.  The host waits four times per wave plus one final read.
+ * HBM: typlonk_prove_batch's arena, unchanged (39 n Fr per proof of a wave; this shape leaves 3 n of it unused). */
+int typlonk_prove_batch_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
+                                const typlonk_buf* const* pi, const size_t* pi_len, size_t count, const uint64_t cosets[3][4],
+                                typlonk_proof_compact* out, int* status);
+/* The same with the columns in HOST memory: wire_evals[3 k + i] holds `rows` Fr elements, and rows must equal the circuit's n
+ * (else TYPLONK_ERR_LENGTH); pi[k] holds pi_len[k] values. */
+int typlonk_prove_batch_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
+                                     size_t rows, const uint64_t* const* pi, const size_t* pi_len, size_t count,
+                                     const uint64_t cosets[3][4], typlonk_proof_compact* out, int* status);
 /* `count` compact proofs against one verifying key: ok[k] = 1 iff proof k is accepted.  No SRS and no loaded circuit are
  * needed.  pi[k] / pi_len[k] as for typlonk_verify (pi_len[k] > n -> TYPLONK_ERR_LENGTH).  A vk point off the curve (or a
  * g2s off the twist, a log_n outside 1..24) returns TYPLONK_ERR_INVALID_ARG / TYPLONK_ERR_DOMAIN; a bad proof gets ok = 0;

@@ -13,7 +13,7 @@
 //!   * `Backend::load_circuit` + `Backend::prove`
 //!                               replace the body of `plonk::proof::prove`           plonk/src/proof.rs:96-194
 //!   * `Backend::verify_batch`   replaces `plonk::proof::verify` for a batch          plonk/src/proof.rs:195-281
-//!   * `Backend::prove_compact` / `verifying_key` / `verify_compact`
+//!   * `Backend::prove_compact` / `prove_batch_compact` / `verifying_key` / `verify_compact`
 //!                               the compact proof shape of include/typlonk.h (batched openings; no counterpart there)
 //!
 //! Data crosses the boundary in arkworks' own in-memory form (`Fp256.0 .0`: 4 LE u64 limbs of the Montgomery residue;
@@ -385,6 +385,35 @@ impl Backend {
                                             k.as_ptr(), out.as_mut_ptr())
         });
         unsafe { out.assume_init() }
+    }
+
+    /// `prove_compact` for many witnesses of one circuit in one call (`typlonk_prove_batch_compact_host`, batched across
+    /// proofs in waves): `wire_evals[k]` as for `prove_batch`, `public_inputs` empty or one list of public values per witness.
+    /// Returns each proof with its status: `TYPLONK_OK`, or `TYPLONK_ERR_UNSATISFIED` for a witness with r(zeta) != 0 (its
+    /// proof is filled all the same and will not verify) -- no panic for those.  Proof k equals `prove_compact` on witness
+    /// k and statement k, bit for bit.
+    pub fn prove_batch_compact(&self, srs: SrsHandle, circuit: CircuitHandle, wire_evals: &[[&[Fr]; 3]], public_inputs: &[&[Fr]],
+                               cosets: [Fr; 3]) -> Vec<(ffi::TyplonkProofCompact, i32)> {
+        assert!(public_inputs.is_empty() || public_inputs.len() == wire_evals.len(), "one public-input list per witness");
+        let count = wire_evals.len();
+        let rows = if count == 0 { 0 } else { wire_evals[0][0].len() };   // the library checks it against the circuit's n
+        assert!(wire_evals.iter().all(|cols| cols.iter().all(|c| c.len() == rows)), "columns of equal length");
+        let flat = |c: &[Fr]| -> Vec<u64> { c.iter().flat_map(|e| fr_limbs(e)).collect() };
+        let w: Vec<Vec<u64>> = wire_evals.iter().flat_map(|cols| cols.iter().map(|c| flat(c))).collect();
+        let wp: Vec<*const u64> = w.iter().map(|c| c.as_ptr()).collect();
+        let pi: Vec<Vec<u64>> = public_inputs.iter().map(|c| flat(c)).collect();
+        let pp: Vec<*const u64> = pi.iter().map(|c| if c.is_empty() { ptr::null() } else { c.as_ptr() }).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|c| c.len()).collect();
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut out: Vec<ffi::TyplonkProofCompact> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+        let mut status = vec![0i32; count];
+        self.check(unsafe {
+            ffi::typlonk_prove_batch_compact_host(self.ctx, srs.id, circuit.id, wp.as_ptr(), rows,
+                                                  if pp.is_empty() { ptr::null() } else { pp.as_ptr() },
+                                                  if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, count, k.as_ptr(),
+                                                  out.as_mut_ptr(), status.as_mut_ptr())
+        });
+        out.into_iter().zip(status).collect()
     }
 
     /// `typlonk_verify_compact`: a batch of compact proofs against a verifying key; needs no SRS and no circuit on this

@@ -32,6 +32,7 @@ SYMBOLS = [
     "typlonk_msm_g1_sharded_devptr", "typlonk_msm_g1_sharded_batch_devptr", "typlonk_g1_fold_records_host",
     "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify", "typlonk_prove_batch", "typlonk_prove_batch_host",
     "typlonk_circuit_vk", "typlonk_prove_compact", "typlonk_prove_compact_host", "typlonk_verify_compact", "typlonk_compact_challenges",
+    "typlonk_prove_batch_compact", "typlonk_prove_batch_compact_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 
@@ -276,6 +277,13 @@ def load_library() -> C.CDLL:
                                                C.POINTER(C.c_size_t), u8p]
         lib.typlonk_compact_challenges.argtypes = [C.POINTER(Vk), C.POINTER(ProofCompact), u64p, C.c_size_t,
                                                    C.POINTER(C.c_uint64 * 4)]
+    if hasattr(lib, "typlonk_prove_batch_compact") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_prove_batch_compact.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t),
+                                                    C.c_size_t, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(ProofCompact),
+                                                    C.POINTER(C.c_int)]
+        lib.typlonk_prove_batch_compact_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(u64p), C.c_size_t, C.POINTER(u64p),
+                                                         C.POINTER(C.c_size_t), C.c_size_t, C.POINTER((C.c_uint64 * 4) * 3),
+                                                         C.POINTER(ProofCompact), C.POINTER(C.c_int)]
     lib.typlonk_prover_free.argtypes = [vp]
     lib.typlonk_prover_free.restype = None
     lib.typlonk_circuit_load.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -908,6 +916,47 @@ class Context:
         st = (C.c_int * max(k, 1))()
         self._chk(fn(self.h, sid, circuit, w, pi, k, C.byref(ks), out, st))
         return [self._proof_dict(out[i]) for i in range(k)], [int(st[i]) for i in range(k)]
+
+    def prove_batch_compact(self, sid: int, circuit: int, wire_evals, pi=None, pi_len=None, cosets=None):
+        """typlonk_prove_batch_compact: wire_evals = one [a, b, c] list of DeviceBuffers per proof; pi = None or one entry per
+        proof (a DeviceBuffer of >= pi_len[k] public values, or None); pi_len = None (each buffer's length, 0 for None) or
+        one count per proof.  Returns (proofs, statuses): one compact_dict per proof as prove_compact returns it, and per
+        proof OK or ERR_UNSATISFIED (that proof's dict is filled all the same)."""
+        k = len(wire_evals)
+        w = (C.c_void_p * max(3 * k, 1))(*[b.handle.value for cols in wire_evals for b in cols])
+        pip = None
+        if pi is not None:
+            pip = (C.c_void_p * max(k, 1))(*[b.handle.value if b is not None else None for b in pi])
+        if pi_len is None and pi is not None:
+            pi_len = [b.n if b is not None else 0 for b in pi]
+        lens = (C.c_size_t * max(k, 1))(*[int(x) for x in pi_len]) if pi_len is not None else None
+        out = (ProofCompact * max(k, 1))()
+        st = (C.c_int * max(k, 1))()
+        self._chk(self.lib.typlonk_prove_batch_compact(self.h, sid, circuit, w, pip, lens, k, C.byref(_cosets_arg(cosets)), out, st))
+        return [compact_dict(out[i]) for i in range(k)], [int(st[i]) for i in range(k)]
+
+    def prove_batch_compact_host(self, sid: int, circuit: int, wire_evals_host, pi=None, cosets=None):
+        """typlonk_prove_batch_compact_host: the columns are (rows, 4) u64 host arrays of equal length, one [a, b, c] list per
+        proof; pi = None or one entry per proof (None or an (l, 4) column of l public values).  The row count is passed on and
+        checked against the circuit's n by the library.  Same result as prove_batch_compact."""
+        k = len(wire_evals_host)
+        keep = [np.ascontiguousarray(c, dtype=np.uint64) for cols in wire_evals_host for c in cols]
+        if any(c.ndim != 2 or c.shape[1] != 4 or c.shape != keep[0].shape for c in keep):
+            raise ValueError("prove_batch_compact_host needs (rows, 4) uint64 columns of equal length")
+        w = (C.POINTER(C.c_uint64) * max(3 * k, 1))(*[_u64p(c) for c in keep])
+        pip = lens = None
+        if pi is not None:
+            pis = [np.ascontiguousarray(c, dtype=np.uint64) if c is not None else None for c in pi]
+            if any(c is not None and (c.ndim != 2 or c.shape[1] != 4) for c in pis):
+                raise ValueError("pi entries must be (l, 4) uint64 columns")
+            keep += [c for c in pis if c is not None]
+            pip = (C.POINTER(C.c_uint64) * max(k, 1))(*[_u64p(c) if c is not None and c.shape[0] else None for c in pis])
+            lens = (C.c_size_t * max(k, 1))(*[c.shape[0] if c is not None else 0 for c in pis])
+        out = (ProofCompact * max(k, 1))()
+        st = (C.c_int * max(k, 1))()
+        self._chk(self.lib.typlonk_prove_batch_compact_host(self.h, sid, circuit, w, keep[0].shape[0] if keep else 0, pip, lens, k,
+                                                            C.byref(_cosets_arg(cosets)), out, st))
+        return [compact_dict(out[i]) for i in range(k)], [int(st[i]) for i in range(k)]
 
     def circuit_load(self, log_n: int, selectors, sigma) -> int:
         sel = (C.c_void_p * 5)(*[b.handle.value for b in selectors])

@@ -7,6 +7,12 @@
 // three times per wave -- after round 1's and round 2's commitments (the transcripts need them) and for round 3's
 // evaluations -- plus the final read, never once per proof.  Every proof keeps its own Fiat-Shamir transcript, and every
 // field operation is exact, so proof k is bit for bit what typlonk_prove returns for witness k.
+//
+// typlonk_prove_batch_compact runs the same waves in the compact shape (typlonk_prove_compact): rounds 1 and 2 are shared
+// (wave_rounds12, with the shape's transcript), round 3 goes in the compact transcript's order -- the 3G quotient commitments
+// before any zeta is drawn (a fourth host wait per wave), then the evaluations, then r and F of every proof from one fused
+// kernel (pb_fold_kernel) and the 2G opening commitments.
+#include "compact_transcript.hpp"
 #include "fr_inv.hpp"
 #include "host.hpp"
 #include "scan_ops.hpp"
@@ -23,6 +29,7 @@ constexpr uint32_t PB_MAX = 64;              // proofs per wave (the cap of typl
 constexpr uint64_t PB_ROWS = 1ull << 22;     // and at most this many rows of all proofs of a wave together
 constexpr uint32_t PB_ITEMS = 8;             // round 3's openings / evaluations per proof
 constexpr uint32_t PB_QGROUP = 4;            // proofs one thread of the quotient kernel evaluates per point
+constexpr uint32_t PB_FGROUP = 4;            // proofs one thread of the compact shape's fold kernel combines per coefficient
 constexpr uint32_t PB_SLOTS = 16;            // pinned result slots per proof
 // per-proof arena of a wave, in units of n Fr: ev[3] co[3] pi z t(4) q[6] r | ext a b c Z PI (5 x 4)
 constexpr uint64_t PB_EV = 0, PB_CO = 3, PB_PI = 6, PB_Z = 7, PB_T = 8, PB_Q = 12, PB_R = 18, PB_EXT = 19, PB_STRIDE = 39;
@@ -38,6 +45,10 @@ struct PbLin {         // round 3, linearisation
     Fr scalar[LIN_TERMS];
     Fr constant;
 };
+struct PbFold {        // round 3 of the compact shape: r's terms, then F = a + v b + ... with vpow[j] = v^(j + 1)
+    PbLin lin;
+    Fr vpow[6];
+};
 struct PbItem {        // one opening (q != null) or evaluation at zpow[zi]
     const Fr* c;
     Fr* q;
@@ -51,7 +62,8 @@ struct PbTables {
     PbQuot quot[PB_MAX];
     PbLin lin[PB_MAX];
     PbItem item[PB_MAX * PB_ITEMS];
-    PbItem ritem[PB_MAX];
+    PbItem ritem[2 * PB_MAX];   // r's opening; the compact shape: F's opening and r's evaluation
+    PbFold fold[PB_MAX];
     Fr zpow[2 * PB_MAX][32];   // zeta_p^(2^k) at 2p, (zeta_p w)^(2^k) at 2p + 1
 };
 
@@ -245,6 +257,52 @@ __global__ __launch_bounds__(256) void pb_lincomb_kernel(PbLinArgs a) {
     p_st(a.r + p * a.stride + i, acc);
 }
 
+// ---- round 3 of the compact shape: r and F = a + v b + v^2 c + v^3 Z + v^4 r + v^5 sigma_1 + v^6 sigma_2 in one pass ----------
+// One thread owns coefficient i and PB_FGROUP proofs: the circuit's eight coefficients at i are loaded once and serve every proof
+// of the group.  A single proof runs lincomb_kernel twice (17 n Fr read, r written and read back); here a proof reads its own
+// seven vectors and writes r and F.  Every value is a canonical residue of an exact field expression, so the order of the sums
+// does not show in the result.
+struct PbFoldArgs {
+    const Fr* coef;      // the circuit's coefficient copies (8 n): q_l q_r q_o q_m q_c sigma_0 sigma_1 sigma_2
+    const Fr* co;        // proof p's a, b, c: co + p * stride + k * n; its Z, t, r, F at z / t / r / f + p * stride
+    const Fr* z;
+    const Fr* t;
+    Fr* r;
+    Fr* f;
+    const PbFold* fold;
+    uint64_t n, stride;
+    uint32_t count;
+};
+__global__ __launch_bounds__(256) void pb_fold_kernel(PbFoldArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    Fr cc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cc[k] = p_ld(a.coef + k * a.n + i);
+    const uint32_t p0 = blockIdx.y * PB_FGROUP, p1 = min(a.count, p0 + PB_FGROUP);
+    for (uint32_t p = p0; p < p1; ++p) {
+        const PbFold& s = a.fold[p];
+        const uint64_t at = p * a.stride + i;
+        Fr r = (i == 0) ? s.lin.constant : Fr::zero();
+#pragma unroll
+        for (int k = 0; k < 5; ++k) r = fe_add(r, fe_mul(s.lin.scalar[k], cc[k]));
+        const Fr z = p_ld(a.z + at);
+        r = fe_add(r, fe_mul(s.lin.scalar[5], z));
+        r = fe_add(r, fe_mul(s.lin.scalar[6], cc[7]));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r = fe_add(r, fe_mul(s.lin.scalar[7 + k], p_ld(a.t + at + k * a.n)));
+        p_st(a.r + at, r);
+        Fr f = p_ld(a.co + at);
+        f = fe_add(f, fe_mul(s.vpow[0], p_ld(a.co + at + a.n)));
+        f = fe_add(f, fe_mul(s.vpow[1], p_ld(a.co + at + 2 * a.n)));
+        f = fe_add(f, fe_mul(s.vpow[2], z));
+        f = fe_add(f, fe_mul(s.vpow[3], r));
+        f = fe_add(f, fe_mul(s.vpow[4], cc[5]));
+        f = fe_add(f, fe_mul(s.vpow[5], cc[6]));
+        p_st(a.f + at, f);
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 const uint64_t* coset_g(Fr* g_out) {
     // the quotient's coset generator (prover.hip): Fr's multiplicative generator 7
@@ -260,10 +318,17 @@ struct ColumnsIn {   // the caller's columns: device buffers or host arrays, pro
     const typlonk_buf* const* pi_bufs;
     const uint64_t* const* wire_host;
     const uint64_t* const* pi_host;
+    const size_t* pi_len = nullptr;   // the compact shape: proof k's column is its first pi_len[k] rows, the rest zero
+    bool compact = false;
     const void* wire(size_t k, int i) const { return wire_bufs ? (const void*)wire_bufs[3 * k + i]->d : (const void*)wire_host[3 * k + i]; }
     const void* pi(size_t k) const {
         if (wire_bufs) return pi_bufs && pi_bufs[k] ? (const void*)pi_bufs[k]->d : nullptr;
         return pi_host ? (const void*)pi_host[k] : nullptr;
+    }
+    // rows of proof k's public-input column that are read (0: the zero polynomial)
+    uint64_t pi_rows(size_t k, uint64_t n) const {
+        if (compact) return pi_len ? pi_len[k] : 0;
+        return pi(k) ? n : 0;
     }
     hipMemcpyKind kind() const { return wire_bufs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
 };
@@ -279,6 +344,8 @@ struct Wave {
     PbTables* dev;
     Fr* slots;        // PB_SLOTS per proof
     Fr k[3];
+    bool has_pi[PB_MAX];   // of the running wave (wave_rounds12)
+    const typlonk_vk* vk = nullptr;   // the compact shape's statement (without [s]G2)
     Fr* at(uint32_t p, uint64_t off) const { return mem + ((uint64_t)p * PB_STRIDE + off) * n; }
 };
 
@@ -292,7 +359,47 @@ int upload(const Wave& w, const void* host_part, size_t bytes) {
     return hip_rc(w.ctx, hipMemcpyAsync((char*)w.dev + off, host_part, bytes, hipMemcpyHostToDevice, w.ctx->stream));
 }
 
-int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
+// The Fiat-Shamir script of a proof shape over rounds 1 and 2: after_round1 hashes [a] [b] [c] and fills beta, gamma;
+// after_round2 hashes [Z] and fills alpha (the reference shape draws zeta with it, the compact shape only in round 3).
+struct RefScript {
+    using Proof = typlonk_proof;
+    ChallengeGenerator g;
+    void after_round1(Proof& o) {                      // (beta, gamma) <- H([a], [b], [c])      proof.rs:111
+        uint64_t ch[8];
+        for (int i = 0; i < 3; ++i) g.digest(o.commit_xy[i], o.commit_inf[i]);
+        g.generate(2, ch);
+        memcpy(o.beta, ch, 32);
+        memcpy(o.gamma, ch + 4, 32);
+    }
+    void after_round2(Proof& o) {                      // (alpha, zeta) <- H([a], [b], [c], [Z])  proof.rs:133-136
+        uint64_t ch[8];
+        g.digest(o.z_xy, o.z_inf);
+        g.generate(2, ch);
+        memcpy(o.alpha, ch, 32);
+        memcpy(o.zeta, ch + 4, 32);
+    }
+};
+struct CompactScript {
+    using Proof = typlonk_proof_compact;
+    CompactTranscript tr;
+    explicit CompactScript(const uint8_t d0[64]) : tr(d0) {}
+    void after_round1(Proof& o) {
+        for (int i = 0; i < 3; ++i) tr.point(o.commit_xy[i], o.commit_inf[i]);
+        const Fr beta = tr.squeeze('b'), gamma = tr.squeeze('g');
+        memcpy(o.beta, beta.v, 32);
+        memcpy(o.gamma, gamma.v, 32);
+    }
+    void after_round2(Proof& o) {
+        tr.point(o.z_xy, o.z_inf);
+        const Fr alpha = tr.squeeze('a');
+        memcpy(o.alpha, alpha.v, 32);
+    }
+};
+
+// Rounds 1 and 2 of a wave in either shape: [a] [b] [c] and [Z] of every proof, beta / gamma / alpha in out[], the coset
+// extensions of a, b, c, Z (and PI) queued, and the quotient's per-proof table (w.host->quot) filled.
+template <class Script>
+int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typename Script::Proof* out, std::vector<Script>& tr) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = w.n, n4 = 4 * n;
@@ -300,8 +407,8 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     const uint64_t stride = PB_STRIDE * n;
     const uint64_t* g_limbs = coset_g(nullptr);
     int rc = TYPLONK_OK;
-    bool has_pi[PB_MAX];
-    for (uint32_t p = 0; p < G; ++p) has_pi[p] = in.pi(first + p) != nullptr;
+    bool* has_pi = w.has_pi;
+    for (uint32_t p = 0; p < G; ++p) has_pi[p] = in.pi_rows(first + p, n) != 0;
     auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
 
     // ---- round 1: columns into the arena, a, b, c (and PI) by one batched inverse transform, 3G commitments ----
@@ -314,7 +421,9 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
             co.push_back(w.at(p, PB_CO + i));
         }
         if (!rc && has_pi[p]) {
-            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_PI), in.pi(first + p), n * sizeof(Fr), in.kind(), s));
+            const uint64_t rows = in.pi_rows(first + p, n);   // (the compact shape reads pi_len rows; the rest are zero)
+            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_PI), in.pi(first + p), rows * sizeof(Fr), in.kind(), s));
+            if (!rc && rows < n) rc = hip_rc(ctx, hipMemsetAsync(w.at(p, PB_PI) + rows, 0, (n - rows) * sizeof(Fr), s));
             co.push_back(w.at(p, PB_PI));
         }
     }
@@ -340,15 +449,9 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
         if (!rc) rc = r;
     }
     if (rc) return rc;
-    // (beta, gamma) <- H([a], [b], [c]) of each proof                                        proof.rs:111
-    std::vector<ChallengeGenerator> tr(G);
-    uint64_t ch[8];
     for (uint32_t p = 0; p < G; ++p) {
-        typlonk_proof& o = out[first + p];
-        for (int i = 0; i < 3; ++i) tr[p].digest(o.commit_xy[i], o.commit_inf[i]);
-        tr[p].generate(2, ch);
-        memcpy(o.beta, ch, 32);
-        memcpy(o.gamma, ch + 4, 32);
+        auto& o = out[first + p];
+        tr[p].after_round1(o);
         PbGp& g = w.host->gp[p];
         memcpy(g.beta.v, o.beta, 32);
         memcpy(g.gamma.v, o.gamma, 32);
@@ -400,35 +503,96 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
         if (!rc) rc = r;
     }
     if (rc) return rc;
-    // (alpha, zeta) <- H([a], [b], [c], [Z])                                                    proof.rs:133-136
-    std::vector<Fr> zeta(G), alpha(G);
-    const Fr wn = fr_domain_root(log_n);
     for (uint32_t p = 0; p < G; ++p) {
-        typlonk_proof& o = out[first + p];
-        tr[p].digest(o.z_xy, o.z_inf);
-        tr[p].generate(2, ch);
-        memcpy(o.alpha, ch, 32);
-        memcpy(o.zeta, ch + 4, 32);
-        memcpy(alpha[p].v, o.alpha, 32);
-        memcpy(zeta[p].v, o.zeta, 32);
+        auto& o = out[first + p];
+        tr[p].after_round2(o);
         PbQuot& q = w.host->quot[p];
-        q.alpha = alpha[p];
-        q.alpha2 = fe_sqr(alpha[p]);
+        memcpy(q.alpha.v, o.alpha, 32);
+        q.alpha2 = fe_sqr(q.alpha);
         q.beta = w.host->gp[p].beta;
         q.gamma = w.host->gp[p].gamma;
         q.has_pi = has_pi[p];
-        Fr* zp0 = w.host->zpow[2 * p];
-        Fr* zp1 = w.host->zpow[2 * p + 1];
-        zp0[0] = zeta[p];
-        zp1[0] = fe_mul(zeta[p], wn);
-        for (int k = 1; k < 32; ++k) {
-            zp0[k] = fe_sqr(zp0[k - 1]);
-            zp1[k] = fe_sqr(zp1[k - 1]);
-        }
+    }
+    return TYPLONK_OK;
+}
+
+// zeta_p^(2^k) and (zeta_p w)^(2^k) of proof p into the staged table
+void stage_zpow(Wave& w, uint32_t p, const Fr& zeta) {
+    Fr* zp0 = w.host->zpow[2 * p];
+    Fr* zp1 = w.host->zpow[2 * p + 1];
+    zp0[0] = zeta;
+    zp1[0] = fe_mul(zeta, fr_domain_root(w.log_n));
+    for (int k = 1; k < 32; ++k) {
+        zp0[k] = fe_sqr(zp0[k - 1]);
+        zp1[k] = fe_sqr(zp1[k - 1]);
+    }
+}
+
+// The quotient of every proof of the wave (proof.rs:139-145): the staged table w.host->quot to the device, the pointwise kernel
+// and one batched inverse 4n transform; t_lo, t_mid, t_hi of proof p are then the first 3n coefficients at PB_T.
+int wave_quotient(Wave& w, uint32_t G) {
+    typlonk_ctx* ctx = w.ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = w.n, n4 = 4 * n;
+    const uint32_t log_n = w.log_n, log4 = log_n + 2;
+    int rc;
+    if ((rc = upload(w, w.host->quot, G * sizeof(PbQuot)))) return rc;
+    PbQuotArgs a{};
+    Fr g;
+    const uint64_t* g_limbs = coset_g(&g);
+    a.ext = w.at(0, PB_EXT);
+    a.cext = w.ce->ext;
+    a.t = w.at(0, PB_T);
+    a.pq = w.dev->quot;
+    a.n4 = n4;
+    a.stride = PB_STRIDE * n;
+    a.count = G;
+    Table lo, hi;
+    const Fr w4 = fr_domain_root(log4);
+    if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &a.w_h))) return rc;
+    a.w_lo = lo.d;
+    const uint64_t n_hi = 1ull << (log4 - a.w_h);
+    if ((rc = ensure(ctx, ctx->quot_tab, n_hi * sizeof(Fr)))) return rc;
+    launch_fr_scale(hi.d, n_hi, g, (Fr*)ctx->quot_tab.p, s);
+    a.gx_hi = (const Fr*)ctx->quot_tab.p;
+    // X^n - 1 on the coset: g^n iota^k - 1, iota = w_{4n}^n
+    Fr gn = g, iota = w4;
+    for (uint32_t i = 0; i < log_n; ++i) {
+        gn = fe_sqr(gn);
+        iota = fe_sqr(iota);
+    }
+    Fr cur = gn;
+    for (int k = 0; k < 4; ++k) {
+        a.zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
+        cur = fe_mul(cur, iota);
+    }
+    for (int k = 0; k < 3; ++k) a.k[k] = w.k[k];
+    a.k0_is_one = w.k[0] == Fr::one();
+    hipLaunchKernelGGL(pb_quotient_kernel, dim3((unsigned)((n4 + 255) / 256), (G + PB_QGROUP - 1) / PB_QGROUP), dim3(256), 0, s, a);
+    if ((rc = hip_rc(ctx, hipGetLastError()))) return rc;
+    std::vector<Fr*> ts(G);
+    for (uint32_t p = 0; p < G; ++p) ts[p] = w.at(p, PB_T);
+    return ntt_run_batch(ctx, ts.data(), G, log4, 1, g_limbs, /*sync=*/false);
+}
+
+int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
+    typlonk_ctx* ctx = w.ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = w.n, stride = PB_STRIDE * n;
+    const uint32_t log_n = w.log_n;
+    const bool* has_pi = w.has_pi;
+    auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
+    std::vector<RefScript> tr(G);
+    int rc = wave_rounds12(w, in, first, G, out, tr);
+    if (rc) return rc;
+    std::vector<Fr> zeta(G), alpha(G);
+    for (uint32_t p = 0; p < G; ++p) {
+        memcpy(alpha[p].v, out[first + p].alpha, 32);
+        memcpy(zeta[p].v, out[first + p].zeta, 32);
+        stage_zpow(w, p, zeta[p]);
     }
 
     // ---- round 3: openings (:147-163), quotient (:139-145), linearisation (:165-175), nine commitments per proof (:181) ----
-    const uint32_t nblk = (uint32_t)((n + 2047) / 2048);
     Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
     uint32_t nitems = 0;
     for (uint32_t p = 0; p < G; ++p) {
@@ -441,49 +605,11 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
         if (has_pi[p]) item(w.at(p, PB_PI), nullptr, 6, 0);
         item(w.at(p, PB_Z), w.at(p, PB_Q + 4), 8, 1);        // Z at zeta * w
     }
-    if ((rc = upload(w, w.host->quot, G * sizeof(PbQuot)))) return rc;
     if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
     if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
     pb_launch_open(w.dev->item, nitems, &w.dev->zpow[0][0], n, blocks, s);
     if ((rc = lasterr())) return rc;
-    {
-        PbQuotArgs a{};
-        Fr g;
-        coset_g(&g);
-        a.ext = w.at(0, PB_EXT);
-        a.cext = w.ce->ext;
-        a.t = w.at(0, PB_T);
-        a.pq = w.dev->quot;
-        a.n4 = n4;
-        a.stride = stride;
-        a.count = G;
-        Table lo, hi;
-        const Fr w4 = fr_domain_root(log4);
-        if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &a.w_h))) return rc;
-        a.w_lo = lo.d;
-        const uint64_t n_hi = 1ull << (log4 - a.w_h);
-        if ((rc = ensure(ctx, ctx->quot_tab, n_hi * sizeof(Fr)))) return rc;
-        launch_fr_scale(hi.d, n_hi, g, (Fr*)ctx->quot_tab.p, s);
-        a.gx_hi = (const Fr*)ctx->quot_tab.p;
-        // X^n - 1 on the coset: g^n iota^k - 1, iota = w_{4n}^n
-        Fr gn = g, iota = w4;
-        for (uint32_t i = 0; i < log_n; ++i) {
-            gn = fe_sqr(gn);
-            iota = fe_sqr(iota);
-        }
-        Fr cur = gn;
-        for (int k = 0; k < 4; ++k) {
-            a.zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
-            cur = fe_mul(cur, iota);
-        }
-        for (int k = 0; k < 3; ++k) a.k[k] = w.k[k];
-        a.k0_is_one = w.k[0] == Fr::one();
-        hipLaunchKernelGGL(pb_quotient_kernel, dim3((unsigned)((n4 + 255) / 256), (G + PB_QGROUP - 1) / PB_QGROUP), dim3(256), 0, s, a);
-        if ((rc = lasterr())) return rc;
-        std::vector<Fr*> ts(G);
-        for (uint32_t p = 0; p < G; ++p) ts[p] = w.at(p, PB_T);
-        if ((rc = ntt_run_batch(ctx, ts.data(), G, log4, 1, g_limbs, /*sync=*/false))) return rc;
-    }
+    if ((rc = wave_quotient(w, G))) return rc;
     // what the linearisation needs of zeta alone, while the kernels run; then ONE wait for every evaluation of the wave
     std::vector<Fr> zn(G), zh(G), l0z(G);
     for (uint32_t p = 0; p < G; ++p) lin_zeta_terms(zeta[p], log_n, &zn[p], &zh[p], &l0z[p]);
@@ -534,6 +660,135 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     return TYPLONK_OK;
 }
 
+// A wave in the compact shape (typlonk_prove_compact's order, prover.hip prover_round3_compact).  The host waits four times --
+// round 1's, round 2's and the quotient's commitments, round 3's evaluations -- plus the final read.
+int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof_compact* out, int* status) {
+    typlonk_ctx* ctx = w.ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = w.n, stride = PB_STRIDE * n;
+    const uint32_t log_n = w.log_n;
+    const bool* has_pi = w.has_pi;
+    auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
+    int rc;
+    // ---- the statements: d0 of every proof from the shared vk and its own public values; the device form brings the values
+    // of the whole wave to the host behind ONE synchronisation ----
+    std::vector<CompactScript> tr;
+    tr.reserve(G);
+    {
+        std::vector<std::vector<uint64_t>> fetched(in.wire_bufs ? G : 0);
+        bool any = false;
+        for (uint32_t p = 0; p < G && in.wire_bufs; ++p) {
+            const uint64_t rows = in.pi_rows(first + p, n);
+            if (!rows) continue;
+            fetched[p].resize(4 * rows);
+            HIPCHK(hipMemcpyAsync(fetched[p].data(), in.pi(first + p), rows * sizeof(Fr), hipMemcpyDeviceToHost, s));
+            any = true;
+        }
+        if (any) HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t p = 0; p < G; ++p) {
+            const uint64_t rows = in.pi_rows(first + p, n);
+            const uint64_t* vals = !rows ? nullptr : in.wire_bufs ? fetched[p].data() : (const uint64_t*)in.pi(first + p);
+            uint8_t d0[64];
+            compact_statement_digest(*w.vk, vals, rows, d0);
+            tr.emplace_back(d0);
+        }
+    }
+    if ((rc = wave_rounds12(w, in, first, G, out, tr))) return rc;
+
+    // ---- round 3: the quotient as soon as every alpha is known, its 3G commitments behind one fence; zeta binds them ----
+    if ((rc = wave_quotient(w, G))) return rc;
+    {
+        HIPCHK(hipEventRecord(ctx->batch_fence, s));
+        MsmQueue q(ctx, w.srs, /*first_lane=*/0);
+        q.fence = ctx->batch_fence;
+        const size_t m[3] = {n, n, n > 3 ? n - 3 : 0};
+        for (uint32_t p = 0; p < G && !rc; ++p)
+            for (int k = 0; k < 3 && !rc; ++k)
+                rc = q.submit(w.at(p, PB_T + k), m[k], out[first + p].t_xy[k], out[first + p].t_inf + k);
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    std::vector<Fr> zeta(G);
+    for (uint32_t p = 0; p < G; ++p) {
+        typlonk_proof_compact& o = out[first + p];
+        for (int i = 0; i < 3; ++i) tr[p].tr.point(o.t_xy[i], o.t_inf[i]);
+        zeta[p] = tr[p].tr.squeeze('z');
+        memcpy(o.zeta, zeta[p].v, 32);
+        stage_zpow(w, p, zeta[p]);
+    }
+    // ---- a, b, c, Z, sigma_1, sigma_2 (and PI) at zeta_p, Z at zeta_p w with its quotient: slots 0..6 are the proof's seven
+    // evaluations in order, 7 = PI(zeta); one wait for the whole wave ----
+    Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
+    uint32_t nitems = 0;
+    for (uint32_t p = 0; p < G; ++p) {
+        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        auto item = [&](const Fr* c, Fr* q, int slot, uint32_t zi) { w.host->item[nitems++] = PbItem{c, q, y + slot, 2ull * p + zi}; };
+        for (int i = 0; i < 3; ++i) item(w.at(p, PB_CO + i), nullptr, i, 0);
+        item(w.at(p, PB_Z), nullptr, 3, 0);
+        item(w.ce->coef + 5 * n, nullptr, 5, 0);             // sigma_1
+        item(w.ce->coef + 6 * n, nullptr, 6, 0);             // sigma_2
+        if (has_pi[p]) item(w.at(p, PB_PI), nullptr, 7, 0);
+        item(w.at(p, PB_Z), w.at(p, PB_Q + 4), 4, 1);        // Z at zeta * w
+    }
+    if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
+    if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
+    pb_launch_open(w.dev->item, nitems, &w.dev->zpow[0][0], n, blocks, s);
+    if ((rc = lasterr())) return rc;
+    std::vector<Fr> zn(G), zh(G), l0z(G);
+    for (uint32_t p = 0; p < G; ++p) lin_zeta_terms(zeta[p], log_n, &zn[p], &zh[p], &l0z[p]);   // while the kernels run
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t p = 0; p < G; ++p) {
+        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        typlonk_proof_compact& o = out[first + p];
+        for (int i = 0; i < 7; ++i) {
+            memcpy(o.evals[i], y[i].v, 32);
+            tr[p].tr.scalar(o.evals[i]);
+        }
+        const Fr v = tr[p].tr.squeeze('v');
+        memcpy(o.v, v.v, 32);
+        const Fr pi_z = has_pi[p] ? y[7] : Fr::zero();
+        Fr alpha;
+        memcpy(alpha.v, o.alpha, 32);
+        PbFold& f = w.host->fold[p];
+        lin_scalars(y, y[5], y[6], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha, zeta[p], zn[p], zh[p], l0z[p],
+                    f.lin.scalar, &f.lin.constant);
+        f.vpow[0] = v;
+        for (int j = 1; j < 6; ++j) f.vpow[j] = fe_mul(f.vpow[j - 1], v);
+        // F (in q[1]) opened at zeta with its witness into q[0]; r evaluated there for the status (q[0..3] are free in this shape)
+        w.host->ritem[2 * p] = PbItem{w.at(p, PB_Q + 1), w.at(p, PB_Q), y + 8, 2ull * p};
+        w.host->ritem[2 * p + 1] = PbItem{w.at(p, PB_R), nullptr, y + 9, 2ull * p};
+    }
+    if ((rc = upload(w, w.host->fold, G * sizeof(PbFold)))) return rc;
+    if ((rc = upload(w, w.host->ritem, 2 * G * sizeof(PbItem)))) return rc;
+    {
+        PbFoldArgs a{w.ce->coef, w.at(0, PB_CO), w.at(0, PB_Z), w.at(0, PB_T), w.at(0, PB_R), w.at(0, PB_Q + 1), w.dev->fold,
+                     n, stride, G};
+        hipLaunchKernelGGL(pb_fold_kernel, dim3((unsigned)((n + 255) / 256), (G + PB_FGROUP - 1) / PB_FGROUP), dim3(256), 0, s, a);
+        if ((rc = lasterr())) return rc;
+    }
+    pb_launch_open(w.dev->ritem, 2 * G, &w.dev->zpow[0][0], n, blocks, s);
+    if ((rc = lasterr())) return rc;
+    // ---- W_zeta and W_zeta_w of every proof in one queue ----
+    {
+        HIPCHK(hipEventRecord(ctx->batch_fence, s));
+        MsmQueue q(ctx, w.srs, /*first_lane=*/0);
+        q.fence = ctx->batch_fence;
+        for (uint32_t p = 0; p < G && !rc; ++p) {
+            typlonk_proof_compact& o = out[first + p];
+            rc = q.submit(w.at(p, PB_Q), n - 1, o.w_xy[0], o.w_inf + 0);
+            if (!rc) rc = q.submit(w.at(p, PB_Q + 4), n - 1, o.w_xy[1], o.w_inf + 1);
+        }
+        const int r = q.wait_all();
+        if (!rc) rc = r;
+    }
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t p = 0; p < G; ++p)   // r(zeta) != 0: the witness does not satisfy the circuit, as typlonk_prove_compact reports it
+        status[first + p] = w.slots[(uint64_t)p * PB_SLOTS + 9].is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
+    return TYPLONK_OK;
+}
+
 struct BusyGuard {
     typlonk_ctx* ctx;
     ~BusyGuard() {
@@ -542,29 +797,50 @@ struct BusyGuard {
     }
 };
 
-int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsIn& in, size_t count,
-                     const uint64_t cosets[3][4], typlonk_proof* out, int* status) {
+// rows: the compact host form's column length (must be n), SIZE_MAX where the form does not state one
+template <class Proof>
+int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsIn& in, size_t rows, size_t count,
+                     const uint64_t cosets[3][4], Proof* out, int* status) {
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     if (count == 0) return TYPLONK_OK;
     if (!cosets || !out || !status || !(in.wire_bufs || in.wire_host)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     auto ci = ctx->circuits.find(circuit_id);
     if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
     const uint32_t log_n = ci->second.log_n;
+    if (in.compact && log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "prover supports up to 2^24 rows");
     const uint64_t n = 1ull << log_n;
     for (size_t k = 0; k < 3 * count; ++k) {
         if (in.wire_bufs ? !in.wire_bufs[k] : !in.wire_host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
         if (in.wire_bufs && in.wire_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
     }
-    if (in.wire_bufs && in.pi_bufs)
+    if (in.compact) {
+        for (size_t k = 0; k < count; ++k) {
+            const uint64_t len = in.pi_rows(k, n);
+            if (!len) continue;
+            if (!in.pi(k)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "pi_len != 0 without public inputs");
+            if (in.wire_bufs && in.pi_bufs[k]->n < len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
+            if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
+        }
+    } else if (in.wire_bufs && in.pi_bufs) {
         for (size_t k = 0; k < count; ++k)
             if (in.pi_bufs[k] && in.pi_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "public-input column shorter than n");
+    }
     auto si = ctx->srs.find(srs_id);
     if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
     if (si->second.total_len || comm_folds(ctx, srs_id))
         return fail(ctx, TYPLONK_ERR_INVALID_ARG, "batched proving needs a whole SRS on one GPU, not a shard");
     if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
+    if (rows != SIZE_MAX && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
     HIPCHK(hipSetDevice(ctx->device));
+    typlonk_vk vk;
+    if (in.compact) {
+        // the statement's shared part: the circuit's commitments (one batch of eight MSMs the first time per circuit and SRS,
+        // then cached) and P0 -- once per call, not per proof or wave
+        memset((void*)out, 0, count * sizeof(Proof));
+        const int vrc = circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
+        if (vrc) return vrc;
+    }
     const uint32_t G = (uint32_t)std::min<uint64_t>({(uint64_t)count, PB_MAX, std::max<uint64_t>(1, PB_ROWS >> log_n)});
     // the wave's workspaces: the per-proof arenas, the openings' carries, the result slots, the tables
     int rc = ensure(ctx, ctx->prover_mem, (size_t)G * PB_STRIDE * n * sizeof(Fr));
@@ -594,6 +870,7 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
     w.host = (PbTables*)ctx->batch_host;
     w.dev = (PbTables*)ctx->batch_tab.p;
     w.slots = ctx->eval_slots_host;
+    w.vk = in.compact ? &vk : nullptr;
     for (int i = 0; i < 3; ++i) memcpy(w.k[i].v, cosets[i], 32);
     for (size_t first = 0; first < count && !rc; first += G) {
         const uint32_t g = (uint32_t)std::min<size_t>(G, count - first);
@@ -608,12 +885,27 @@ int typlonk_prove_batch(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, 
                         const typlonk_buf* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
                         int* status) {
     const ColumnsIn in{wire_evals, pi_evals, nullptr, nullptr};
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
 }
 
 int typlonk_prove_batch_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
                              const uint64_t* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
                              int* status) {
     const ColumnsIn in{nullptr, nullptr, wire_evals, pi_evals};
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
+}
+
+int typlonk_prove_batch_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
+                                const typlonk_buf* const* pi, const size_t* pi_len, size_t count, const uint64_t cosets[3][4],
+                                typlonk_proof_compact* out, int* status) {
+    const ColumnsIn in{wire_evals, pi, nullptr, nullptr, pi_len, true};
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
+}
+
+int typlonk_prove_batch_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
+                                     size_t rows, const uint64_t* const* pi, const size_t* pi_len, size_t count,
+                                     const uint64_t cosets[3][4], typlonk_proof_compact* out, int* status) {
+    const ColumnsIn in{nullptr, nullptr, wire_evals, pi, pi_len, true};
+    // (SIZE_MAX means "no row count stated" to prove_batch_impl: as a caller's row count it is refused like any other != n)
+    return prove_batch_impl(ctx, srs_id, circuit_id, in, rows == SIZE_MAX ? 0 : rows, count, cosets, out, status);
 }

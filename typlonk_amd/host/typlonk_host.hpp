@@ -754,6 +754,38 @@ class CompiledCircuit {
               c);
         return out;
     }
+    // prove_compact() for many witnesses in one call (typlonk_prove_batch_compact_host, batched across proofs in waves):
+    // advice[k] as for prove_batch(), public_inputs[k] = proof k's public values (the vector or an entry may be empty).
+    // proofs[k] equals prove_compact(advice[k], public_inputs[k]); status[k] is TYPLONK_OK or TYPLONK_ERR_UNSATISFIED (its
+    // proof is filled all the same and will not verify) -- no throw for those.
+    std::vector<typlonk_proof_compact> prove_batch_compact(const std::vector<std::array<std::vector<Fr>, 3>>& advice,
+                                                           const std::vector<std::vector<Fr>>& public_inputs,
+                                                           std::vector<int>* status) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        const size_t count = advice.size();
+        if (!public_inputs.empty() && public_inputs.size() != count) throw std::runtime_error("one public-input list per witness");
+        std::vector<const uint64_t*> wc(3 * count), pc(count, nullptr);
+        std::vector<size_t> lens(count, 0);
+        for (size_t k = 0; k < count; ++k) {
+            for (int i = 0; i < 3; ++i) {
+                if (advice[k][i].size() != n_) throw std::runtime_error("witness column must hold n values");
+                wc[3 * k + i] = advice[k][i][0].limbs();
+            }
+            if (!public_inputs.empty() && !public_inputs[k].empty()) {
+                pc[k] = public_inputs[k][0].limbs();
+                lens[k] = public_inputs[k].size();
+            }
+        }
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        std::vector<typlonk_proof_compact> out(count);
+        std::vector<int> st(count, TYPLONK_OK);
+        check(typlonk_prove_batch_compact_host(c, srs_.id(), circuit_, wc.data(), n_, pc.data(), lens.data(), count, ks, out.data(),
+                                               st.data()),
+              c);
+        if (status) *status = st;
+        return out;
+    }
 
    private:
     void g2s_limbs(uint64_t g2s[24]) const {
