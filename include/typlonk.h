@@ -525,6 +525,81 @@ int typlonk_verify_compact(typlonk_ctx* ctx, const typlonk_vk* vk, const typlonk
 int typlonk_compact_challenges(const typlonk_vk* vk, const typlonk_proof_compact* proof, const uint64_t* pi, size_t pi_len,
                                uint64_t out[5][4]);
 
+/* ---- wire format: compact proofs, verifying keys and SRS points as bytes, with compressed points ------------------------
+ * Everything above works on in-memory arkworks limbs that the caller is trusted to have formed.  The byte forms below are
+ * what leaves the process -- and what comes in from a peer that is NOT trusted: every decoded point is checked to lie on
+ * the curve AND in the subgroup of order r.  Nothing that is hashed changes: the transcripts, d0, rho and vk_bytes above keep
+ * their 96-byte uncompressed points.
+ *   G1 point   48 bytes, the ZCash / IETF BLS12-381 compressed form: x as a big-endian canonical integer, with the three top
+ *              bits of byte 0 used as flags:  bit 7 = compressed, always set;  bit 6 = infinity, and then every other bit of
+ *              the 48 bytes is 0 (c0 00 .. 00);  bit 5 = y > (p - 1) / 2.  80 00 .. 00 is the order-3 point (0, 2), not infinity.
+ *   G2 point   96 bytes, the same convention over Fq2: x.c1 then x.c0, big-endian; flags on byte 0; the sign bit is set iff
+ *              y.c1 > (p - 1) / 2, or y.c1 = 0 and y.c0 > (p - 1) / 2.
+ *   Fr         32 bytes, little-endian canonical integer (the encoding the compact transcript hashes).
+ *   proof      TYPLONK_PROOF_COMPACT_BYTES = 656: [a] [b] [c] [Z] [t_lo] [t_mid] [t_hi] [W_z] [W_zw] (fields 0..8, 48 bytes each)
+ *              then a(z) b(z) c(z) Z(z) Z(z w) sigma_1(z) sigma_2(z) (fields 9..15, 32 bytes each).  No challenges.
+ *   key        TYPLONK_VK_WIRE_BYTES = 628 ("vk wire form"; NOT the transcript's vk_bytes): u32 log_n little-endian, k_0 k_1 k_2
+ *              (Fr), [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3] P0 (48 bytes each), [s]G2 (96 bytes).
+ * Accepted encodings are unique.  A point is rejected with the FIRST class that applies, in this order:
+ *   TYPLONK_POINT_ENCODING         the compression bit clear, or the infinity bit with any other bit set
+ *   TYPLONK_POINT_X_RANGE          x >= p (for G2: either coordinate of x)
+ *   TYPLONK_POINT_NOT_ON_CURVE     x^3 + 4 is not a square (G2: x^3 + 4 (1 + u) over Fq2)
+ *   TYPLONK_POINT_NOT_IN_SUBGROUP  [r] P != O; skipped -- this check only -- with TYPLONK_DECODE_SKIP_SUBGROUP
+ * and a scalar >= r with TYPLONK_SCALAR_RANGE.  (The curve has points of order 3, 11, ... outside the subgroup; e.g. every
+ * curve point with x in {0, 4, 5, 6, 8}.) */
+#define TYPLONK_POINT_ENCODING 1
+#define TYPLONK_POINT_X_RANGE 2
+#define TYPLONK_POINT_NOT_ON_CURVE 3
+#define TYPLONK_POINT_NOT_IN_SUBGROUP 4
+#define TYPLONK_SCALAR_RANGE 5
+#define TYPLONK_DECODE_SKIP_SUBGROUP 1u
+#define TYPLONK_G1_BYTES 48
+#define TYPLONK_G2_BYTES 96
+#define TYPLONK_PROOF_COMPACT_BYTES 656
+#define TYPLONK_VK_WIRE_BYTES 628
+/* a decode status of a proof: 0, or the class of the first bad field (in wire order) and that field's index */
+#define TYPLONK_DECODE_STATUS(cls, field) ((uint32_t)(cls) | ((uint32_t)(field) << 8))
+#define TYPLONK_DECODE_CLASS(status) ((status) & 0xffu)
+#define TYPLONK_DECODE_FIELD(status) ((status) >> 8)
+/* Host-only.  xy: count*12 limbs, inf: count flags or NULL, out: count*48 bytes.  Coordinates that are not canonical
+ * residues return TYPLONK_ERR_INVALID_ARG (the curve equation is not checked here); `out` is then left as it was. */
+int typlonk_g1_compress(const uint64_t* xy, const uint8_t* inf, size_t count, uint8_t* out);
+/* bytes: count*48 -> xy: count*12 limbs, inf: count flags, status: count classes (0 = decoded; may be NULL).  A rejected
+ * slot gets the C-ABI identity (x = 0, y = 1, inf = 1).  With a context the points are decoded by one kernel launch, a
+ * thread per point; ctx = NULL runs the same code on the host.  Word for word the same output either way.  A rejected
+ * point is not an error of the call. */
+int typlonk_g1_decompress(typlonk_ctx* ctx, const uint8_t* bytes, size_t count, uint32_t flags, uint64_t* xy, uint8_t* inf,
+                          uint8_t* status);
+/* typlonk_srs_load from len = 48 * points bytes (a ceremony file's points): 48 bytes per point cross PCIe and the kernel
+ * writes the SRS's device records directly.  If any point is rejected NO SRS is created: the call returns
+ * TYPLONK_ERR_INVALID_ARG, *first_bad (may be NULL) is the lowest rejected index and typlonk_last_error names its class.
+ * len not a multiple of 48 returns TYPLONK_ERR_LENGTH. */
+int typlonk_srs_load_compressed(typlonk_ctx* ctx, const uint8_t* bytes, size_t len, uint32_t flags, uint32_t* srs_id,
+                                size_t* first_bad);
+/* typlonk_srs_download as count*48 bytes, compressed on the device. */
+int typlonk_srs_download_compressed(typlonk_ctx* ctx, uint32_t srs_id, size_t offset, size_t count, uint8_t* out);
+/* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
+ * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
+int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);
+int typlonk_vk_to_bytes(const typlonk_vk* vk, uint8_t out[TYPLONK_VK_WIRE_BYTES]);
+/* Host-only (a verifier needs nothing else).  The nine G1 points go through the decoder above; [s]G2 by a square root in
+ * Fq2, checked on the twist and -- unless skipped -- for [r] Q = O.  log_n outside 1..24 returns TYPLONK_ERR_DOMAIN; any
+ * rejected field TYPLONK_ERR_INVALID_ARG with its decode status in *status (may be NULL; fields: 0..2 the cosets, 3..11
+ * the G1 points, 12 [s]G2).  An infinite [s]G2 is TYPLONK_POINT_ENCODING. */
+int typlonk_vk_from_bytes(const uint8_t bytes[TYPLONK_VK_WIRE_BYTES], uint32_t flags, typlonk_vk* vk, uint32_t* status);
+/* bytes: count * 656.  All 9 * count points are decoded by ONE kernel launch (ctx = NULL: on the host), the scalars on the
+ * host.  status[k] = 0: proofs[k] is decoded, its five challenge fields zero (the verifier recomputes them); otherwise
+ * TYPLONK_DECODE_STATUS(class, field) of the first bad field and proofs[k] is all identities / zeros.  A rejected proof is
+ * not an error of the call; count = 0 is a no-op. */
+int typlonk_proof_compact_from_bytes(typlonk_ctx* ctx, const uint8_t* bytes, size_t count, uint32_t flags,
+                                     typlonk_proof_compact* proofs, uint32_t* status);
+/* typlonk_verify_compact over the wire form: ok[k] = 0 for a proof that does not decode; the others are handed to
+ * typlonk_verify_compact together, and ok[k] is its verdict.  pi / pi_len as there, indexed by k.  The key and every pi entry
+ * are judged before anything is decoded, by the checks of typlonk_verify_compact itself and with its error codes: a refusal
+ * does not depend on which proofs decode. */
+int typlonk_verify_compact_bytes(typlonk_ctx* ctx, const typlonk_vk* vk, const uint8_t* bytes, size_t count,
+                                 const uint64_t* const* pi, const size_t* pi_len, uint32_t flags, uint8_t* ok);
+
 /* ---- device-resident Fr vectors (so an iNTT result feeds an MSM without crossing PCIe) ---------- */
 int typlonk_buf_alloc(typlonk_ctx* ctx, size_t n_elems, typlonk_buf** out);
 int typlonk_buf_free(typlonk_ctx* ctx, typlonk_buf* buf);

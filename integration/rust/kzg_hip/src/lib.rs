@@ -15,6 +15,9 @@
 //!   * `Backend::verify_batch`   replaces `plonk::proof::verify` for a batch          plonk/src/proof.rs:195-281
 //!   * `Backend::prove_compact` / `prove_batch_compact` / `verifying_key` / `verify_compact`
 //!                               the compact proof shape of include/typlonk.h (batched openings; no counterpart there)
+//!   * `proof_to_bytes` / `vk_to_bytes` / `vk_from_bytes` / `Backend::proofs_from_bytes` / `verify_compact_bytes` /
+//!     `upload_srs_compressed` / `download_srs_compressed`
+//!                               the wire format of include/typlonk.h: compressed points, subgroup-checked on the way in
 //!
 //! Data crosses the boundary in arkworks' own in-memory form (`Fp256.0 .0`: 4 LE u64 limbs of the Montgomery residue;
 //! `Fp384.0 .0`: 6), so nothing is converted -- coordinates are copied limb-wise because `GroupAffine` is `repr(Rust)`.
@@ -31,6 +34,41 @@ pub type G1Point = G1Affine;
 pub type Poly = DensePolynomial<Fr>;
 /// `TYPLONK_VERIFY_PI_AS_PROVER` of include/typlonk.h (a flag of `typlonk_verify`)
 pub const VERIFY_PI_AS_PROVER: u32 = 1;
+/// `TYPLONK_DECODE_SKIP_SUBGROUP` of include/typlonk.h (a flag of the `*_from_bytes` / `*_compressed` calls)
+pub const DECODE_SKIP_SUBGROUP: u32 = 1;
+
+/// Why a byte string was refused: the reject class (`TYPLONK_POINT_*` / `TYPLONK_SCALAR_RANGE`) of the first bad field and
+/// that field's index in wire order (`TYPLONK_DECODE_CLASS` / `TYPLONK_DECODE_FIELD` of a decode status).
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct DecodeError {
+    pub class: u32,
+    pub field: u32,
+}
+impl DecodeError {
+    fn from_status(status: u32) -> Option<DecodeError> {
+        if status == 0 { None } else { Some(DecodeError { class: status & 0xff, field: status >> 8 }) }
+    }
+}
+
+/// `typlonk_proof_compact_to_bytes` (host-only): the 656-byte wire form.  `None` for a field that is not canonical or a
+/// point that is not on the curve.
+pub fn proof_to_bytes(proof: &ffi::TyplonkProofCompact) -> Option<[u8; ffi::TYPLONK_PROOF_COMPACT_BYTES]> {
+    let mut out = [0u8; ffi::TYPLONK_PROOF_COMPACT_BYTES];
+    if unsafe { ffi::typlonk_proof_compact_to_bytes(proof, out.as_mut_ptr()) } == ffi::TYPLONK_OK { Some(out) } else { None }
+}
+/// `typlonk_vk_to_bytes` (host-only): the 628-byte wire form of a verifying key.
+pub fn vk_to_bytes(vk: &ffi::TyplonkVk) -> Option<[u8; ffi::TYPLONK_VK_WIRE_BYTES]> {
+    let mut out = [0u8; ffi::TYPLONK_VK_WIRE_BYTES];
+    if unsafe { ffi::typlonk_vk_to_bytes(vk, out.as_mut_ptr()) } == ffi::TYPLONK_OK { Some(out) } else { None }
+}
+/// `typlonk_vk_from_bytes` (host-only; a verifier needs nothing else): every point on the curve and in the subgroup.
+/// `Err((code, status))`: the library's error code and, for a rejected field, what was wrong with it.
+pub fn vk_from_bytes(bytes: &[u8; ffi::TYPLONK_VK_WIRE_BYTES], flags: u32) -> Result<ffi::TyplonkVk, (c_int, Option<DecodeError>)> {
+    let mut vk = std::mem::MaybeUninit::<ffi::TyplonkVk>::zeroed();
+    let mut status = 0u32;
+    let rc = unsafe { ffi::typlonk_vk_from_bytes(bytes.as_ptr(), flags, vk.as_mut_ptr(), &mut status) };
+    if rc == ffi::TYPLONK_OK { Ok(unsafe { vk.assume_init() }) } else { Err((rc, DecodeError::from_status(status))) }
+}
 
 /// One HIP device + stream + workspaces (`typlonk_ctx`).  It holds a raw pointer, so it is neither `Send` nor `Sync`
 /// -- and therefore neither is anything that embeds it (`kzg::srs::Srs`, `plonk::CompiledCircuit` after the patches):
@@ -430,6 +468,59 @@ impl Backend {
                                         if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, ok.as_mut_ptr())
         });
         ok[..proofs.len()].iter().map(|&b| b != 0).collect()
+    }
+
+    // ---- the wire format (include/typlonk.h): compressed points, decoded and subgroup-checked on the device --------------
+    /// `typlonk_srs_load_compressed`: a ceremony file's G1 powers, 48 bytes per point.  `Err(i)`: point i (the lowest such)
+    /// was rejected and no SRS was created.  Panics on any other failure.
+    pub fn upload_srs_compressed(&self, bytes: &[u8], flags: u32, tables: bool) -> Result<SrsHandle, usize> {
+        let mut id = 0u32;
+        let mut first_bad = usize::MAX;
+        let rc = unsafe { ffi::typlonk_srs_load_compressed(self.ctx, bytes.as_ptr(), bytes.len(), flags, &mut id, &mut first_bad) };
+        if rc == ffi::TYPLONK_ERR_INVALID_ARG && first_bad != usize::MAX {
+            return Err(first_bad);
+        }
+        self.check(rc);
+        let h = SrsHandle { id, len: bytes.len() / ffi::TYPLONK_G1_BYTES };
+        if tables {
+            self.precompute_tables(h);
+        }
+        Ok(h)
+    }
+    /// `typlonk_srs_download_compressed`: the whole SRS as 48 bytes per point, compressed on the device
+    pub fn download_srs_compressed(&self, srs: SrsHandle) -> Vec<u8> {
+        let mut out = vec![0u8; srs.len * ffi::TYPLONK_G1_BYTES];
+        self.check(unsafe { ffi::typlonk_srs_download_compressed(self.ctx, srs.id, 0, srs.len, out.as_mut_ptr()) });
+        out
+    }
+    /// `typlonk_proof_compact_from_bytes`: `bytes` = count x 656; every point through one kernel launch.  Entry k is the
+    /// proof (its challenge fields zero) or why it was refused.
+    pub fn proofs_from_bytes(&self, bytes: &[u8], flags: u32) -> Vec<Result<ffi::TyplonkProofCompact, DecodeError>> {
+        assert!(bytes.len() % ffi::TYPLONK_PROOF_COMPACT_BYTES == 0, "proofs are 656 bytes each");
+        let count = bytes.len() / ffi::TYPLONK_PROOF_COMPACT_BYTES;
+        let mut out: Vec<ffi::TyplonkProofCompact> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+        let mut status = vec![0u32; count];
+        self.check(unsafe {
+            ffi::typlonk_proof_compact_from_bytes(self.ctx, bytes.as_ptr(), count, flags, out.as_mut_ptr(), status.as_mut_ptr())
+        });
+        out.into_iter().zip(status).map(|(p, st)| match DecodeError::from_status(st) { None => Ok(p), Some(e) => Err(e) }).collect()
+    }
+    /// `typlonk_verify_compact_bytes`: `verify_compact` over the wire form.  A proof that does not decode is `false` and
+    /// never reaches the verifier.
+    pub fn verify_compact_bytes(&self, vk: &ffi::TyplonkVk, bytes: &[u8], public_inputs: &[Vec<Fr>], flags: u32) -> Vec<bool> {
+        assert!(bytes.len() % ffi::TYPLONK_PROOF_COMPACT_BYTES == 0, "proofs are 656 bytes each");
+        let count = bytes.len() / ffi::TYPLONK_PROOF_COMPACT_BYTES;
+        assert!(public_inputs.is_empty() || public_inputs.len() == count, "one public-input list per proof");
+        let cols: Vec<Vec<u64>> = public_inputs.iter().map(|c| c.iter().flat_map(|e| fr_limbs(e)).collect()).collect();
+        let pis: Vec<*const u64> = cols.iter().map(|c| if c.is_empty() { ptr::null() } else { c.as_ptr() }).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|c| c.len()).collect();
+        let mut ok = vec![0u8; count.max(1)];
+        self.check(unsafe {
+            ffi::typlonk_verify_compact_bytes(self.ctx, vk, bytes.as_ptr(), count,
+                                              if pis.is_empty() { ptr::null() } else { pis.as_ptr() },
+                                              if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, flags, ok.as_mut_ptr())
+        });
+        ok[..count].iter().map(|&b| b != 0).collect()
     }
 
     // ---- multi-GPU: one process per GPU, RCCL inside the library --------------------------------------------------

@@ -33,8 +33,20 @@ SYMBOLS = [
     "typlonk_poly_eval_dev", "typlonk_circuit_commitments", "typlonk_verify", "typlonk_prove_batch", "typlonk_prove_batch_host",
     "typlonk_circuit_vk", "typlonk_prove_compact", "typlonk_prove_compact_host", "typlonk_verify_compact", "typlonk_compact_challenges",
     "typlonk_prove_batch_compact", "typlonk_prove_batch_compact_host",
+    "typlonk_g1_compress", "typlonk_g1_decompress", "typlonk_srs_load_compressed", "typlonk_srs_download_compressed",
+    "typlonk_proof_compact_to_bytes", "typlonk_vk_to_bytes", "typlonk_vk_from_bytes", "typlonk_proof_compact_from_bytes",
+    "typlonk_verify_compact_bytes",
 ]
 VERIFY_PI_AS_PROVER = 1
+# the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
+POINT_ENCODING, POINT_X_RANGE, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP, SCALAR_RANGE = 1, 2, 3, 4, 5
+DECODE_SKIP_SUBGROUP = 1
+G1_BYTES, G2_BYTES, PROOF_COMPACT_BYTES, VK_WIRE_BYTES = 48, 96, 656, 628
+
+
+def decode_status(status: int) -> tuple[int, int]:
+    """a decode status -> (reject class, index of the first bad field)"""
+    return status & 0xff, status >> 8
 
 
 class TyplonkError(RuntimeError):
@@ -304,6 +316,18 @@ def load_library() -> C.CDLL:
                                      C.POINTER(C.c_uint64)]
     lib.typlonk_selftest_fq_inv.argtypes = [vp, C.c_uint64, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.typlonk_version.restype = C.c_char_p
+    if hasattr(lib, "typlonk_g1_decompress") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_g1_compress.argtypes = [u64p, u8p, C.c_size_t, u8p]
+        lib.typlonk_g1_decompress.argtypes = [vp, u8p, C.c_size_t, C.c_uint32, u64p, u8p, u8p]
+        lib.typlonk_srs_load_compressed.argtypes = [vp, u8p, C.c_size_t, C.c_uint32, u32p, C.POINTER(C.c_size_t)]
+        lib.typlonk_srs_download_compressed.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_size_t, u8p]
+        lib.typlonk_proof_compact_to_bytes.argtypes = [C.POINTER(ProofCompact), u8p]
+        lib.typlonk_vk_to_bytes.argtypes = [C.POINTER(Vk), u8p]
+        lib.typlonk_vk_from_bytes.argtypes = [u8p, C.c_uint32, C.POINTER(Vk), u32p]
+        lib.typlonk_proof_compact_from_bytes.argtypes = [vp, u8p, C.c_size_t, C.c_uint32, C.POINTER(ProofCompact), u32p]
+        lib.typlonk_verify_compact_bytes.argtypes = [vp, C.POINTER(Vk), u8p, C.c_size_t, C.POINTER(u64p), C.POINTER(C.c_size_t),
+                                                     C.c_uint32, u8p]
     _lib = lib
     return lib
 
@@ -365,6 +389,102 @@ def g1_sum_host(xy, inf=None):
     if rc:
         raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
     return out, int(oinf[0])
+
+
+def _bytes_arg(data, unit: int, what: str) -> np.ndarray:
+    """bytes / a uint8 array whose length is a multiple of `unit` -> a contiguous uint8 array"""
+    a = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if a.size % unit:
+        raise ValueError(f"{what}: {a.size} bytes is not a multiple of {unit}")
+    return a
+
+
+def _host_err(lib, rc: int):
+    if rc:
+        raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
+
+
+def g1_compress(xy, inf=None) -> bytes:
+    """typlonk_g1_compress (host-only): (count, 12) limbs + optional flags -> count * 48 bytes"""
+    lib = load_library()
+    xy = _as_u64(xy, 12)
+    n = xy.shape[0]
+    infp = None
+    if inf is not None:
+        inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+        if inf.size != n:
+            raise ValueError("g1_compress: one infinity flag per point")
+        infp = _u8p(inf)
+    out = np.zeros(max(n, 1) * G1_BYTES, dtype=np.uint8)
+    _host_err(lib, lib.typlonk_g1_compress(_u64p(xy), infp, n, _u8p(out)))
+    return out[:n * G1_BYTES].tobytes()
+
+
+def g1_decompress(data, skip_subgroup: bool = False, ctx: "Context | None" = None):
+    """typlonk_g1_decompress: count * 48 bytes -> (xy (count, 12), inf (count,), status (count,)).  ctx = None: on the host."""
+    lib = load_library()
+    a = _bytes_arg(data, G1_BYTES, "g1_decompress")
+    n = a.size // G1_BYTES
+    xy = np.zeros((max(n, 1), 12), dtype=np.uint64)
+    inf = np.zeros(max(n, 1), dtype=np.uint8)
+    st = np.zeros(max(n, 1), dtype=np.uint8)
+    rc = lib.typlonk_g1_decompress(ctx.h if ctx is not None else None, _u8p(a) if n else None, n,
+                                   DECODE_SKIP_SUBGROUP if skip_subgroup else 0, _u64p(xy), _u8p(inf), _u8p(st))
+    if ctx is not None:
+        ctx._chk(rc)
+    _host_err(lib, rc)
+    return xy[:n], inf[:n], st[:n]
+
+
+def proof_to_bytes(proof) -> bytes:
+    """typlonk_proof_compact_to_bytes (host-only): a compact dict or struct -> 656 bytes"""
+    lib = load_library()
+    pr = compact_struct(proof)
+    out = np.zeros(PROOF_COMPACT_BYTES, dtype=np.uint8)
+    _host_err(lib, lib.typlonk_proof_compact_to_bytes(C.byref(pr), _u8p(out)))
+    return out.tobytes()
+
+
+def proofs_from_bytes(data, skip_subgroup: bool = False, ctx: "Context | None" = None):
+    """typlonk_proof_compact_from_bytes: count * 656 bytes -> ([compact dict] * count, status (count,) uint32); a proof with a
+    non-zero status (decode_status) is all identities.  ctx = None decodes on the host, a context on the device."""
+    lib = load_library()
+    a = _bytes_arg(data, PROOF_COMPACT_BYTES, "proofs_from_bytes")
+    k = a.size // PROOF_COMPACT_BYTES
+    arr = (ProofCompact * max(k, 1))()
+    st = np.zeros(max(k, 1), dtype=np.uint32)
+    rc = lib.typlonk_proof_compact_from_bytes(ctx.h if ctx is not None else None, _u8p(a) if k else None, k,
+                                              DECODE_SKIP_SUBGROUP if skip_subgroup else 0, arr,
+                                              st.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if ctx is not None:
+        ctx._chk(rc)
+    _host_err(lib, rc)
+    return [compact_dict(arr[i]) for i in range(k)], st[:k]
+
+
+def vk_to_bytes(vk: Vk) -> bytes:
+    """typlonk_vk_to_bytes (host-only): the 628-byte wire form of a verifying key"""
+    lib = load_library()
+    out = np.zeros(VK_WIRE_BYTES, dtype=np.uint8)
+    _host_err(lib, lib.typlonk_vk_to_bytes(C.byref(vk), _u8p(out)))
+    return out.tobytes()
+
+
+def vk_from_bytes(data, skip_subgroup: bool = False) -> Vk:
+    """typlonk_vk_from_bytes (host-only).  A rejected field raises TyplonkError with .status = its decode status."""
+    lib = load_library()
+    a = _bytes_arg(data, 1, "vk_from_bytes")
+    if a.size != VK_WIRE_BYTES:
+        raise ValueError(f"vk_from_bytes: {a.size} bytes, a key has {VK_WIRE_BYTES}")
+    vk = Vk()
+    st = C.c_uint32(0)
+    rc = lib.typlonk_vk_from_bytes(_u8p(a), DECODE_SKIP_SUBGROUP if skip_subgroup else 0, C.byref(vk), C.byref(st))
+    if rc:
+        err = TyplonkError(rc, lib.typlonk_strerror(rc).decode() + f" (decode status {decode_status(st.value)})")
+        err.status = st.value
+        raise err
+    return vk
 
 
 def transcript_challenges(points, n: int):
@@ -483,6 +603,48 @@ class Context:
         inf = np.zeros(count, dtype=np.uint8)
         self._chk(self.lib.typlonk_srs_download(self.h, sid, offset, count, _u64p(xy), _u8p(inf)))
         return xy, inf
+
+    def srs_load_compressed(self, data, skip_subgroup: bool = False) -> int:
+        """typlonk_srs_load_compressed: 48 bytes per point, decoded (and subgroup-checked) on the device.  A rejected point
+        raises TyplonkError with .first_bad = the lowest rejected index; no SRS is created."""
+        a = _bytes_arg(data, 1, "srs_load_compressed")
+        sid = C.c_uint32()
+        bad = C.c_size_t(0)
+        rc = self.lib.typlonk_srs_load_compressed(self.h, _u8p(a) if a.size else None, a.size,
+                                                  DECODE_SKIP_SUBGROUP if skip_subgroup else 0, C.byref(sid), C.byref(bad))
+        if rc:
+            err = TyplonkError(rc, self.lib.typlonk_strerror(rc).decode() + ": " + self.lib.typlonk_last_error(self.h).decode())
+            err.first_bad = bad.value
+            raise err
+        return sid.value
+
+    def srs_download_compressed(self, sid: int, offset: int = 0, count: int | None = None) -> bytes:
+        """typlonk_srs_download_compressed: count * 48 bytes, compressed on the device"""
+        count = self.srs_len(sid) - offset if count is None else count
+        out = np.zeros(max(count, 1) * G1_BYTES, dtype=np.uint8)
+        self._chk(self.lib.typlonk_srs_download_compressed(self.h, sid, offset, count, _u8p(out)))
+        return out[:count * G1_BYTES].tobytes()
+
+    def g1_decompress(self, data, skip_subgroup: bool = False):
+        """g1_decompress on this context's device"""
+        return g1_decompress(data, skip_subgroup, ctx=self)
+
+    def proofs_from_bytes(self, data, skip_subgroup: bool = False):
+        """proofs_from_bytes with the points decoded on this context's device"""
+        return proofs_from_bytes(data, skip_subgroup, ctx=self)
+
+    def verify_compact_bytes(self, vk: Vk, data, pi=None, skip_subgroup: bool = False) -> np.ndarray:
+        """typlonk_verify_compact_bytes: count * 656 bytes of proofs; pi as for verify_compact.  Returns a bool array; a proof
+        that does not decode is False and does not reach the verifier."""
+        a = _bytes_arg(data, PROOF_COMPACT_BYTES, "verify_compact_bytes")
+        k = a.size // PROOF_COMPACT_BYTES
+        if pi is not None and len(pi) != k:
+            raise ValueError("verify_compact_bytes: one public-input entry per proof")
+        keep, pip, lens = _pi_arg(pi, k)  # noqa: F841
+        ok = np.zeros(max(k, 1), dtype=np.uint8)
+        self._chk(self.lib.typlonk_verify_compact_bytes(self.h, C.byref(vk), _u8p(a) if k else None, k, pip, lens,
+                                                        DECODE_SKIP_SUBGROUP if skip_subgroup else 0, _u8p(ok)))
+        return ok[:k].astype(bool)
 
     def srs_precompute(self, sid: int, window_bits: int = 0):
         """fixed-base window tables for this SRS (typlonk_srs_precompute); 0 = the library picks the window by length"""

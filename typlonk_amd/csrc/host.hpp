@@ -356,6 +356,10 @@ int poly_eval_run(typlonk_ctx* ctx, const Fr* const* polys, size_t count, uint64
 int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const CircuitEntry::Commitments** out);
 // a verifying key without [s]G2 (zero): log_n, cosets, the eight commitments, SRS point 0
 int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4], typlonk_vk* vk);
+// what typlonk_verify_compact refuses before it looks at a proof, in its order and with its codes: log_n outside 1..24, a
+// pi_len[k] > n or a null pi[k] with pi_len[k] != 0, a g2s off the twist, a vk point off the curve, a non-canonical coset
+// (typlonk_verify_compact_bytes judges its arguments by the same function, before it decodes anything)
+int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------
 void comm_release(typlonk_ctx* ctx);

@@ -605,6 +605,25 @@ bool vk_points_valid(const typlonk_vk& vk) {
 
 }  // namespace
 
+namespace tyh {
+int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len) {
+    const uint32_t log_n = vk->log_n;
+    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "vk log_n outside 1..24");
+    const uint64_t n = 1ull << log_n;
+    for (size_t k = 0; k < count; ++k) {
+        const size_t len = pi_len ? pi_len[k] : 0;
+        if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "public-input column longer than n");
+        if (len && (!pi || !pi[k])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null public-input column");
+    }
+    P::G2Affine g2s;
+    if (!g2s_load(vk->g2s_xy, &g2s)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "vk g2s is not a point of the twist in canonical coordinates");
+    if (!vk_points_valid(*vk)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a vk point is not on the curve");
+    for (int i = 0; i < 3; ++i)
+        if (!fr_canonical(vk->cosets[i])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "vk coset is not a canonical residue");
+    return TYPLONK_OK;
+}
+}  // namespace tyh
+
 int typlonk_circuit_vk(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4],
                        const uint64_t g2s_xy[24], typlonk_vk* vk) {
     if (!ctx || !cosets || !g2s_xy || !vk) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
@@ -640,19 +659,12 @@ int typlonk_verify_compact(typlonk_ctx* ctx, const typlonk_vk* vk, const typlonk
     HIPCHK(hipSetDevice(ctx->device));
     const auto t_start = std::chrono::steady_clock::now();
     memset(ok, 0, count);
+    const int args_rc = verify_compact_check_args(ctx, vk, count, pi, pi_len);
+    if (args_rc) return args_rc;
     const uint32_t log_n = vk->log_n;
-    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "vk log_n outside 1..24");
     const uint64_t n = 1ull << log_n;
-    for (size_t k = 0; k < count; ++k) {
-        const size_t len = pi_len ? pi_len[k] : 0;
-        if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "public-input column longer than n");
-        if (len && (!pi || !pi[k])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null public-input column");
-    }
     P::G2Affine g2s;
-    if (!g2s_load(vk->g2s_xy, &g2s)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "vk g2s is not a point of the twist in canonical coordinates");
-    if (!vk_points_valid(*vk)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a vk point is not on the curve");
-    for (int i = 0; i < 3; ++i)
-        if (!fr_canonical(vk->cosets[i])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "vk coset is not a canonical residue");
+    (void)g2s_load(vk->g2s_xy, &g2s);   // (judged by verify_compact_check_args)
     ProfilingOff prof_off(ctx);
     const bool profiling = prof_off.saved;
 

@@ -831,5 +831,60 @@ inline std::vector<bool> verify_compact(const Context& ctx, const typlonk_vk& vk
     return std::vector<bool>(ok.begin(), ok.begin() + proofs.size());
 }
 
+// ---- the wire format (include/typlonk.h): compact proofs and verifying keys as bytes, points compressed ----
+// Proof <-> its 656 bytes.  to_bytes throws for a field that is not canonical or a point off the curve.
+inline std::vector<uint8_t> proof_to_bytes(const typlonk_proof_compact& proof) {
+    std::vector<uint8_t> out(TYPLONK_PROOF_COMPACT_BYTES);
+    check(typlonk_proof_compact_to_bytes(&proof, out.data()));
+    return out;
+}
+// `bytes` = count * 656.  Every point is decoded -- on the curve, in the subgroup -- by one kernel launch on `ctx` (nullptr: on the
+// host); status[k] != 0 names the class and field of the first bad field of proof k (TYPLONK_DECODE_CLASS / _FIELD), and that
+// proof is all identities.  The challenge fields are zero: the verifier recomputes them.
+inline std::vector<typlonk_proof_compact> proofs_from_bytes(const Context* ctx, const std::vector<uint8_t>& bytes,
+                                                            std::vector<uint32_t>* status, uint32_t flags = 0) {
+    if (bytes.size() % TYPLONK_PROOF_COMPACT_BYTES) throw std::runtime_error("proofs are 656 bytes each");
+    const size_t count = bytes.size() / TYPLONK_PROOF_COMPACT_BYTES;
+    std::vector<typlonk_proof_compact> out(count);
+    std::vector<uint32_t> st(count, 0);
+    typlonk_ctx* c = ctx ? ctx->raw() : nullptr;
+    check(typlonk_proof_compact_from_bytes(c, bytes.data(), count, flags, out.data(), st.data()), c);
+    if (status) *status = st;
+    return out;
+}
+inline std::vector<uint8_t> vk_to_bytes(const typlonk_vk& vk) {
+    std::vector<uint8_t> out(TYPLONK_VK_WIRE_BYTES);
+    check(typlonk_vk_to_bytes(&vk, out.data()));
+    return out;
+}
+// throws for a key that is refused (a bad field, log_n outside 1..24)
+inline typlonk_vk vk_from_bytes(const std::vector<uint8_t>& bytes, uint32_t flags = 0) {
+    if (bytes.size() != TYPLONK_VK_WIRE_BYTES) throw std::runtime_error("a verifying key is 628 bytes");
+    typlonk_vk vk;
+    uint32_t st = 0;
+    const int rc = typlonk_vk_from_bytes(bytes.data(), flags, &vk, &st);
+    if (rc < 0)
+        throw std::runtime_error(std::string(typlonk_strerror(rc)) + ": key field " + std::to_string(TYPLONK_DECODE_FIELD(st)) +
+                                 ", class " + std::to_string(TYPLONK_DECODE_CLASS(st)));
+    return vk;
+}
+// verify_compact over the wire form: a proof that does not decode is false and never reaches the verifier
+inline std::vector<bool> verify_compact_bytes(const Context& ctx, const typlonk_vk& vk, const std::vector<uint8_t>& bytes,
+                                              const std::vector<std::vector<Fr>>& public_inputs = {}, uint32_t flags = 0) {
+    if (bytes.size() % TYPLONK_PROOF_COMPACT_BYTES) throw std::runtime_error("proofs are 656 bytes each");
+    const size_t count = bytes.size() / TYPLONK_PROOF_COMPACT_BYTES;
+    if (!public_inputs.empty() && public_inputs.size() != count) throw std::runtime_error("one public-input list per proof");
+    std::vector<const uint64_t*> pis(count, nullptr);
+    std::vector<size_t> lens(count, 0);
+    for (size_t k = 0; k < public_inputs.size(); ++k)
+        if (!public_inputs[k].empty()) {
+            pis[k] = public_inputs[k][0].limbs();
+            lens[k] = public_inputs[k].size();
+        }
+    std::vector<uint8_t> ok(count + 1, 0);
+    check(typlonk_verify_compact_bytes(ctx.raw(), &vk, bytes.data(), count, pis.data(), lens.data(), flags, ok.data()), ctx.raw());
+    return std::vector<bool>(ok.begin(), ok.begin() + count);
+}
+
 }  // namespace plonk
 }  // namespace typlonk
