@@ -119,6 +119,30 @@ int typlonk_srs_len(typlonk_ctx* ctx, uint32_t srs_id, size_t* len);
  *                            full coefficient vector(s) and gets the full sum(s) (collective).
  * typlonk_prove on a context with a communicator and an SRS shard folds the commitments of every round itself, so
  * all ranks hash identical points, squeeze identical challenges and return the identical proof.
+ * The compact shape on a shard -- a "folding context" is one with a communicator, used with an SRS id that has a shard set.
+ * On it these five calls are COLLECTIVES that every rank must make, in the same order, and each returns on every rank exactly
+ * what one context holding the whole SRS returns, byte for byte:
+ *   typlonk_circuit_commitments            one fold of 8 records: the ranks' partial sums of the eight circuit commitments
+ *   typlonk_circuit_vk                     one fold of 9 records: the same and the P0 record (SRS point 0 on the rank whose
+ *                                          range starts at index 0, the identity on the others)
+ *   typlonk_prove_compact / _compact_host  four folds of 12, 1, 3 and 2 records per proof, a FIXED schedule:
+ *                                            1. [a] [b] [c], the eight partial circuit commitments, the P0 record  (-> beta, gamma)
+ *                                            2. [Z]  (-> alpha)     3. [t_lo] [t_mid] [t_hi]  (-> zeta)     4. W_z, W_zw
+ *                                          The statement digest d0 is formed from the folded key after fold 1.  The eight MSMs run
+ *                                          once per (circuit, SRS) on a rank -- what is cached is that rank's PARTIAL sums -- and
+ *                                          the nine records are sent with every proof (about 1 KB), so that no rank can disagree
+ *                                          with its peers about a fold's record count, whatever its cache holds and whichever
+ *                                          argument it refuses.
+ * The record counts above are the contract: they depend on nothing that differs between ranks.  Failure: once such a call is
+ * past its null-pointer checks every path ends in its next fold.  A rank that refuses its arguments (an unknown circuit, a
+ * short wire column, pi_len > n, ...), meets a device error or fails a round joins that fold with flagged records and returns
+ * ITS OWN code; every peer returns TYPLONK_ERR_COMM naming that rank; all ranks leave at the same fold, no proof is in flight
+ * afterwards, and the communicator and the context stay usable.  An unsatisfied witness is not a failure of the exchange:
+ * r(zeta) comes from replicated data, all four folds complete and every rank returns TYPLONK_ERR_UNSATISFIED with `out` filled
+ * as on one GPU.  A shard WITHOUT a communicator is refused with TYPLONK_ERR_INVALID_ARG by all five (nothing can fold
+ * mid-call from outside).  typlonk_verify, typlonk_prove_batch and typlonk_prove_batch_compact refuse shards with or without
+ * one: sharding is for the latency of ONE large proof; a batch of small proofs belongs on one GPU per proof (a wave holds 4
+ * proofs at 2^20 rows and 1 from 2^22 on).  Exercised with 2 and 8 ranks: tests/test_gpu_dist_compact.py.
  * Failure on one rank: a member of a communicator never leaves between "decided to fold" and the collective.  The
  * *_sharded_* entry points, typlonk_comm_fold_g1 and typlonk_prove join the collective of the step that failed with
  * flagged records -- whether the failure is the local MSM / prover round, a bad argument (a null output, m > len) or the
@@ -376,7 +400,9 @@ int typlonk_transcript_challenges(const uint64_t* xy, const uint8_t* inf, size_t
  * typlonk_circuit_load keeps (CircuitEntry::coef), one batch of eight MSMs over srs_id (>= n points, no shard set).
  * Computed once per (circuit, srs) and cached with the circuit; GateConstrains::fixed_commitments (builder.rs) and
  * CompiledPermutation::sigma_commitments (permutation/src/lib.rs:178-194).  An SRS shorter than n returns
- * TYPLONK_ERR_LENGTH, a sharded one (typlonk_srs_set_shard) TYPLONK_ERR_INVALID_ARG. */
+ * TYPLONK_ERR_LENGTH.  An SRS shard (typlonk_srs_set_shard): TYPLONK_ERR_INVALID_ARG on a context without a communicator; with
+ * one the call is a COLLECTIVE every rank must make -- one fold of 8 records, this rank's cached partial sums -- and returns the
+ * whole-SRS commitments on every rank ("The compact shape on a shard" above, failure protocol included). */
 int typlonk_circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[8][12], uint8_t inf[8]);
 
 /* `count` proofs of one circuit.  ok[k] = 1 iff proof k is accepted.
@@ -400,7 +426,7 @@ int typlonk_circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circ
  * the flags) read as a little-endian integer mod r: deterministic.  When the fold fails it is bisected with the same
  * weights, so every verdict is the per-proof decision of the reference (up to the fold's soundness error, <= 6 count / r);
  * b bad proofs cost at most 2 b ceil(log2 count) + 1 pairing products.  Single GPU: a sharded SRS returns
- * TYPLONK_ERR_INVALID_ARG.  Returns an error only for bad arguments or device failures; a bad proof is ok[k] = 0.
+ * TYPLONK_ERR_INVALID_ARG, with or without a communicator (a verifier's two MSMs are short; nothing is gained by sharding them).  Returns an error only for bad arguments or device failures; a bad proof is ok[k] = 0.
  * count = 0 is a no-op.  With profiling on (typlonk_set_profiling), typlonk_profile_get reports the host wall time of the
  * stages: "verify_host", "verify_eval", "verify_msm", "verify_pairing", then "verify_folds" -- the number of
  * pairing products, a count, not milliseconds. */
@@ -464,20 +490,26 @@ typedef struct typlonk_proof_compact {
 } typlonk_proof_compact;
 /* The verifying key of a loaded circuit: the cached typlonk_circuit_commitments (one batch of eight MSMs the first time per
  * (circuit, SRS)), SRS point 0, the cosets and [s]G2.  A g2s that is not on the twist returns TYPLONK_ERR_INVALID_ARG; SRS
- * errors as for typlonk_circuit_commitments. */
+ * errors as for typlonk_circuit_commitments.  On an SRS shard with a communicator: a COLLECTIVE every rank must make, one fold
+ * of 9 records (the eight partial sums and the P0 record); every rank gets the whole-SRS key, so a rank of a sharded job can
+ * hand out the verifying key of its own circuit. */
 int typlonk_circuit_vk(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4],
                        const uint64_t g2s_xy[24], typlonk_vk* vk);
 /* One compact proof.  wire_evals as for typlonk_prove; pi: a buffer of >= pi_len elements of which only the first pi_len are
  * read (may be NULL when pi_len = 0), brought to the host once for d0.  The first compact proof of a (circuit, SRS) pair
  * computes the circuit commitments for d0 (a one-time cost, cached with the circuit).  Rounds 1 and 2 run as in typlonk_prove;
  * round 3 queues the quotient once alpha is known and waits for its three commitments before it draws zeta.
- * Returns TYPLONK_ERR_UNSATISFIED (with `out` completely filled) when r(zeta) != 0; TYPLONK_ERR_INVALID_ARG for a sharded SRS
- * or while a round-by-round prover is open; TYPLONK_ERR_DOMAIN above 2^24 rows; TYPLONK_ERR_LENGTH when pi_len > n or the
- * SRS is shorter than n. */
+ * Returns TYPLONK_ERR_UNSATISFIED (with `out` completely filled) when r(zeta) != 0; TYPLONK_ERR_INVALID_ARG for an SRS shard
+ * on a context without a communicator or while a round-by-round prover is open; TYPLONK_ERR_DOMAIN above 2^24 rows;
+ * TYPLONK_ERR_LENGTH when pi_len > n or the SRS (a shard: its total length) is shorter than n.
+ * On an SRS shard with a communicator the call is a COLLECTIVE: four folds of 12, 1, 3 and 2 records ("The compact shape on a
+ * shard" above), the same proof on every rank as from one context with the whole SRS; a rank that fails returns its own code
+ * and its peers TYPLONK_ERR_COMM, at the same fold. */
 int typlonk_prove_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
                           const typlonk_buf* pi, size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out);
 /* The same with the columns in HOST memory (uploaded column by column beside round 1, as typlonk_prove_host): wire_evals[i]
- * holds `rows` Fr elements, and rows must equal the circuit's n (else TYPLONK_ERR_LENGTH); pi holds pi_len values. */
+ * holds `rows` Fr elements, and rows must equal the circuit's n (else TYPLONK_ERR_LENGTH); pi holds pi_len values.  On a shard
+ * with a communicator: the same collective as typlonk_prove_compact. */
 int typlonk_prove_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
                                size_t rows, const uint64_t* pi, size_t pi_len, const uint64_t cosets[3][4],
                                typlonk_proof_compact* out);

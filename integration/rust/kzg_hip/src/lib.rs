@@ -398,6 +398,8 @@ impl Backend {
 
     // ---- the compact proof shape (include/typlonk.h): batched openings, a transcript that binds the statement ----------
     /// The verifying key of a loaded circuit (`typlonk_circuit_vk`): all `verify_compact` needs, on any backend.
+    /// After `set_shard` and `comm_init` this is a COLLECTIVE every rank must call: one fold of 9 records (the ranks' partial
+    /// sums of the eight circuit commitments and the P0 record); every rank gets the key one GPU with the whole SRS returns.
     pub fn verifying_key(&self, srs: SrsHandle, circuit: CircuitHandle, cosets: [Fr; 3], g2s: &[u64; 24]) -> ffi::TyplonkVk {
         let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
         let mut vk = std::mem::MaybeUninit::<ffi::TyplonkVk>::zeroed();
@@ -407,6 +409,15 @@ impl Backend {
 
     /// A compact proof (`typlonk_prove_compact_host`): `wire_evals` as for `prove`; `public_inputs` = the statement's public
     /// values themselves (at most n, not padded: their number is part of the statement).  Panics on an unsatisfied witness.
+    ///
+    /// Multi-GPU: after `set_shard` on `srs` and `comm_init` on this backend the call is a COLLECTIVE that every rank makes
+    /// with the same witness -- four folds of 12, 1, 3 and 2 records inside the library ([a] [b] [c] + the rank's eight
+    /// partial circuit commitments + its P0 record; [Z]; [t_lo] [t_mid] [t_hi]; W_z, W_zw) -- and every rank returns the
+    /// proof one GPU holding the whole SRS returns, byte for byte.  A rank whose call is refused (or whose device fails)
+    /// panics with its own error, every peer with `TYPLONK_ERR_COMM` naming that rank, all at the same fold; the
+    /// communicator stays usable.  A shard without a communicator is refused (`TYPLONK_ERR_INVALID_ARG`);
+    /// `prove_batch_compact`, `prove_batch` and `verify_batch` refuse shards always: a batch of small proofs belongs on one GPU
+    /// per proof.
     pub fn prove_compact(&self, srs: SrsHandle, circuit: CircuitHandle, wire_evals: [&[Fr]; 3], public_inputs: &[Fr],
                          cosets: [Fr; 3]) -> ffi::TyplonkProofCompact {
         let rows = wire_evals[0].len();   // the library checks it against the circuit's n

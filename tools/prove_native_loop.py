@@ -1,5 +1,6 @@
 """A fixed number of NATIVE proofs (typlonk_prove: the library's own transcript between the rounds, no Python in between) on the
-squaring-chain circuit, for rocprofv3 kernel traces.  HOST=1: typlonk_prove_host (columns in host memory)."""
+squaring-chain circuit, for rocprofv3 kernel traces.  HOST=1: typlonk_prove_host (columns in host memory).
+SHAPE=compact: typlonk_prove_compact / typlonk_prove_compact_host instead (no public values)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,6 +32,11 @@ host = os.environ.get("HOST", "0") == "1"
 cols = [b.download() for b in chain.wire_evals] if host else None
 run = (lambda: ctx.prove_native_host(sid, chain.circuit, cols, None, chain.cosets)) if host else \
       (lambda: ctx.prove_native(sid, chain.circuit, chain.wire_evals, chain.pi_evals, chain.cosets))
+shape = os.environ.get("SHAPE", "reference")
+if shape == "compact":
+    run = (lambda: ctx.prove_compact_host(sid, chain.circuit, cols, None, chain.cosets)) if host else \
+          (lambda: ctx.prove_compact(sid, chain.circuit, chain.wire_evals, None, 0, chain.cosets))
+    run()      # the circuit commitments for the statement digest: once per (circuit, SRS)
 run()
 torch.cuda.synchronize()
 reps = int(os.environ.get("REPS", "5"))
@@ -43,4 +49,4 @@ for _ in range(reps):
     if gap:
         torch.cuda.synchronize()
         time.sleep(gap)
-print(f"prove_native log_n={log_n} host={host}: {tot / reps * 1e3:.2f} ms per proof", flush=True)
+print(f"prove_native log_n={log_n} host={host} shape={shape}: {tot / reps * 1e3:.2f} ms per proof", flush=True)

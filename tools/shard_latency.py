@@ -2,7 +2,8 @@
 
 Prints wall time per local MSM, the kernel stage times, and the cost of the exchange path (all-gather + fold) measured
 with a one-rank RCCL group (TYPLONK_FORCE_COLLECTIVE-style), which has the launch and copy latencies of the real thing
-but no wire time."""
+but no wire time.
+LEG=compact: one rank's share of a sharded COMPACT proof instead (see below), WORLD = 1, 2, 4, 8."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,6 +27,43 @@ sh.generate_srs(fr_mont_limbs(2))
 tables = os.environ.get("TABLES", "auto")
 if (sh.hi - sh.lo) >= (1 << 16) and tables != "0":
     ctx.srs_precompute(sh.sid, 0 if tables == "auto" else int(tables))
+if os.environ.get("LEG") == "compact":
+    # One rank's SHARE of a sharded COMPACT proof (typlonk_prove_compact on the shard): this process is rank 0 of WORLD with a
+    # 1/WORLD shard, on a ONE-rank communicator -- the four folds (12, 1, 3, 2 records) have the launch, copy and
+    # synchronisation latencies of the real thing but no wire time and no peers.  With WORLD > 1 the result is a PARTIAL sum,
+    # not a valid proof: timing only.  Nothing here is a multi-GPU measurement (real RCCL with N > 1 has never run); the figure
+    # is a projection of what each of N GPUs would spend.  In the same process, alternated: the whole-SRS
+    # typlonk_prove_compact (one GPU) and typlonk_prove (reference shape) on the same shard.
+    from typlonk_amd.capi import comm_unique_id
+    from typlonk_amd.circuits import SquaringChain
+    ctx.set_profiling(False)
+    ctx.comm_init(comm_unique_id(), 0, 1)
+    whole = ctx.srs_generate(fr_mont_limbs(2), n + 3)
+    if tables != "0":
+        ctx.srs_precompute(whole, 0 if tables == "auto" else int(tables))
+    chain = SquaringChain(ctx, log_n)
+    legs = {"compact_on_shard_ms": lambda: ctx.prove_compact(sh.sid, chain.circuit, chain.wire_evals, None, 0, chain.cosets),
+            "compact_whole_srs_ms": lambda: ctx.prove_compact(whole, chain.circuit, chain.wire_evals, None, 0, chain.cosets),
+            "prove_on_shard_ms": lambda: ctx.prove_native(sh.sid, chain.circuit, chain.wire_evals, chain.pi_evals, chain.cosets)}
+    for f in legs.values():          # warm-up: the circuit commitments of both SRS ids, the arena, the NTT tables
+        f()
+        f()
+    rounds = int(os.environ.get("ROUNDS", "8"))
+    ts = {k: [] for k in legs}
+    for _ in range(rounds):          # alternated: every leg sees the same clocks and the same neighbours
+        for k, f in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    out = {"leg": "compact", "log_n": log_n, "world": world, "rank": rank, "tables": tables, "rounds": rounds,
+           "local_points": sh.hi - sh.lo, "one_gpu_share_not_a_multi_gpu_measurement": True}
+    for k, v in ts.items():
+        v = sorted(v)
+        out[k] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+    out["share_vs_one_gpu_compact"] = round(out["compact_on_shard_ms"]["median"] / out["compact_whole_srs_ms"]["median"], 3)
+    print("SHARD " + json.dumps(out))
+    sys.exit(0)
 full = synthetic_scalars(n, 0x5EED0000 + log_n, dev)
 for _ in range(10):
     sh.msm_local_devptr(full.data_ptr(), n)

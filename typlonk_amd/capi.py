@@ -803,7 +803,9 @@ class Context:
         return out
 
     def circuit_commitments(self, sid: int, circuit: int):
-        """typlonk_circuit_commitments: [(xy[12], inf)] * 8 -- [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3]"""
+        """typlonk_circuit_commitments: [(xy[12], inf)] * 8 -- [q_l] [q_r] [q_o] [q_m] [q_c] [sigma_1] [sigma_2] [sigma_3].
+        On an SRS shard with a communicator: a COLLECTIVE (one fold of 8 records) every rank must call; every rank gets the
+        whole-SRS commitments."""
         xy = np.zeros((8, 12), dtype=np.uint64)
         inf = np.zeros(8, dtype=np.uint8)
         self._chk(self.lib.typlonk_circuit_commitments(self.h, sid, circuit, _u64p(xy), _u8p(inf)))
@@ -860,7 +862,10 @@ class Context:
 
     # ---- the compact proof shape (include/typlonk.h, typlonk_prove_compact) ----------------------------------------------
     def circuit_vk(self, sid: int, circuit: int, cosets, g2s_xy) -> Vk:
-        """typlonk_circuit_vk: the verifying key (the cached circuit commitments, SRS point 0, the cosets, [s]G2)"""
+        """typlonk_circuit_vk: the verifying key (the cached circuit commitments, SRS point 0, the cosets, [s]G2).
+        On an SRS shard with a communicator this is a COLLECTIVE every rank must call: one fold of 9 records (the ranks'
+        partial sums of the eight commitments and the P0 record of the rank that holds index 0); every rank gets the key one
+        context with the whole SRS returns.  A shard without a communicator is refused (ERR_INVALID_ARG)."""
         vk = Vk()
         g2 = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
         self._chk(self.lib.typlonk_circuit_vk(self.h, sid, circuit, C.byref(_cosets_arg(cosets)), _u64p(g2), C.byref(vk)))
@@ -878,7 +883,10 @@ class Context:
 
     def prove_compact(self, sid: int, circuit: int, wire_evals, pi=None, pi_len: int | None = None, cosets=None) -> dict:
         """typlonk_prove_compact: wire_evals = [a, b, c] DeviceBuffers; pi = a DeviceBuffer of >= pi_len public values (pi_len
-        defaults to its length) or None.  Returns compact_dict(proof)."""
+        defaults to its length) or None.  Returns compact_dict(proof).
+        On an SRS shard with a communicator (comm_init) the call is a COLLECTIVE: four folds of 12, 1, 3 and 2 records, the same
+        proof on every rank as from one context with the whole SRS.  A rank whose call fails raises its own error, its peers
+        ERR_COMM naming it, all at the same fold; ERR_UNSATISFIED is raised on every rank with the same filled .proof."""
         w = (C.c_void_p * 3)(*[b.handle.value for b in wire_evals])
         if pi_len is None:
             pi_len = pi.n if pi is not None else 0
@@ -889,7 +897,8 @@ class Context:
 
     def prove_compact_host(self, sid: int, circuit: int, wire_evals_host, pi=None, cosets=None) -> dict:
         """typlonk_prove_compact_host: three (n, 4) u64 host columns of equal length, pi = None or an (l, 4) column of l public
-        values.  The row count is passed on and checked against the circuit's n by the library."""
+        values.  The row count is passed on and checked against the circuit's n by the library.  On an SRS shard with a
+        communicator: the same collective as prove_compact."""
         cols = [np.ascontiguousarray(w, dtype=np.uint64) for w in wire_evals_host]
         if len(cols) != 3 or any(c.ndim != 2 or c.shape[1] != 4 or c.shape != cols[0].shape for c in cols):
             raise ValueError("prove_compact_host needs three (rows, 4) uint64 columns of equal length")

@@ -354,7 +354,11 @@ int poly_eval_run(typlonk_ctx* ctx, const Fr* const* polys, size_t count, uint64
                   uint64_t* out);
 // the eight commitments of a circuit over a whole SRS (>= n points): computed on first use per (circuit, SRS), then cached
 int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const CircuitEntry::Commitments** out);
-// a verifying key without [s]G2 (zero): log_n, cosets, the eight commitments, SRS point 0
+// an SRS SHARD's share of the statement, to be folded over the ranks by the caller: this rank's partial sums of the eight
+// commitments (cached per (circuit, SRS) like the above) and its P0 record -- the point on the rank that holds index 0, the
+// identity elsewhere.  Local: no collective inside.
+int circuit_statement_partial(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[9][12], uint8_t inf[9]);
+// a verifying key without [s]G2 (zero): log_n, cosets, the eight commitments, SRS point 0 (whole SRS)
 int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4], typlonk_vk* vk);
 // what typlonk_verify_compact refuses before it looks at a proof, in its order and with its codes: log_n outside 1..24, a
 // pi_len[k] > n or a null pi[k] with pi_len[k] != 0, a g2s off the twist, a vk point off the curve, a non-canonical coset

@@ -828,7 +828,11 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
     auto si = ctx->srs.find(srs_id);
     if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
     if (si->second.total_len || comm_folds(ctx, srs_id))
-        return fail(ctx, TYPLONK_ERR_INVALID_ARG, "batched proving needs a whole SRS on one GPU, not a shard");
+        // sharding buys latency for ONE large proof (typlonk_prove, typlonk_prove_compact); a batch of small proofs belongs on
+        // one GPU per proof, and from 2^22 rows on a wave holds a single proof anyway (4 at 2^20)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                    "batched proving needs a whole SRS on one GPU, not a shard (shard single large proofs with "
+                    "typlonk_prove / typlonk_prove_compact; give each GPU its own batch)");
     if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
     if (rows != SIZE_MAX && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");

@@ -905,21 +905,29 @@ int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typ
 // compact transcript's order -- the quotient is committed before zeta is drawn, sigma_1(zeta) and sigma_2(zeta) are sent, and
 // every opening at zeta is one witness of F = a + v b + v^2 c + v^3 Z + v^4 r + v^5 sigma_1 + v^6 sigma_2.
 namespace {
-int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al, typlonk_proof_compact* out) {
+// folds (an SRS shard on a context with a communicator): the two groups of commitments are folded over the ranks where the
+// host needs them -- [t_lo] [t_mid] [t_hi] before zeta (3 records), W_zeta and W_zeta_w at the end (2 records).  A rank that
+// fails joins the NEXT of the two collectives with flagged records and returns there, as its peers do (comm_fold).
+int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al, typlonk_proof_compact* out, bool folds) {
     typlonk_ctx* ctx = p->ctx;
-    if (p->round != 2) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "round3 must follow round2");
-    HIPCHK(hipSetDevice(ctx->device));
+    // every way out before zeta / after zeta: through that stage's collective when folding
+    auto leave_t = [&](int rc) { return folds ? comm_fold(ctx, &out->t_xy[0][0], out->t_inf, 3, rc) : rc; };
+    auto leave_w = [&](int rc) { return folds ? comm_fold(ctx, &out->w_xy[0][0], out->w_inf, 2, rc) : rc; };
+    auto hip_rc = [&](hipError_t he) { return he == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)); };
+    if (p->round != 2) return leave_t(fail(ctx, TYPLONK_ERR_INVALID_ARG, "round3 must follow round2"));
+    int rc = hip_rc(hipSetDevice(ctx->device));
+    if (rc) return leave_t(rc);
     auto cit = ctx->circuits.find(p->circuit);
-    if (cit == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "circuit was freed during the proof");
+    if (cit == ctx->circuits.end()) return leave_t(fail(ctx, TYPLONK_ERR_INVALID_ARG, "circuit was freed during the proof"));
     const CircuitEntry& ce = cit->second;
     const uint64_t n = p->n;
     const uint32_t log_n = p->log_n;
     ProfilingOff prof_off(ctx);  // stage events are per call
     ProverRound in_round(ctx);
     const SrsEntry* srs = nullptr;
-    int rc = msm_validate(ctx, p->srs_id, n, &srs);
-    if (rc) return rc;
-    if (!ctx->batch_fence) HIPCHK(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+    rc = msm_validate(ctx, p->srs_id, n, &srs);
+    if (!rc && !ctx->batch_fence) rc = hip_rc(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+    if (rc) return leave_t(rc);
     // the queue outlives every early return (its destructor-side wait below): the MSMs write into `out`
     MsmQueue q(ctx, srs, /*first_lane=*/0);
     struct WaitAll {
@@ -957,6 +965,7 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
         const int r = q.wait_all();
         if (!rc) rc = r;
     }
+    rc = leave_t(rc);   // collective 3 of a sharded proof
     if (rc) return rc;
     // ---- zeta binds the quotient ----
     for (int i = 0; i < 3; ++i) tr.point(out->t_xy[i], out->t_inf[i]);
@@ -969,7 +978,7 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
     {
         Fr *blocks = nullptr, *slots = nullptr;
         rc = prover_ops_tmp(p, &blocks, &slots);
-        if (rc) return rc;
+        if (rc) return leave_w(rc);
         const Fr* polys[8];
         Fr* quots[8];
         Fr* ys[8];
@@ -989,10 +998,10 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
         item(p->z, p->q[4], 4, 1);                        // Z at zeta * w, with its quotient
         launch_open_multi(polys, quots, ys, zsel, cnt, n, ze, zw, blocks, ctx->stream);
         const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        if (he != hipSuccess) return leave_w(fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)));
         lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);   // while the kernels run
         rc = prover_fetch(p, host, 8);
-        if (rc) return rc;
+        if (rc) return leave_w(rc);
     }
     const Fr pi_z = p->has_pi ? host[7] : Fr::zero();
     for (int i = 0; i < 7; ++i) {
@@ -1014,7 +1023,7 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
         la.n = n;
         launch_lincomb(la, ctx->stream);
         const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        if (he != hipSuccess) return leave_w(fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)));
     }
     rc = prover_open_async(p, p->r, n, ze, nullptr, 0);
     // ---- F as one 7-term combination in q[1], its witness polynomial in q[0] (q[0..3] are free in this shape) ----
@@ -1046,6 +1055,9 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
     }
     Fr rz;
     if (!rc) rc = prover_fetch(p, &rz, 1);   // (every lane has been waited for: this returns at once)
+    // collective 4 of a sharded proof.  r(zeta) comes from replicated data: an unsatisfied witness is unsatisfied on every
+    // rank, the points are folded all the same and `out` is filled as on one GPU
+    rc = leave_w(rc);
     if (rc) return rc;
     p->round = 3;
     if (!rz.is_zero())
@@ -1053,10 +1065,11 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
     return TYPLONK_OK;
 }
 
+// what typlonk_prove_compact refuses before it queues anything, in this order; fills the column sources
 // rows: the host form's column length (must be n), SIZE_MAX for the device form
-int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
+int prove_compact_args(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
                        const uint64_t* const* wire_host, size_t rows, const typlonk_buf* pi_buf, const uint64_t* pi_host,
-                       size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
+                       size_t pi_len, ColumnSrc (&w)[3], ColumnSrc& pi) {
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
     auto ci = ctx->circuits.find(circuit_id);
@@ -1066,11 +1079,13 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     const uint64_t n = 1ull << log_n;
     auto si = ctx->srs.find(srs_id);
     if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
-    if (si->second.total_len) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "compact proofs need a whole SRS, not a shard");
-    if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
+    if (si->second.total_len && !ctx->comm.comm)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                    "a compact proof on an SRS shard needs a communicator on the context (typlonk_comm_init): its commitments are "
+                    "folded over the ranks inside the call, before each challenge");
+    if (si->second.total() < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
     if (pi_len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
     if (!wire_bufs && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
-    ColumnSrc w[3], pi;
     for (int i = 0; i < 3; ++i) {
         if (wire_bufs) {
             if (!wire_bufs[i] || wire_bufs[i]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
@@ -1085,36 +1100,80 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
         pi.host = pi_host;
         pi.rows = pi_len;
     }
-    memset(out, 0, sizeof(*out));
+    return TYPLONK_OK;
+}
+
+// On an SRS shard with a communicator (folds) the call is a collective with a FIXED schedule of 12, 1, 3 and 2 records:
+//   1. [a] [b] [c], this rank's eight partial circuit commitments (cached or not) and its P0 record -- before beta, gamma;
+//      the statement digest d0 is formed from the folded key, after this fold (it is first hashed together with [a] [b] [c])
+//   2. [Z] before alpha      3. [t_lo] [t_mid] [t_hi] before zeta      4. W_zeta, W_zeta_w
+// The counts depend on nothing a rank could see differently from its peers: not on its cache, not on which argument it
+// refuses.  From here on every path of a member ends in the next collective: a rank that fails joins it with flagged records
+// and returns its own code there, its peers return TYPLONK_ERR_COMM there (comm_fold), the prover is freed on every path.
+int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
+                       const uint64_t* const* wire_host, size_t rows, const typlonk_buf* pi_buf, const uint64_t* pi_host,
+                       size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
+    const bool folds = comm_folds(ctx, srs_id);
+    ColumnSrc w[3], pi;
+    int rc = prove_compact_args(ctx, srs_id, circuit_id, wire_bufs, wire_host, rows, pi_buf, pi_host, pi_len, w, pi);
+    if (rc && !folds) return rc;
+    if (!rc) memset(out, 0, sizeof(*out));
     // the statement: the circuit's commitments (one batch of eight MSMs the first time per circuit and SRS, then cached), P0,
     // and the pi_len public values -- brought to the host once in the device form
     typlonk_vk vk;
-    int rc = circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
-    if (rc) return rc;
+    uint64_t rec_xy[12][12];   // the first fold of a sharded proof: a b c | q_l .. sigma_3 | P0
+    uint8_t rec_inf[12];
+    if (!rc) rc = folds ? circuit_statement_partial(ctx, srs_id, circuit_id, rec_xy + 3, rec_inf + 3)
+                        : circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
     std::vector<uint64_t> pi_vals;
     const uint64_t* piv = pi_host;
-    if (pi.dev) {
+    if (!rc && pi.dev) {
         pi_vals.resize(4 * pi_len);
-        HIPCHK(hipMemcpyAsync(pi_vals.data(), pi.dev, pi_len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        hipError_t he = hipMemcpyAsync(pi_vals.data(), pi.dev, pi_len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
+        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
         piv = pi_vals.data();
     }
+    if (rc && !folds) return rc;
     uint8_t d0[64];
-    compact_statement_digest(vk, piv, pi_len, d0);
+    if (!folds) compact_statement_digest(vk, piv, pi_len, d0);
     typlonk_prover* p = nullptr;
-    rc = prover_round1_impl(ctx, srs_id, circuit_id, w, pi, &p, out->commit_xy, out->commit_inf);
-    if (rc) return rc;
+    if (!rc) rc = prover_round1_impl(ctx, srs_id, circuit_id, w, pi, &p, out->commit_xy, out->commit_inf);
+    if (folds) {
+        if (!rc) {
+            memcpy(rec_xy, out->commit_xy, 3 * 96);
+            memcpy(rec_inf, out->commit_inf, 3);
+        }
+        rc = comm_fold(ctx, &rec_xy[0][0], rec_inf, 12, rc);   // collective 1
+        if (!rc) {
+            memcpy(out->commit_xy, rec_xy, 3 * 96);
+            memcpy(out->commit_inf, rec_inf, 3);
+            memset(&vk, 0, sizeof(vk));
+            vk.log_n = p->log_n;
+            memcpy(vk.cosets, cosets, sizeof(vk.cosets));
+            memcpy(vk.commit_xy, rec_xy + 3, sizeof(vk.commit_xy));
+            memcpy(vk.commit_inf, rec_inf + 3, sizeof(vk.commit_inf));
+            memcpy(vk.srs0_xy, rec_xy[11], sizeof(vk.srs0_xy));
+            vk.srs0_inf = rec_inf[11];
+            compact_statement_digest(vk, piv, pi_len, d0);
+        }
+    }
+    if (rc) {
+        if (p) typlonk_prover_free(p);
+        return rc;
+    }
     CompactTranscript tr(d0);
     for (int i = 0; i < 3; ++i) tr.point(out->commit_xy[i], out->commit_inf[i]);
     const Fr beta = tr.squeeze('b'), gamma = tr.squeeze('g');
     memcpy(out->beta, beta.v, 32);
     memcpy(out->gamma, gamma.v, 32);
     rc = typlonk_prover_round2(p, out->beta, out->gamma, cosets, out->z_xy, &out->z_inf);
+    if (folds) rc = comm_fold(ctx, out->z_xy, &out->z_inf, 1, rc);   // collective 2
     if (!rc) {
         tr.point(out->z_xy, out->z_inf);
         const Fr alpha = tr.squeeze('a');
         memcpy(out->alpha, alpha.v, 32);
-        rc = prover_round3_compact(p, tr, alpha, out);
+        rc = prover_round3_compact(p, tr, alpha, out, folds);   // collectives 3 and 4
     }
     typlonk_prover_free(p);
     return rc;

@@ -76,7 +76,13 @@ int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, 
     if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
     auto si = ctx->srs.find(srs_id);
     if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
-    if (si->second.total_len) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "verification needs a whole SRS, not a shard");
+    // (a shard on a context WITH a communicator never comes here: typlonk_circuit_commitments / typlonk_circuit_vk /
+    // typlonk_prove_compact fold circuit_statement_partial instead.  typlonk_verify and the batched provers stay on one GPU:
+    // sharding is for the latency of one large proof; many small ones belong on one GPU per proof)
+    if (si->second.total_len)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                    "this call needs a whole SRS, not a shard (a shard's circuit commitments are a collective: they need a "
+                    "communicator on the context, typlonk_comm_init; verification and batched proving run on one GPU)");
     CircuitEntry& ce = ci->second;
     const uint64_t n = 1ull << ce.log_n;
     if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
@@ -95,6 +101,41 @@ int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, 
         hit = ce.commitments.emplace(srs_id, c).first;
     }
     *out = &hit->second;
+    return TYPLONK_OK;
+}
+
+// A rank's share of the statement on an SRS SHARD: records 0..7 = its partial sums of the eight circuit commitments (the
+// MSMs sum only the shard's index range; run once per (circuit, SRS) on this rank, then cached -- what is cached is the
+// PARTIAL sum, the fold is the caller's), record 8 = SRS point 0 on the rank whose range starts at index 0 and the identity
+// elsewhere.  The fold of the nine records over the ranks is the whole-SRS statement.  No collective here: every failure is
+// local and the caller carries it into its fold.
+int circuit_statement_partial(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[9][12], uint8_t inf[9]) {
+    auto ci = ctx->circuits.find(circuit_id);
+    if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
+    auto si = ctx->srs.find(srs_id);
+    if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
+    CircuitEntry& ce = ci->second;
+    const uint64_t n = 1ull << ce.log_n;
+    if (si->second.total() < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
+    auto hit = ce.commitments.find(srs_id);
+    if (hit == ce.commitments.end()) {
+        CircuitEntry::Commitments c;
+        const void* ptrs[8];
+        size_t ms[8];
+        for (int k = 0; k < 8; ++k) {
+            ptrs[k] = ce.coef + (uint64_t)k * n;
+            ms[k] = n;
+        }
+        ProfilingOff prof_off(ctx);
+        const int rc = msm_batch(ctx, srs_id, ptrs, ms, 8, &c.xy[0][0], c.inf);
+        if (rc) return rc;
+        hit = ce.commitments.emplace(srs_id, c).first;
+    }
+    memcpy(xy, hit->second.xy, 8 * 96);
+    memcpy(inf, hit->second.inf, 8);
+    if (si->second.shard_first == 0 && si->second.len > 0) return typlonk_srs_download(ctx, srs_id, 0, 1, xy[8], &inf[8]);
+    memset(xy[8], 0, 96);
+    inf[8] = 1;
     return TYPLONK_OK;
 }
 }  // namespace tyh
@@ -346,6 +387,20 @@ void put_point(std::vector<uint8_t>& b, const uint64_t xy[12], uint8_t inf) {
 
 int typlonk_circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[8][12], uint8_t inf[8]) {
     if (!ctx || !xy || !inf) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (comm_folds(ctx, srs_id)) {
+        // a collective: ALWAYS one fold of 8 records, the rank's partial sums -- or flagged ones when anything failed here
+        uint64_t rec_xy[9][12];
+        uint8_t rec_inf[9];
+        int rc = TYPLONK_OK;
+        const hipError_t he = hipSetDevice(ctx->device);
+        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+        if (!rc) rc = circuit_statement_partial(ctx, srs_id, circuit_id, rec_xy, rec_inf);
+        rc = comm_fold(ctx, &rec_xy[0][0], rec_inf, 8, rc);
+        if (rc) return rc;
+        memcpy(xy, rec_xy, 8 * 96);
+        memcpy(inf, rec_inf, 8);
+        return TYPLONK_OK;
+    }
     HIPCHK(hipSetDevice(ctx->device));
     const CircuitEntry::Commitments* c = nullptr;
     const int rc = circuit_commitments(ctx, srs_id, circuit_id, &c);
@@ -627,6 +682,30 @@ int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t cou
 int typlonk_circuit_vk(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4],
                        const uint64_t g2s_xy[24], typlonk_vk* vk) {
     if (!ctx || !cosets || !g2s_xy || !vk) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (comm_folds(ctx, srs_id)) {
+        // a collective: ALWAYS one fold of 9 records (the eight partial sums and the P0 record), flagged when anything failed here
+        uint64_t rec_xy[9][12];
+        uint8_t rec_inf[9];
+        int rc = TYPLONK_OK;
+        const hipError_t he = hipSetDevice(ctx->device);
+        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+        P::G2Affine g2s;
+        if (!rc && !g2s_load(g2s_xy, &g2s)) rc = fail(ctx, TYPLONK_ERR_INVALID_ARG, "g2s is not a point of the twist in canonical coordinates");
+        if (!rc) rc = circuit_statement_partial(ctx, srs_id, circuit_id, rec_xy, rec_inf);
+        rc = comm_fold(ctx, &rec_xy[0][0], rec_inf, 9, rc);
+        if (rc) return rc;
+        typlonk_vk out;
+        memset(&out, 0, sizeof(out));
+        out.log_n = ctx->circuits.at(circuit_id).log_n;
+        memcpy(out.cosets, cosets, sizeof(out.cosets));
+        memcpy(out.commit_xy, rec_xy, sizeof(out.commit_xy));
+        memcpy(out.commit_inf, rec_inf, sizeof(out.commit_inf));
+        memcpy(out.srs0_xy, rec_xy[8], sizeof(out.srs0_xy));
+        out.srs0_inf = rec_inf[8];
+        memcpy(out.g2s_xy, g2s_xy, sizeof(out.g2s_xy));
+        *vk = out;
+        return TYPLONK_OK;
+    }
     HIPCHK(hipSetDevice(ctx->device));
     P::G2Affine g2s;
     if (!g2s_load(g2s_xy, &g2s)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "g2s is not a point of the twist in canonical coordinates");

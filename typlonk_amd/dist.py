@@ -130,6 +130,18 @@ class ShardedMsm:
         self.ctx.srs_set_shard(self.sid, self.lo, self.total_len)
         return self.sid
 
+    def load_srs_compressed(self, data, skip_subgroup: bool = False):
+        """this rank's slice of a compressed SRS (48 bytes per point, total_len points): only bytes [48 lo, 48 hi) are
+        decoded -- on the device, subgroup-checked unless skipped -- and the shard is set.  Rank 0's slice holds SRS point 0,
+        which the compact shape's statement needs (it reaches the other ranks in the first fold of a proof)."""
+        from .capi import G1_BYTES
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+        if a.size != self.total_len * G1_BYTES:
+            raise ValueError(f"load_srs_compressed: {self.total_len} points of {G1_BYTES} bytes expected, got {a.size} bytes")
+        self.sid = self.ctx.srs_load_compressed(a[self.lo * G1_BYTES:self.hi * G1_BYTES], skip_subgroup)
+        self.ctx.srs_set_shard(self.sid, self.lo, self.total_len)
+        return self.sid
+
     def msm_local_devptr(self, d_scalars: int, m: int):
         """this rank's partial sum of an m-term MSM; d_scalars = device address of coefficient 0 of the full
         vector (a rank holding only its slice passes slice_address - 32 * lo; nothing outside the slice is read)"""
@@ -177,3 +189,19 @@ class ShardedProver:
         """typlonk_prove on the shard: the library folds every round's commitments itself (needs the native comm)"""
         assert self.sh.native or self.sh.world == 1
         return self.sh.ctx.prove_native(self.sh.sid, circuit, wire_evals, pi_evals, cosets)
+
+    def prove_compact(self, circuit: int, wire_evals, pi=None, pi_len=None, cosets=None):
+        """typlonk_prove_compact on the shard: four collectives per proof (12, 1, 3 and 2 records) inside the library, the
+        same compact proof on every rank as from one GPU holding the whole SRS (needs the native comm)"""
+        assert self.sh.native or self.sh.world == 1
+        return self.sh.ctx.prove_compact(self.sh.sid, circuit, wire_evals, pi, pi_len, cosets)
+
+    def prove_compact_host(self, circuit: int, wire_evals_host, pi=None, cosets=None):
+        """the same with the columns in host memory (typlonk_prove_compact_host)"""
+        assert self.sh.native or self.sh.world == 1
+        return self.sh.ctx.prove_compact_host(self.sh.sid, circuit, wire_evals_host, pi, cosets)
+
+    def circuit_vk(self, circuit: int, cosets, g2s_xy):
+        """the verifying key on the shard: a collective every rank calls (one fold of 9 records); needs the native comm"""
+        assert self.sh.native or self.sh.world == 1
+        return self.sh.ctx.circuit_vk(self.sh.sid, circuit, cosets, g2s_xy)

@@ -84,6 +84,18 @@ class Context {
     Context(const Context&) = delete;
     Context& operator=(const Context&) = delete;
     typlonk_ctx* raw() const { return ctx_; }
+    // ---- multi-GPU: one process per GPU, the library's own exchange (include/typlonk.h, typlonk_comm_*) ----
+    // rank 0 creates the rendezvous id and hands its bytes to the other ranks by whatever channel the host program has
+    static std::array<uint8_t, TYPLONK_COMM_ID_BYTES> comm_unique_id() {
+        std::array<uint8_t, TYPLONK_COMM_ID_BYTES> id{};
+        check(typlonk_comm_unique_id(id.data()));
+        return id;
+    }
+    // collective: returns once all `world` ranks have called it
+    void comm_init(const std::array<uint8_t, TYPLONK_COMM_ID_BYTES>& id, int rank, int world) const {
+        check(typlonk_comm_init(ctx_, id.data(), rank, world), ctx_);
+    }
+    void comm_destroy() const { check(typlonk_comm_destroy(ctx_), ctx_); }
 
    private:
     typlonk_ctx* ctx_ = nullptr;
@@ -250,6 +262,22 @@ class Srs {
         r.has_g2_ = true;
         return r;
     }
+    // Multi-GPU: this rank's slice [first, first + count) of the same SRS (typlonk_srs_set_shard).  On a context with a
+    // communicator (Context::comm_init) plonk::CompiledCircuit's constructor, verifying_key() and prove_compact() are then
+    // COLLECTIVES every rank must call in the same order; each returns what one GPU holding the whole SRS returns.
+    static Srs from_secret_shard(const Context& ctx, const Fr& s, size_t gates, size_t first, size_t count) {
+        Srs r(ctx);
+        r.len_ = gates + 3;
+        r.local_len_ = count;
+        r.sharded_ = true;
+        check(typlonk_srs_generate(ctx.raw(), s.limbs(), first, count, &r.id_), ctx.raw());
+        check(typlonk_srs_set_shard(ctx.raw(), r.id_, first, r.len_), ctx.raw());
+        r.g2_ = pairing::g2_generator();
+        r.g2s_ = pairing::g2_mul(r.g2_, s.v);
+        r.has_g2_ = true;
+        return r;
+    }
+    bool sharded() const { return sharded_; }
     // an SRS loaded from points brings its G2 pair along (needed by KzgScheme::verify only)
     void set_g2(const pairing::G2Affine& g2, const pairing::G2Affine& g2s) {
         g2_ = g2;
@@ -276,21 +304,26 @@ class Srs {
         check(typlonk_srs_load(ctx.raw(), xy.data(), inf.data(), pts.size(), &r.id_), ctx.raw());
         return r;
     }
-    Srs(Srs&& o) noexcept : ctx_(o.ctx_), id_(o.id_), len_(o.len_), g2_(o.g2_), g2s_(o.g2s_), has_g2_(o.has_g2_) { o.id_ = 0; }
+    Srs(Srs&& o) noexcept
+        : ctx_(o.ctx_), id_(o.id_), len_(o.len_), local_len_(o.local_len_), sharded_(o.sharded_), g2_(o.g2_), g2s_(o.g2s_),
+          has_g2_(o.has_g2_) {
+        o.id_ = 0;
+    }
     Srs(const Srs&) = delete;
     ~Srs() {
         if (id_) typlonk_srs_free(ctx_->raw(), id_);
     }
-    size_t len() const { return len_; }
+    size_t len() const { return len_; }   // of the whole SRS, also on a shard
     // optional, once per SRS: fixed-base tables in HBM (window chosen by the library from the length when 0); every later
     // commitment over this SRS is faster, results are unchanged -- nothing in the reference corresponds to it
     void precompute(uint32_t window_bits = 0) const { check(typlonk_srs_precompute(ctx_->raw(), id_, window_bits), ctx_->raw()); }
-    std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>)
-        std::vector<uint64_t> xy(len_ * 12);
-        std::vector<uint8_t> inf(len_);
-        check(typlonk_srs_download(ctx_->raw(), id_, 0, len_, xy.data(), inf.data()), ctx_->raw());
-        std::vector<G1Point> out(len_);
-        for (size_t i = 0; i < len_; ++i) {
+    std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>); a shard: its slice
+        const size_t cnt = sharded_ ? local_len_ : len_;
+        std::vector<uint64_t> xy(cnt * 12);
+        std::vector<uint8_t> inf(cnt);
+        check(typlonk_srs_download(ctx_->raw(), id_, 0, cnt, xy.data(), inf.data()), ctx_->raw());
+        std::vector<G1Point> out(cnt);
+        for (size_t i = 0; i < cnt; ++i) {
             std::memcpy(out[i].xy, &xy[i * 12], 96);
             out[i].infinity = inf[i] != 0;
         }
@@ -310,7 +343,8 @@ class Srs {
     explicit Srs(const Context& c) : ctx_(&c) {}
     const Context* ctx_;
     uint32_t id_ = 0;
-    size_t len_ = 0;
+    size_t len_ = 0, local_len_ = 0;
+    bool sharded_ = false;
     pairing::G2Affine g2_{}, g2s_{};
     bool has_g2_ = false;
 };
@@ -495,7 +529,9 @@ class CompiledCircuit {
                 ptrs[k] = typlonk_buf_devptr(polys[k]);
                 lens[k] = n_;
             }
-            const int rc = typlonk_msm_g1_batch_devptr(c, srs.id(), ptrs, lens, 8, &xy[0][0], inf);
+            // (an SRS shard: the ranks' partial sums folded by the library, a collective -- the same points on every rank)
+            const int rc = srs.sharded() ? typlonk_msm_g1_sharded_batch_devptr(c, srs.id(), ptrs, lens, 8, &xy[0][0], inf)
+                                         : typlonk_msm_g1_batch_devptr(c, srs.id(), ptrs, lens, 8, &xy[0][0], inf);
             if (rc < 0) {
                 for (typlonk_buf* b : polys) typlonk_buf_free(c, b);
                 check(rc, c);
@@ -728,7 +764,7 @@ class CompiledCircuit {
 
     // ---- the compact proof shape (include/typlonk.h): batched openings, a transcript that binds the statement ----
     // The verifying key: all typlonk_verify_compact needs instead of this object (log n, the cosets, the eight commitments,
-    // SRS point 0 and the SRS's [s]G2).
+    // SRS point 0 and the SRS's [s]G2).  On a sharded SRS: a collective (one fold of 9 records), the whole-SRS key on every rank.
     typlonk_vk verifying_key() const {
         typlonk_ctx* c = srs_.ctx().raw();
         uint64_t g2s[24], ks[3][4];
@@ -740,7 +776,9 @@ class CompiledCircuit {
     }
     // A compact proof (typlonk_prove_compact_host): `advice` as for prove(); `public_inputs` = the statement's public values
     // themselves (at most n, not padded: their number is part of the statement).  A witness that does not satisfy the circuit
-    // throws, as prove() does.
+    // throws, as prove() does.  On a sharded SRS (kzg::Srs::from_secret_shard, Context::comm_init) the call is a collective:
+    // four folds of 12, 1, 3 and 2 records inside the library, the same proof on every rank as from one GPU with the whole SRS;
+    // a rank whose call fails throws its own error, its peers TYPLONK_ERR_COMM naming it.
     typlonk_proof_compact prove_compact(const std::vector<Fr> (&advice)[3], const std::vector<Fr>& public_inputs = {}) const {
         typlonk_ctx* c = srs_.ctx().raw();
         for (int i = 0; i < 3; ++i)
