@@ -237,6 +237,10 @@ int typlonk_ntt_fr_batch_devptr(typlonk_ctx* ctx, void* const* d_data, size_t co
  *   ntt_scratch (a 2^25 / 2^26 batch)      1.0 GiB    1.0 GiB    2.0 GiB
  *   SRS of n + 3 points with c = 20 tables 6.5 GiB   13.0 GiB   26.0 GiB   (13 x 128 B per point)
  *   total                                 18.8 GiB   36.5 GiB   73.0 GiB   plus twiddle / coset tables and MSM workspaces
+ *   check cache (5 n Fr + 12 n B)          0.7 GiB    1.3 GiB    2.7 GiB   per circuit, only once typlonk_witness_check /
+ *                                                                           typlonk_circuit_permutation has run on it: the
+ *                                                                           selector evaluations and the 3n-entry permutation
+ *                                                                           (160 MiB + 12 MiB at 2^20); not in the total
  * typlonk_prove_batch keeps one wave's arena in prover_mem instead (39 n Fr per proof in flight, one proof per wave here):
  *   prover_mem (39 n Fr)                   4.9 GiB    9.8 GiB   19.5 GiB   (quot_ext is not used by a batch)
  *   ops_tmp (8 n / 2048 Fr) + slots        4 MiB      8 MiB     16 MiB
@@ -556,6 +560,63 @@ int typlonk_verify_compact(typlonk_ctx* ctx, const typlonk_vk* vk, const typlonk
  * its points and evaluations, the vk and the public inputs.  pi_len > 2^log_n returns TYPLONK_ERR_LENGTH. */
 int typlonk_compact_challenges(const typlonk_vk* vk, const typlonk_proof_compact* proof, const uint64_t* pi, size_t pi_len,
                                uint64_t out[5][4]);
+
+/* ---- witness check: which gate rows and which copy constraints does a witness fail? -------------------------------------
+ * The provers report an unsatisfied witness as TYPLONK_ERR_UNSATISFIED, after the whole proof has been computed, from one
+ * probabilistic test (r(zeta) != 0) that names no row; the reference panics in vanishes() or emits a proof its own verifier
+ * rejects (plonk/src/proof.rs:234-235, 504-507).  The calls below read the columns once, need no SRS and no communicator, are
+ * never a collective (everything they read is replicated, so they work on a sharded context too), are exact, and may be made
+ * while a round-by-round prover is open (they touch none of its arena).  Work runs on the context's stream; the calls block.
+ * Cells are flat indices x = col * n + row, col in {0, 1, 2} (Tag::to_index, permutation/src/lib.rs).
+ * Kept with the circuit after the first call (freed by typlonk_circuit_free / typlonk_destroy): the permutation (3n uint32) with
+ * the cosets it was recovered for -- a call with other cosets recovers it again -- and the five selector columns as evaluations
+ * (5n Fr, one batch of five forward transforms of the coefficient copies typlonk_circuit_load keeps). */
+#define TYPLONK_CELL_NONE 0xffffffffu
+/* The successor map of the copy-constraint permutation, recovered from the circuit's sigma columns (compiled by
+ * permutation/src/lib.rs:101-128 into field values, which is all typlonk_circuit_load sees):
+ * perm[x] = y  iff  sigma_col(x)(w^row(x)) = k_col(y) * w^row(y).  perm: 3n entries or NULL.
+ * *defects = number of cells whose sigma value is no cell id (perm[x] = TYPLONK_CELL_NONE)
+ *          + number of cells that are the image of != 1 cells.  0 = sigma is a permutation of the cells.
+ * One thread per cell: the coset by u = sigma / k_i, u^n = 1; the row by Pohlig-Hellman over the order-2^log_n subgroup, about
+ * log_n^2 / 2 + 4 log_n field products per cell.  Setup-time work, once per (circuit, cosets).  A coset that is not a canonical
+ * residue returns TYPLONK_ERR_INVALID_ARG. */
+int typlonk_circuit_permutation(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t cosets[3][4],
+                                uint32_t* perm, uint64_t* defects);
+
+typedef struct typlonk_witness_report {
+    uint64_t gate_failures;  /* rows j with q_l a + q_r b - q_o c + q_m a b + q_c + PI != 0 at w^j (proof.rs:317-320)      */
+    uint64_t copy_failures;  /* cells x whose value differs (mod r) from the value of perm[x]                              */
+    uint32_t gate_listed, copy_listed;  /* min(failures, cap)                                                              */
+} typlonk_witness_report;
+
+/* `count` witnesses of one circuit.  wire_evals proof-major as typlonk_prove_batch; pi / pi_len per witness as
+ * typlonk_prove_batch_compact (rows pi_len.. of the public-input column are zero; pi_len = n covers typlonk_prove's
+ * full column; pi_len may be NULL = all 0).  gate_rows: count*cap; copy_cells: count*cap*2 (x, perm[x]); both may be NULL
+ * when cap = 0.  Witness k's lists start at gate_rows[k * cap] and copy_cells[2 * k * cap].
+ *   return value  reports only bad arguments and device failures; a failing witness is data in its report, as status[k] is
+ *                 for the batch provers.  count = 0 is a no-op.  TYPLONK_ERR_INVALID_ARG: a null argument, an unknown circuit,
+ *                 a null column, pi_len[k] != 0 with pi or pi[k] NULL.  TYPLONK_ERR_RANGE: a wire buffer shorter than n or a
+ *                 pi buffer shorter than pi_len[k].  TYPLONK_ERR_LENGTH: pi_len[k] > n.  A refused call leaves every output
+ *                 as it was.
+ *   malformed     a circuit with defects != 0 (typlonk_circuit_permutation) returns TYPLONK_ERR_INVALID_ARG and
+ *                 typlonk_last_error names the lowest defective cell.
+ *   lists         the lowest failing rows / cells in ascending order, whatever the launch geometry; the counts are totals:
+ *                 cap truncates the lists, not the counts.  Entries beyond gate_listed / copy_listed are not written.
+ *   equality      of residues mod r, not of bits: a cell holding v + r in its limbs equals one holding v.
+ *   agreement     gate_failures == 0 && copy_failures == 0 exactly when the witness satisfies the circuit, which is when the
+ *                 provers do not return TYPLONK_ERR_UNSATISFIED (up to their soundness error).
+ * One thread per row, the witness in the grid's second dimension; failure flags -> wave ballots -> block counts -> one
+ * exclusive scan over the blocks -> an ordered write of the first cap entries. */
+int typlonk_witness_check(typlonk_ctx* ctx, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
+                          const typlonk_buf* const* pi, const size_t* pi_len, size_t count,
+                          const uint64_t cosets[3][4], uint32_t cap,
+                          typlonk_witness_report* reports, uint32_t* gate_rows, uint32_t* copy_cells);
+/* The same with the columns in HOST memory: wire_evals[3 k + i] holds `rows` Fr elements, and rows must equal the circuit's n
+ * (else TYPLONK_ERR_LENGTH); pi[k] holds pi_len[k] values. */
+int typlonk_witness_check_host(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t* const* wire_evals, size_t rows,
+                               const uint64_t* const* pi, const size_t* pi_len, size_t count,
+                               const uint64_t cosets[3][4], uint32_t cap,
+                               typlonk_witness_report* reports, uint32_t* gate_rows, uint32_t* copy_cells);
 
 /* ---- wire format: compact proofs, verifying keys and SRS points as bytes, with compressed points ------------------------
  * Everything above works on in-memory arkworks limbs that the caller is trusted to have formed.  The byte forms below are

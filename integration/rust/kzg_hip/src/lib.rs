@@ -34,6 +34,8 @@ pub type G1Point = G1Affine;
 pub type Poly = DensePolynomial<Fr>;
 /// `TYPLONK_VERIFY_PI_AS_PROVER` of include/typlonk.h (a flag of `typlonk_verify`)
 pub const VERIFY_PI_AS_PROVER: u32 = 1;
+/// `TYPLONK_CELL_NONE` of include/typlonk.h (`circuit_permutation`: a sigma value that is the id of no cell)
+pub const CELL_NONE: u32 = 0xffff_ffff;
 /// `TYPLONK_DECODE_SKIP_SUBGROUP` of include/typlonk.h (a flag of the `*_from_bytes` / `*_compressed` calls)
 pub const DECODE_SKIP_SUBGROUP: u32 = 1;
 
@@ -465,6 +467,53 @@ impl Backend {
         out.into_iter().zip(status).collect()
     }
 
+    /// `typlonk_circuit_permutation`: the successor map of the 3n cells (flat index col * n + row) recovered from the
+    /// circuit's sigma columns -- `CELL_NONE` where a sigma value is the id of no cell -- and the number of
+    /// defects; 0 = sigma is a permutation of the cells.  A lint to run once after `load_circuit`; cached with the circuit.
+    pub fn circuit_permutation(&self, circuit: CircuitHandle, cosets: [Fr; 3]) -> (Vec<u32>, u64) {
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut perm = vec![0u32; 3usize << circuit.log_n];
+        let mut defects = 0u64;
+        self.check(unsafe { ffi::typlonk_circuit_permutation(self.ctx, circuit.id, k.as_ptr(), perm.as_mut_ptr(), &mut defects) });
+        (perm, defects)
+    }
+
+    /// `typlonk_witness_check_host`: which gate rows and which copy constraints each witness fails -- exact, no SRS, a
+    /// fraction of a proof's cost; what to call before a prover on witnesses of unknown quality.  `wire_evals` and
+    /// `public_inputs` as for `prove_batch_compact`.  Per witness: the two failure counts (totals), the lowest failing rows
+    /// and the lowest failing cells as (x, perm[x]) over flat cells col * n + row, at most `cap` of each.  A witness
+    /// satisfies the circuit exactly when both counts are 0.  Panics on a malformed circuit (sigma is no permutation).
+    pub fn check_witnesses(&self, circuit: CircuitHandle, wire_evals: &[[&[Fr]; 3]], public_inputs: &[&[Fr]], cosets: [Fr; 3],
+                           cap: u32) -> Vec<WitnessReport> {
+        assert!(public_inputs.is_empty() || public_inputs.len() == wire_evals.len(), "one public-input list per witness");
+        let count = wire_evals.len();
+        let rows = if count == 0 { 0 } else { wire_evals[0][0].len() };   // the library checks it against the circuit's n
+        assert!(wire_evals.iter().all(|cols| cols.iter().all(|c| c.len() == rows)), "columns of equal length");
+        let flat = |c: &[Fr]| -> Vec<u64> { c.iter().flat_map(|e| fr_limbs(e)).collect() };
+        let w: Vec<Vec<u64>> = wire_evals.iter().flat_map(|cols| cols.iter().map(|c| flat(c))).collect();
+        let wp: Vec<*const u64> = w.iter().map(|c| c.as_ptr()).collect();
+        let pi: Vec<Vec<u64>> = public_inputs.iter().map(|c| flat(c)).collect();
+        let pp: Vec<*const u64> = pi.iter().map(|c| if c.is_empty() { ptr::null() } else { c.as_ptr() }).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|c| c.len()).collect();
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut reports: Vec<ffi::TyplonkWitnessReport> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+        let cap_n = cap as usize;
+        let mut gate = vec![0u32; (count * cap_n).max(1)];
+        let mut copy = vec![0u32; (2 * count * cap_n).max(1)];
+        self.check(unsafe {
+            ffi::typlonk_witness_check_host(self.ctx, circuit.id, wp.as_ptr(), rows,
+                                            if pp.is_empty() { ptr::null() } else { pp.as_ptr() },
+                                            if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, count, k.as_ptr(), cap,
+                                            reports.as_mut_ptr(), gate.as_mut_ptr(), copy.as_mut_ptr())
+        });
+        reports.iter().enumerate().map(|(i, r)| WitnessReport {
+            gate_failures: r.gate_failures,
+            copy_failures: r.copy_failures,
+            gate_rows: gate[i * cap_n..i * cap_n + r.gate_listed as usize].to_vec(),
+            copy_cells: (0..r.copy_listed as usize).map(|j| (copy[2 * (i * cap_n + j)], copy[2 * (i * cap_n + j) + 1])).collect(),
+        }).collect()
+    }
+
     /// `typlonk_verify_compact`: a batch of compact proofs against a verifying key; needs no SRS and no circuit on this
     /// backend.  `public_inputs`: empty, or one list of public values per proof.
     pub fn verify_compact(&self, vk: &ffi::TyplonkVk, proofs: &[ffi::TyplonkProofCompact], public_inputs: &[Vec<Fr>]) -> Vec<bool> {
@@ -563,6 +612,19 @@ impl Backend {
 }
 
 /// `typlonk_proof` -> the pieces of the reference's `Proof` (plonk/src/proof.rs:65-95)
+/// One witness's report from `Backend::check_witnesses`.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct WitnessReport {
+    pub gate_failures: u64,
+    pub copy_failures: u64,
+    pub gate_rows: Vec<u32>,
+    pub copy_cells: Vec<(u32, u32)>,
+}
+
+impl WitnessReport {
+    pub fn satisfied(&self) -> bool { self.gate_failures == 0 && self.copy_failures == 0 }
+}
+
 pub struct ProofParts {
     pub commitments: [G1Point; 3],          // [a], [b], [c]
     pub z_commitment: G1Point,               // permutation.commitment

@@ -36,6 +36,7 @@ SYMBOLS = [
     "typlonk_g1_compress", "typlonk_g1_decompress", "typlonk_srs_load_compressed", "typlonk_srs_download_compressed",
     "typlonk_proof_compact_to_bytes", "typlonk_vk_to_bytes", "typlonk_vk_from_bytes", "typlonk_proof_compact_from_bytes",
     "typlonk_verify_compact_bytes",
+    "typlonk_circuit_permutation", "typlonk_witness_check", "typlonk_witness_check_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -90,6 +91,14 @@ class Vk(C.Structure):
     """typlonk_vk: the verifying key of the compact proof shape"""
     _fields_ = [("log_n", C.c_uint32), ("cosets", (C.c_uint64 * 4) * 3), ("commit_xy", (C.c_uint64 * 12) * 8),
                 ("commit_inf", C.c_uint8 * 8), ("srs0_xy", C.c_uint64 * 12), ("srs0_inf", C.c_uint8), ("g2s_xy", C.c_uint64 * 24)]
+
+
+class WitnessReport(C.Structure):
+    """typlonk_witness_report"""
+    _fields_ = [("gate_failures", C.c_uint64), ("copy_failures", C.c_uint64), ("gate_listed", C.c_uint32), ("copy_listed", C.c_uint32)]
+
+
+CELL_NONE = 0xFFFFFFFF   # TYPLONK_CELL_NONE
 
 
 class ProofCompact(C.Structure):
@@ -328,6 +337,14 @@ def load_library() -> C.CDLL:
         lib.typlonk_proof_compact_from_bytes.argtypes = [vp, u8p, C.c_size_t, C.c_uint32, C.POINTER(ProofCompact), u32p]
         lib.typlonk_verify_compact_bytes.argtypes = [vp, C.POINTER(Vk), u8p, C.c_size_t, C.POINTER(u64p), C.POINTER(C.c_size_t),
                                                      C.c_uint32, u8p]
+    if hasattr(lib, "typlonk_witness_check") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_circuit_permutation.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), u32p, C.POINTER(C.c_uint64)]
+        lib.typlonk_witness_check.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t,
+                                              C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32, C.POINTER(WitnessReport), u32p, u32p]
+        lib.typlonk_witness_check_host.argtypes = [vp, C.c_uint32, C.POINTER(u64p), C.c_size_t, C.POINTER(u64p),
+                                                   C.POINTER(C.c_size_t), C.c_size_t, C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32,
+                                                   C.POINTER(WitnessReport), u32p, u32p]
     _lib = lib
     return lib
 
@@ -1128,6 +1145,69 @@ class Context:
         self._chk(self.lib.typlonk_prove_batch_compact_host(self.h, sid, circuit, w, keep[0].shape[0] if keep else 0, pip, lens, k,
                                                             C.byref(_cosets_arg(cosets)), out, st))
         return [compact_dict(out[i]) for i in range(k)], [int(st[i]) for i in range(k)]
+
+    # ---- witness check --------------------------------------------------------------------
+    def circuit_permutation(self, circuit: int, n: int, cosets):
+        """typlonk_circuit_permutation: (perm, defects) -- the 3n-entry successor map over flat cells col * n + row recovered
+        from the circuit's sigma columns (CELL_NONE where a sigma value is no cell id), and the number of defects"""
+        perm = np.empty(3 * n, dtype=np.uint32)
+        defects = C.c_uint64()
+        self._chk(self.lib.typlonk_circuit_permutation(self.h, circuit, C.byref(_cosets_arg(cosets)),
+                                                       perm.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(defects)))
+        return perm, int(defects.value)
+
+    @staticmethod
+    def _witness_reports(k, cap, reports, gate, copy):
+        out = []
+        for i in range(k):
+            r = reports[i]
+            out.append({"gate_failures": int(r.gate_failures), "copy_failures": int(r.copy_failures),
+                        "gate_rows": [int(x) for x in gate[i * cap:i * cap + r.gate_listed]],
+                        "copy_cells": [(int(copy[2 * (i * cap + j)]), int(copy[2 * (i * cap + j) + 1])) for j in range(r.copy_listed)]})
+        return out
+
+    def witness_check(self, circuit: int, wire_evals, pi=None, pi_len=None, cosets=None, cap: int = 16):
+        """typlonk_witness_check: wire_evals / pi / pi_len as prove_batch_compact.  One dict per witness: gate_failures,
+        copy_failures (totals), gate_rows (the lowest failing rows, at most cap) and copy_cells (the lowest failing cells as
+        (x, perm[x]) pairs, at most cap).  A witness satisfies the circuit exactly when both counts are 0."""
+        k = len(wire_evals)
+        w = (C.c_void_p * max(3 * k, 1))(*[b.handle.value for cols in wire_evals for b in cols])
+        pip = None
+        if pi is not None:
+            pip = (C.c_void_p * max(k, 1))(*[b.handle.value if b is not None else None for b in pi])
+        if pi_len is None and pi is not None:
+            pi_len = [b.n if b is not None else 0 for b in pi]
+        lens = (C.c_size_t * max(k, 1))(*[int(x) for x in pi_len]) if pi_len is not None else None
+        reports = (WitnessReport * max(k, 1))()
+        gate = (C.c_uint32 * max(k * cap, 1))()
+        copy = (C.c_uint32 * max(2 * k * cap, 1))()
+        self._chk(self.lib.typlonk_witness_check(self.h, circuit, w, pip, lens, k, C.byref(_cosets_arg(cosets)), cap, reports,
+                                                 gate if cap else None, copy if cap else None))
+        return self._witness_reports(k, cap, reports, gate, copy)
+
+    def witness_check_host(self, circuit: int, wire_evals_host, pi=None, cosets=None, cap: int = 16):
+        """typlonk_witness_check_host: the columns are (rows, 4) u64 host arrays of equal length, one [a, b, c] list per witness;
+        pi = None or one entry per witness (None or an (l, 4) column of l public values).  Same result as witness_check."""
+        k = len(wire_evals_host)
+        keep = [np.ascontiguousarray(c, dtype=np.uint64) for cols in wire_evals_host for c in cols]
+        if any(c.ndim != 2 or c.shape[1] != 4 or c.shape != keep[0].shape for c in keep):
+            raise ValueError("witness_check_host needs (rows, 4) uint64 columns of equal length")
+        w = (C.POINTER(C.c_uint64) * max(3 * k, 1))(*[_u64p(c) for c in keep])
+        pip = lens = None
+        if pi is not None:
+            pis = [np.ascontiguousarray(c, dtype=np.uint64) if c is not None else None for c in pi]
+            if any(c is not None and (c.ndim != 2 or c.shape[1] != 4) for c in pis):
+                raise ValueError("pi entries must be (l, 4) uint64 columns")
+            keep += [c for c in pis if c is not None]
+            pip = (C.POINTER(C.c_uint64) * max(k, 1))(*[_u64p(c) if c is not None and c.shape[0] else None for c in pis])
+            lens = (C.c_size_t * max(k, 1))(*[c.shape[0] if c is not None else 0 for c in pis])
+        reports = (WitnessReport * max(k, 1))()
+        gate = (C.c_uint32 * max(k * cap, 1))()
+        copy = (C.c_uint32 * max(2 * k * cap, 1))()
+        self._chk(self.lib.typlonk_witness_check_host(self.h, circuit, w, keep[0].shape[0] if keep else 0, pip, lens, k,
+                                                      C.byref(_cosets_arg(cosets)), cap, reports, gate if cap else None,
+                                                      copy if cap else None))
+        return self._witness_reports(k, cap, reports, gate, copy)
 
     def circuit_load(self, log_n: int, selectors, sigma) -> int:
         sel = (C.c_void_p * 5)(*[b.handle.value for b in selectors])

@@ -118,12 +118,13 @@ void typlonk_destroy(typlonk_ctx* ctx) {
         (void)hipFree(kv.second.ext);
         (void)hipFree(kv.second.coef);
         (void)hipFree(kv.second.sig_ev);
+        circuit_check_release(kv.second);
     }
     for (auto& kv : ctx->tables) (void)hipFree(kv.second.d);
     if (ctx->eval_slots_host) (void)hipHostFree(ctx->eval_slots_host);
     if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
     for (DevBuf* b : {&ctx->srs_comb, &ctx->scal, &ctx->ntt_scratch, &ctx->ntt_io, &ctx->quot_ext, &ctx->quot_tab, &ctx->ops_tmp, &ctx->prover_mem, &ctx->eval_ws,
-                      &ctx->batch_tab}) release(*b);
+                      &ctx->batch_tab, &ctx->wc_ws, &ctx->wc_stage}) release(*b);
     for (MsmWs& ws : ctx->ws) {
         for (SortBufs& sb : ws.sb)
             for (DevBuf* b : sb.all()) release(*b);

@@ -6,6 +6,7 @@
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip)
+//   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -66,6 +67,13 @@ struct CircuitEntry {
         uint8_t inf[8];
     };
     std::map<uint32_t, Commitments> commitments;
+    // typlonk_circuit_permutation / typlonk_witness_check (witness_check.hip), built on first use:
+    uint32_t* perm = nullptr;       // 3n : successor map of the cells recovered from sig_ev (TYPLONK_CELL_NONE: no cell id)
+    uint64_t perm_cosets[3][4] = {};  //      the cosets it was recovered for (other cosets rebuild it)
+    bool perm_ready = false;
+    uint64_t perm_defects = 0;      //      cells without an image + cells that are the image of != 1 cells
+    uint32_t perm_first_bad = 0;    //      the lowest such cell
+    Fr* sel_ev = nullptr;           // 5n : selector evaluations over the domain
 };
 
 struct ProfStage {
@@ -179,6 +187,7 @@ struct typlonk_ctx {
     bool msm_rc4 = false;          // always the four-launch row/column reduction
     // NTT
     tyh::DevBuf ntt_scratch, ntt_io, quot_ext, quot_tab, ops_tmp, prover_mem;
+    tyh::DevBuf wc_ws, wc_stage;   // typlonk_witness_check: masks, counts and lists of a launch; the host form's staged columns
     tyh::DevBuf eval_ws;           // typlonk_poly_eval_dev: points, results and chunk partials (poly_eval.hip)
     tyh::DevBuf batch_tab;         // typlonk_prove_batch: per-proof scalars and item tables of a wave (device copy of batch_host)
     void* batch_host = nullptr;    // pinned staging of batch_tab (PROVE_BATCH_TAB_BYTES)
@@ -364,6 +373,10 @@ int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, cons
 // pi_len[k] > n or a null pi[k] with pi_len[k] != 0, a g2s off the twist, a vk point off the curve, a non-canonical coset
 // (typlonk_verify_compact_bytes judges its arguments by the same function, before it decodes anything)
 int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len);
+
+// ---- witness_check.hip ----------------------------------------------------------------------------------------------
+// frees a circuit's recovered permutation and selector evaluations (typlonk_circuit_free, typlonk_destroy)
+void circuit_check_release(CircuitEntry& e);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------
 void comm_release(typlonk_ctx* ctx);

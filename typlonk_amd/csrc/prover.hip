@@ -95,6 +95,7 @@ int typlonk_circuit_free(typlonk_ctx* ctx, uint32_t circuit_id) {
     HIPCHK(hipFree(it->second.ext));
     HIPCHK(hipFree(it->second.coef));
     HIPCHK(hipFree(it->second.sig_ev));
+    circuit_check_release(it->second);
     ctx->circuits.erase(it);
     return TYPLONK_OK;
 }

@@ -824,6 +824,35 @@ class CompiledCircuit {
         if (status) *status = st;
         return out;
     }
+    // Which gate rows and which copy constraints does a witness fail (typlonk_witness_check_host)?  Exact, no SRS work, a
+    // fraction of a proof's cost: what to call before prove() on a witness of unknown quality -- the reference only panics in
+    // vanishes() (proof.rs:504-507).  gate_rows / copy_cells hold the lowest failing rows and cells (x, perm[x]; flat cells
+    // col * n + row), at most `cap` each; the counts are totals.  Throws for a malformed circuit (sigma is no permutation).
+    struct WitnessReport {
+        uint64_t gate_failures = 0, copy_failures = 0;
+        std::vector<uint32_t> gate_rows;
+        std::vector<std::array<uint32_t, 2>> copy_cells;
+        bool satisfied() const { return gate_failures == 0 && copy_failures == 0; }
+    };
+    WitnessReport check_witness(const std::vector<Fr> (&advice)[3], const std::vector<Fr>& public_inputs = {}, uint32_t cap = 16) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        for (int i = 0; i < 3; ++i)
+            if (advice[i].size() != n_) throw std::runtime_error("witness column must hold n values");
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        const uint64_t* wc[3] = {advice[0][0].limbs(), advice[1][0].limbs(), advice[2][0].limbs()};
+        const uint64_t* pc[1] = {public_inputs.empty() ? nullptr : public_inputs[0].limbs()};
+        const size_t lens[1] = {public_inputs.size()};
+        typlonk_witness_report rep{};
+        std::vector<uint32_t> gate(cap), copy(2 * (size_t)cap);
+        check(typlonk_witness_check_host(c, circuit_, wc, n_, pc, lens, 1, ks, cap, &rep, gate.data(), copy.data()), c);
+        WitnessReport out;
+        out.gate_failures = rep.gate_failures;
+        out.copy_failures = rep.copy_failures;
+        out.gate_rows.assign(gate.begin(), gate.begin() + rep.gate_listed);
+        for (uint32_t k = 0; k < rep.copy_listed; ++k) out.copy_cells.push_back({copy[2 * k], copy[2 * k + 1]});
+        return out;
+    }
 
    private:
     void g2s_limbs(uint64_t g2s[24]) const {
