@@ -111,17 +111,20 @@ def squaring_chain(log_n: int, x0: int = 3, blinders=None):
     return n, cols, q, perm
 
 
-def compile_permutation(perm, n, log_n):
-    """per cell (tag, value): tag = k_i w^j, value = k_i' w^j' of the cell it maps to (lib.rs:108-119)"""
+def compile_permutation(perm, n, log_n, cosets=None):
+    """per cell (tag, value): tag = k_i w^j, value = k_i' w^j' of the cell it maps to (lib.rs:108-119).  cosets: the
+    three k_i (default COSETS), as in every function below that takes them"""
+    cosets = COSETS if cosets is None else cosets
     w = O.domain_root(log_n)
     roots = [pow(w, j, R) for j in range(n)]
-    ids = [[COSETS[i] * roots[j] % R for j in range(n)] for i in range(3)]
-    sig = [[COSETS[perm[j + i * n] // n] * roots[perm[j + i * n] % n] % R for j in range(n)] for i in range(3)]
+    ids = [[cosets[i] * roots[j] % R for j in range(n)] for i in range(3)]
+    sig = [[cosets[perm[j + i * n] // n] * roots[perm[j + i * n] % n] % R for j in range(n)] for i in range(3)]
     return ids, sig
 
 
-def grand_product(cols, ids, sig, beta, gamma, n):
-    """CompiledPermutation::prove: n + 1 values starting at 1 (one field division per cell)"""
+def grand_product(cols, ids, sig, beta, gamma, n, cosets=None):
+    """CompiledPermutation::prove: n + 1 values starting at 1 (one field division per cell).  The cosets are in `ids` and
+    `sig` already (compile_permutation); the argument is accepted so that a caller can pass one set everywhere."""
     acc = [1]
     state = 1
     for j in range(n):
@@ -135,14 +138,15 @@ def grand_product(cols, ids, sig, beta, gamma, n):
     return acc
 
 
-def quotient_polynomial(log_n, wires, z, zw, q, sigma_polys, alpha, beta, gamma, pi):
+def quotient_polynomial(log_n, wires, z, zw, q, sigma_polys, alpha, beta, gamma, pi, cosets=None):
     """plonk/src/proof.rs:292-375 with the reference's schoolbook products.  All arguments are
     coefficient vectors.  Returns (t, remainder); the reference discards the remainder."""
+    cosets = COSETS if cosets is None else cosets
     n = 1 << log_n
     a, b, c = wires
     line1 = p_add(p_add(p_add(p_sub(p_add(naive_mul(q["q_l"], a), naive_mul(q["q_r"], b)), naive_mul(q["q_o"], c)),
                               naive_mul(naive_mul(q["q_m"], a), b)), q["q_c"]), pi)
-    f = [p_add(w, trim([gamma, k * beta % R])) for w, k in zip(wires, COSETS)]
+    f = [p_add(w, trim([gamma, k * beta % R])) for w, k in zip(wires, cosets)]
     line2 = naive_mul(naive_mul(naive_mul(f[0], f[1]), f[2]), z)
     g = [p_add(p_add(w, p_scale(s, beta)), trim([gamma])) for w, s in zip(wires, sigma_polys)]
     line3 = naive_mul(naive_mul(naive_mul(g[0], g[1]), g[2]), zw)
@@ -211,13 +215,14 @@ def linearisation_poly(log_n, q, sigma_polys, cosets, adv, z_eval_w, z, challeng
     return p_sub(p_add(p_add(line1, p_scale(copy_constrain, alpha)), p_scale(line4, alpha * alpha % R)), line5)
 
 
-def prove(log_n, cols, q_evals, perm, pi_evals, challenges, zeta, commit):
+def prove(log_n, cols, q_evals, perm, pi_evals, challenges, zeta, commit, cosets=None):
     """plonk/src/proof.rs:96-194.  `commit(coeffs)` is the KZG commitment function (an MSM against the
     SRS).  Returns the proof elements in the order the reference produces them."""
+    cosets = COSETS if cosets is None else cosets
     n = 1 << log_n
     alpha, beta, gamma = challenges
     w = O.domain_root(log_n)
-    ids, sig = compile_permutation(perm, n, log_n)
+    ids, sig = compile_permutation(perm, n, log_n, cosets)
     wires = [O.interpolate(col, log_n) for col in cols]
     pi = O.interpolate(pi_evals, log_n)
     commitments = [commit(p) for p in wires]                                  # round1, :107-110
@@ -229,7 +234,7 @@ def prove(log_n, cols, q_evals, perm, pi_evals, challenges, zeta, commit):
     q = {k: O.interpolate(v, log_n) for k, v in q_evals.items()}
     sigma_polys = [O.interpolate(s, log_n) for s in sig]
     public_eval = O.poly_eval(pi, zeta)                                       # :138
-    (t, rem), _ = quotient_polynomial(log_n, wires, z, zw, q, sigma_polys, alpha, beta, gamma, pi)
+    (t, rem), _ = quotient_polynomial(log_n, wires, z, zw, q, sigma_polys, alpha, beta, gamma, pi, cosets)
     t_slices = slices(t, n)
 
     def open_(p, x):                                                          # kzg/src/lib.rs:55-64
@@ -240,7 +245,7 @@ def prove(log_n, cols, q_evals, perm, pi_evals, challenges, zeta, commit):
     adv = [o[1] for o in openings]
     z_open = open_(z, zeta)                                                   # :162
     zw_open = open_(z, zeta * w % R)                                          # :163
-    r = linearisation_poly(log_n, q, sigma_polys, COSETS, adv, zw_open[1], z, challenges, zeta, t_slices, public_eval)
+    r = linearisation_poly(log_n, q, sigma_polys, cosets, adv, zw_open[1], z, challenges, zeta, t_slices, public_eval)
     r_open = open_(r, zeta)                                                   # :175
     t_commit = [commit(s) for s in t_slices]                                  # :181
     return {"commit": commitments, "open": openings, "z_commit": z_commit, "z_open": z_open, "zw_open": zw_open,

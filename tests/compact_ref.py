@@ -73,28 +73,32 @@ def challenges(vk, proof, pi):
 
 
 # ---- the circuit and its verifying key ---------------------------------------------------------------------------------
-def setup(log_n, q_evals, perm, srs, g2s):
-    """the circuit polynomials and the verifying key: vk = log_n, cosets, the eight commitments, P0 = srs[0], [s]G2"""
+def setup(log_n, q_evals, perm, srs, g2s, cosets=None):
+    """the circuit polynomials and the verifying key: vk = log_n, cosets (default PO.COSETS), the eight commitments,
+    P0 = srs[0], [s]G2"""
+    cosets = PO.COSETS if cosets is None else cosets
     n = 1 << log_n
-    _, sig = PO.compile_permutation(perm, n, log_n)
+    _, sig = PO.compile_permutation(perm, n, log_n, cosets)
     q = {k: O.interpolate(v, log_n) for k, v in q_evals.items()}
     sigma = [O.interpolate(s, log_n) for s in sig]
     commit = lambda c: O.kzg_commit(srs, c)   # noqa: E731
     comms = [commit(q[k]) for k in ("q_l", "q_r", "q_o", "q_m", "q_c")] + [commit(s) for s in sigma]
-    vk = {"log_n": log_n, "cosets": list(PO.COSETS), "commitments": comms, "srs0": srs[0], "g2s": g2s}
+    vk = {"log_n": log_n, "cosets": list(cosets), "commitments": comms, "srs0": srs[0], "g2s": g2s}
     return {"q": q, "sigma": sigma, "perm": perm, "srs": srs, "vk": vk, "log_n": log_n}
 
 
 # ---- the prover -----------------------------------------------------------------------------------------------------------
-def prove(circ, cols, pi, forge=False):
+def prove(circ, cols, pi, forge=False, cosets=None):
     """A compact proof for witness columns `cols` (n evaluations each) and public values `pi` (pi_len <= n values).
     forge=True: a prover holding a witness that satisfies nothing tries the reference shape's forgery -- t = the constant
-    N(zeta*) / Z_H(zeta*) for the zeta* it can predict before committing to t -- which the compact transcript defeats."""
+    N(zeta*) / Z_H(zeta*) for the zeta* it can predict before committing to t -- which the compact transcript defeats.
+    cosets: the key's own by default (what setup() was given, PO.COSETS unless it was told otherwise)."""
+    cosets = circ["vk"]["cosets"] if cosets is None else cosets
     log_n, srs, q, sigma = circ["log_n"], circ["srs"], circ["q"], circ["sigma"]
     n = 1 << log_n
     w = O.domain_root(log_n)
     commit = lambda c: O.kzg_commit(srs, c)   # noqa: E731
-    ids, sig = PO.compile_permutation(circ["perm"], n, log_n)
+    ids, sig = PO.compile_permutation(circ["perm"], n, log_n, cosets)
     wires = [O.interpolate(c, log_n) for c in cols]
     pi_poly = O.interpolate(list(pi) + [0] * (n - len(pi)), log_n)
     tr = Transcript(statement_digest(circ["vk"], pi))
@@ -109,9 +113,9 @@ def prove(circ, cols, pi, forge=False):
     alpha = tr.squeeze(b"a")
     if forge:
         zeta_guess = tr.squeeze(b"z")   # what the reference's transcript would give: t is not hashed there
-        t_slices = forged_quotient(log_n, q, sigma, wires, z, pi_poly, (alpha, beta, gamma), zeta_guess)
+        t_slices = forged_quotient(log_n, q, sigma, wires, z, pi_poly, (alpha, beta, gamma), zeta_guess, cosets)
     else:
-        (t, _), _ = PO.quotient_polynomial(log_n, wires, z, zw, q, sigma, alpha, beta, gamma, pi_poly)
+        (t, _), _ = PO.quotient_polynomial(log_n, wires, z, zw, q, sigma, alpha, beta, gamma, pi_poly, cosets)
         t_slices = PO.slices(t, n)
     t_c = [commit(s) for s in t_slices]
     tr.points(*t_c)
@@ -120,7 +124,7 @@ def prove(circ, cols, pi, forge=False):
     evals = adv + [O.poly_eval(z, zeta), O.poly_eval(z, zeta * w % R), O.poly_eval(sigma[0], zeta), O.poly_eval(sigma[1], zeta)]
     tr.scalars(*evals)
     v = tr.squeeze(b"v")
-    r = PO.linearisation_poly(log_n, q, sigma, PO.COSETS, adv, evals[4], z, (alpha, beta, gamma), zeta, t_slices,
+    r = PO.linearisation_poly(log_n, q, sigma, cosets, adv, evals[4], z, (alpha, beta, gamma), zeta, t_slices,
                               O.poly_eval(pi_poly, zeta))
     w_z, _ = PO.batched_opening([wires[0], wires[1], wires[2], z, r, sigma[0], sigma[1]], v, zeta, commit)
     w_zw = commit(O.poly_div_linear(z, zeta * w % R)[0])
@@ -129,12 +133,13 @@ def prove(circ, cols, pi, forge=False):
             "r_zeta": O.poly_eval(r, zeta)}
 
 
-def forged_quotient(log_n, q, sigma, wires, z, pi_poly, ch, zeta):
+def forged_quotient(log_n, q, sigma, wires, z, pi_poly, ch, zeta, cosets=None):
     """the three slices of the constant t = N(zeta) / Z_H(zeta): r(zeta) = N(zeta) - Z_H(zeta) t(zeta) = 0 at this zeta"""
+    cosets = PO.COSETS if cosets is None else cosets
     n = 1 << log_n
     w = O.domain_root(log_n)
     adv = [O.poly_eval(p, zeta) for p in wires]
-    r0 = PO.linearisation_poly(log_n, q, sigma, PO.COSETS, adv, O.poly_eval(z, zeta * w % R), z, ch, zeta, [[], [], []],
+    r0 = PO.linearisation_poly(log_n, q, sigma, cosets, adv, O.poly_eval(z, zeta * w % R), z, ch, zeta, [[], [], []],
                                O.poly_eval(pi_poly, zeta))
     t0 = O.poly_eval(r0, zeta) * pow((pow(zeta, n, R) - 1) % R, -1, R) % R
     return [[t0], [], []]
