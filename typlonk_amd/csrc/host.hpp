@@ -3,7 +3,8 @@
 //   ntt_host.hip  NTT planning (tables, pass decomposition) + typlonk_ntt_*
 //   msm_host.hip  MSM staging (sort / accumulate / reduce launches, lanes of a batch, host finish) + SRS + typlonk_msm_*
 //   comm.hip      RCCL exchange behind the C ABI
-//   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove
+//   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove; the steps it shares with prove_batch.hip
+//                 (declared below: coset_g, quotient_domain, round3_openings, lin_*); transcripts: proof_script.hpp
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip)
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails
@@ -232,6 +233,12 @@ int fail(typlonk_ctx* c, int code, const std::string& msg);
                              std::string(#expr) + ": " + hipGetErrorString(_e));                          \
     } while (0)
 
+// the same mapping for call sites that cannot return from the middle (a status to carry on with)
+inline int hip_rc(typlonk_ctx* ctx, hipError_t e) {
+    if (e == hipSuccess) return TYPLONK_OK;
+    return fail(ctx, e == hipErrorOutOfMemory ? TYPLONK_ERR_OOM : TYPLONK_ERR_HIP, hipGetErrorString(e));
+}
+
 int ensure(typlonk_ctx* ctx, DevBuf& b, size_t bytes);   // grow-only device workspace
 void release(DevBuf& b);
 
@@ -346,6 +353,11 @@ struct MsmQueue {
     int submit(const Fr* d_scalars, size_t m, uint64_t* out_xy, uint8_t* out_inf, bool standalone = false);
     int wait_all();
 };
+// A round's queue outlives every early return of the round: its MSMs write into the caller's outputs.
+struct WaitAll {
+    MsmQueue& q;
+    ~WaitAll() { (void)q.wait_all(); }
+};
 
 // ---- prover.hip: the linearisation polynomial r (proof.rs:376-439), shared by typlonk_prove and typlonk_prove_batch ------
 // What it needs of zeta alone: zeta^n, Z_H(zeta) = zeta^n - 1 and L0(zeta) (one host inversion).
@@ -355,6 +367,65 @@ void lin_zeta_terms(const Fr& zeta, uint32_t log_n, Fr* zn, Fr* zh, Fr* l0z);
 constexpr int LIN_TERMS = 10;
 void lin_scalars(const Fr* ev, const Fr& s0, const Fr& s1, const Fr& pi_z, const Fr& beta, const Fr& gamma, const Fr (&k)[3],
                  const Fr& alpha, const Fr& zeta, const Fr& zn, const Fr& zh, const Fr& l0z, Fr* scalar /* LIN_TERMS */, Fr* constant);
+
+// where the ten polynomials lie: coef = the circuit's coefficient copies (CircuitEntry::coef), z and t = the proof's Z and
+// quotient (t_lo, t_mid, t_hi are t's first 3n coefficients).  pb_fold_kernel (prove_batch.hip) reads the same ten fused.
+TY_HD void lin_polys(const Fr* coef, const Fr* z, const Fr* t, uint64_t n, const Fr** poly /* LIN_TERMS */) {
+    for (int k = 0; k < 5; ++k) poly[k] = coef + k * n;
+    poly[5] = z;
+    poly[6] = coef + 7 * n;
+    for (int k = 0; k < 3; ++k) poly[7 + k] = t + k * n;
+}
+
+// ---- prover.hip: the steps typlonk_prove* and typlonk_prove_batch* share ---------------------------------------------------
+// The quotient's coset generator: Fr's multiplicative generator 7 (7^(4n) != 1, so X^n - 1 never vanishes on g H_4n), as
+// the limbs the transforms take; g_out: the same as an Fr.
+const uint64_t* coset_g(Fr* g_out = nullptr);
+// The quotient's domain g H_4n for n = 2^log_n: x_i = g w_{4n}^i = g * w_lo[i & (2^w_h - 1)] * w_hi[i >> w_h] (n_hi entries of
+// w_hi; a caller folds g and what else it has per call into a scaled copy), and X^n - 1 there, which takes only the four
+// values g^n iota^k - 1 (iota = w_{4n}^n, k = i mod 4): their inverses.
+struct QuotientDomain {
+    const Fr* w_lo;
+    const Fr* w_hi;
+    uint64_t n_hi;
+    uint32_t w_h;
+    Fr g;
+    const uint64_t* g_limbs;
+    Fr zh_inv[4];
+};
+int quotient_domain(typlonk_ctx* ctx, uint32_t log_n, QuotientDomain* d);
+
+// Round 3's openings and evaluations of one proof.  Where each result lands (a pinned slot per proof) depends on the proof
+// shape: the compact shape keeps its seven evaluations in the proof's order.  (sig0, sig1: CircuitEntry::coef's sigma_0 and
+// sigma_1, which the compact shape's documents count from 1.)  r(zeta) and F come after these and are not part of the list.
+struct Round3Slots {
+    int wire;   // a, b, c at zeta: wire + i
+    int z, sig0, sig1;
+    int pi;     // PI(zeta), for the linearisation only
+    int zw;     // Z at zeta w
+    int count;  // slots to fetch
+};
+constexpr Round3Slots REF_SLOTS{0, 3, 4, 5, 6, 8, 9};
+constexpr Round3Slots COMPACT_SLOTS{0, 3, 5, 6, 7, 4, 8};
+struct Round3Polys {
+    const Fr* co[3];
+    const Fr* z;
+    const Fr* pi;     // null: the zero polynomial
+    Fr* const* q;     // the proof's witness polynomials q[0..4]
+    const Fr* coef;   // CircuitEntry::coef
+    uint64_t n;
+};
+// emit(poly, quotient or null, slot, point) for every item; point 0 = zeta, 1 = zeta w.  with_quotients: a, b, c, Z are
+// opened at zeta one by one (the reference shape's six openings); Z at zeta w always has its quotient.
+template <class Emit>
+void round3_openings(const Round3Slots& s, bool with_quotients, const Round3Polys& p, Emit emit) {
+    for (int i = 0; i < 3; ++i) emit(p.co[i], with_quotients ? p.q[i] : nullptr, s.wire + i, 0);
+    emit(p.z, with_quotients ? p.q[3] : nullptr, s.z, 0);
+    emit(p.coef + 5 * p.n, nullptr, s.sig0, 0);
+    emit(p.coef + 6 * p.n, nullptr, s.sig1, 0);
+    if (p.pi) emit(p.pi, nullptr, s.pi, 0);
+    emit(p.z, p.q[4], s.zw, 1);
+}
 
 // ---- poly_eval.hip / verify.hip ----------------------------------------------------------------------------------------
 // out[(p * n_points + k) * 4 ..] = polys[p](points[k]) over m coefficients each (device pointers; points / out on the host,

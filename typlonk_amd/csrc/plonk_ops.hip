@@ -16,19 +16,14 @@
 
 namespace ty {
 
-// num_j = prod_i (w_ij + beta k_i w^j + gamma),  den_j = prod_i (w_ij + beta sigma_ij + gamma)
+// num_j, den_j of every row (gp_term, scan_ops.hpp)
 __global__ __launch_bounds__(256) void gp_terms_kernel(GrandProductArgs a) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= a.n) return;
     const Fr x = fe_mul(p_ld(a.w_lo + (j & ((1ull << a.w_h) - 1))), p_ld(a.w_hi + (j >> a.w_h)));
     Fr num = Fr::one(), den = Fr::one();
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const Fr w = p_ld(a.wires[i] + j);
-        const Fr wg = fe_add(w, a.gamma);
-        num = fe_mul(num, fe_add(wg, fe_mul(a.kbeta[i], x)));
-        den = fe_mul(den, fe_add(wg, fe_mul(a.beta, p_ld(a.sigma[i] + j))));
-    }
+    for (int i = 0; i < 3; ++i) gp_term(a.wires[i] + j, a.sigma[i] + j, x, a.beta, a.gamma, a.kbeta[i], num, den);
     p_st(a.num + j, num);
     p_st(a.den + j, den);
 }
@@ -53,10 +48,10 @@ __global__ __launch_bounds__(64) void fr_inv_kernel(const Fr* in, Fr* out) {
 __global__ __launch_bounds__(256) void gp_finish_kernel(const Fr* nprefix, const Fr* dsuffix, const Fr* inv_total, uint64_t n, Fr* z) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
-    p_st(z + j, fe_mul(fe_mul(p_ld(nprefix + j), p_ld(dsuffix + j)), p_ld(inv_total)));
+    p_st(z + j, gp_finish(p_ld(nprefix + j), p_ld(dsuffix + j), p_ld(inv_total)));
 }
 
-// ---- open(): H_j = c_j + z H_{j+1} (H_m = 0) for all j at once: horner_block (scan_ops.hpp) ----------------
+// ---- open(): H_j = c_j + z H_{j+1} (H_m = 0) for all j at once; the three stages are bodies of scan_ops.hpp -------------
 
 struct OpenArgs {
     const Fr* c;
@@ -66,36 +61,20 @@ struct OpenArgs {
     Fr* y;          // device scalar: p(z)
     Fr zpow[32];    // z^(2^k)
 };
+__device__ __forceinline__ OpenItem open_item(const OpenArgs& a) { return OpenItem{a.c, a.q, a.y, a.zpow, a.blocks}; }
 
-// sweep 1: H at the start of every workgroup assuming a zero carry
 __global__ __launch_bounds__(256) void open_block_kernel(OpenArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const Fr g0 = horner_block(a.c, a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow, 0, lds, loc, &ci);
-    if (threadIdx.x == 0) p_st(a.blocks + blockIdx.x, g0);
+    open_block_stage(open_item(a), a.m, lds);
 }
+// (always stores the carries: an evaluation too goes through the second sweep, which writes only y)
 __global__ __launch_bounds__(256) void open_top_kernel(OpenArgs a, uint32_t nblk) {
     __shared__ Fr lds[256];
-    open_top_rounds(a.blocks, nblk, a.zpow, true, lds);
+    open_top_stage(open_item(a), nblk, true, lds);
 }
-// sweep 2: seeded with the true carry; writes q and y
 __global__ __launch_bounds__(256) void open_finish_kernel(OpenArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const uint64_t base = (uint64_t)blockIdx.x * 2048;
-    const Fr seed = p_ld(a.blocks + blockIdx.x);
-    horner_block(a.c, a.m, base, seed, a.zpow, 0, lds, loc, &ci);
-    const Fr z = a.zpow[0];
-    Fr h = ci;
-    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
-    for (int e = 7; e >= 0; --e) {
-        const uint64_t i = s0 + e;
-        h = fe_add(loc[e], fe_mul(z, h));  // H_i
-        if (i < a.m) {
-            if (i == 0) p_st(a.y, h);
-            else if (a.q) p_st(a.q + i - 1, h);
-        }
-    }
+    open_finish_stage(open_item(a), a.m, lds);
 }
 
 // ---- up to 8 openings / evaluations of polynomials of the same length at one of two points: three launches in all ----
@@ -111,40 +90,23 @@ struct OpenMultiArgs {
     uint32_t nblk;
     Fr zpow[2][32];
 };
+__device__ __forceinline__ OpenItem open_item(const OpenMultiArgs& a, uint32_t k) {
+    return OpenItem{a.c[k], a.q[k], a.y[k], a.zpow[a.zsel[k]], a.blocks + (uint64_t)k * a.nblk};
+}
 __global__ __launch_bounds__(256) void open_multi_block_kernel(OpenMultiArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const uint32_t k = blockIdx.y;
-    const Fr g0 = horner_block(a.c[k], a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow[a.zsel[k]], 0, lds, loc, &ci);
-    if (threadIdx.x == 0) p_st(a.blocks + (uint64_t)k * a.nblk + blockIdx.x, g0);
+    open_block_stage(open_item(a, blockIdx.y), a.m, lds);
 }
 __global__ __launch_bounds__(256) void open_multi_top_kernel(OpenMultiArgs a) {
     __shared__ Fr lds[256];
-    const uint32_t k = blockIdx.x;
-    const bool store = a.q[k] != nullptr;
-    const Fr y = open_top_rounds(a.blocks + (uint64_t)k * a.nblk, a.nblk, a.zpow[a.zsel[k]], store, lds);
-    if (!store && threadIdx.x == 0) p_st(a.y[k], y);  // p(z) = sum_b A_b (z^2048)^b: an evaluation is complete here
+    const OpenItem it = open_item(a, blockIdx.x);
+    open_top_stage(it, a.nblk, it.q != nullptr, lds);
 }
 __global__ __launch_bounds__(256) void open_multi_finish_kernel(OpenMultiArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const uint32_t k = blockIdx.y;
-    if (!a.q[k]) return;  // whole workgroup: no barrier is skipped by part of it
-    const Fr* zp = a.zpow[a.zsel[k]];
-    const uint64_t base = (uint64_t)blockIdx.x * 2048;
-    const Fr seed = p_ld(a.blocks + (uint64_t)k * a.nblk + blockIdx.x);
-    horner_block(a.c[k], a.m, base, seed, zp, 0, lds, loc, &ci);
-    const Fr z = zp[0];
-    Fr h = ci;
-    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
-    for (int e = 7; e >= 0; --e) {
-        const uint64_t i = s0 + e;
-        h = fe_add(loc[e], fe_mul(z, h));
-        if (i < a.m) {
-            if (i == 0) p_st(a.y[k], h);
-            else p_st(a.q[k] + i - 1, h);
-        }
-    }
+    const OpenItem it = open_item(a, blockIdx.y);
+    if (!it.q) return;  // an evaluation was complete at the top stage (whole workgroup: no barrier is skipped by part of it)
+    open_finish_stage(it, a.m, lds);
 }
 void launch_open_multi(const Fr* const* polys, Fr* const* quotients, Fr* const* ys, const uint8_t* zsel, uint32_t count,
                        uint64_t m, const Fr& z0, const Fr& z1, Fr* blocks, hipStream_t s) {

@@ -12,11 +12,10 @@
 // (wave_rounds12, with the shape's transcript), round 3 goes in the compact transcript's order -- the 3G quotient commitments
 // before any zeta is drawn (a fourth host wait per wave), then the evaluations, then r and F of every proof from one fused
 // kernel (pb_fold_kernel) and the 2G opening commitments.
-#include "compact_transcript.hpp"
 #include "fr_inv.hpp"
 #include "host.hpp"
+#include "proof_script.hpp"
 #include "scan_ops.hpp"
-#include "transcript.hpp"
 
 #include <cstddef>
 
@@ -30,7 +29,8 @@ constexpr uint64_t PB_ROWS = 1ull << 22;     // and at most this many rows of al
 constexpr uint32_t PB_ITEMS = 8;             // round 3's openings / evaluations per proof
 constexpr uint32_t PB_QGROUP = 4;            // proofs one thread of the quotient kernel evaluates per point
 constexpr uint32_t PB_FGROUP = 4;            // proofs one thread of the compact shape's fold kernel combines per coefficient
-constexpr uint32_t PB_SLOTS = 16;            // pinned result slots per proof
+constexpr uint32_t PB_SLOTS = 16;            // pinned result slots per proof: round 3's (Round3Slots, host.hpp), then
+constexpr uint32_t PB_SLOT_F = 8, PB_SLOT_R = 9;   // F(zeta) of the compact shape (not read) and r(zeta)
 // per-proof arena of a wave, in units of n Fr: ev[3] co[3] pi z t(4) q[6] r | ext a b c Z PI (5 x 4)
 constexpr uint64_t PB_EV = 0, PB_CO = 3, PB_PI = 6, PB_Z = 7, PB_T = 8, PB_Q = 12, PB_R = 18, PB_EXT = 19, PB_STRIDE = 39;
 
@@ -90,11 +90,7 @@ __global__ __launch_bounds__(256) void pb_gp_terms_kernel(PbGpArgs a) {
     const Fr* ev = a.ev + p * a.stride;
     Fr num = Fr::one(), den = Fr::one();
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const Fr wg = fe_add(p_ld(ev + i * a.n + j), g.gamma);
-        num = fe_mul(num, fe_add(wg, fe_mul(g.kbeta[i], x)));
-        den = fe_mul(den, fe_add(wg, fe_mul(g.beta, p_ld(a.sigma + i * a.n + j))));
-    }
+    for (int i = 0; i < 3; ++i) gp_term(ev + i * a.n + j, a.sigma + i * a.n + j, x, g.beta, g.gamma, g.kbeta[i], num, den);
     Fr* t = a.tmp + p * a.stride;
     p_st(t + j, num);
     p_st(t + a.n + j, den);
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256) void pb_gp_finish_kernel(PbGpArgs a) {
     const uint32_t p = blockIdx.y;
     const Fr* t = a.tmp + p * a.stride;
     p_st(a.z + p * a.stride + j,
-         fe_mul(fe_mul(p_ld(t + 2 * a.n + j), p_ld(t + 3 * a.n + j)), p_ld(a.blk + p * a.stride + 2 * a.nblk)));
+         gp_finish(p_ld(t + 2 * a.n + j), p_ld(t + 3 * a.n + j), p_ld(a.blk + p * a.stride + 2 * a.nblk)));
 }
 
 // ---- openings / evaluations of many polynomials of m coefficients, each at its own point (launch_open_multi for a wave) -----
@@ -137,40 +133,24 @@ struct PbOpenArgs {
     uint64_t m;
     uint32_t nblk;
 };
+__device__ __forceinline__ OpenItem open_item(const PbOpenArgs& a, uint32_t k) {
+    const PbItem it = a.items[k];
+    return OpenItem{it.c, it.q, it.y, a.zpow + it.zi * 32, a.blocks + (uint64_t)k * a.nblk};
+}
 __global__ __launch_bounds__(256) void pb_open_block_kernel(PbOpenArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const PbItem it = a.items[blockIdx.y];
-    const Fr g0 = horner_block(it.c, a.m, (uint64_t)blockIdx.x * 2048, Fr::zero(), a.zpow + it.zi * 32, 0, lds, loc, &ci);
-    if (threadIdx.x == 0) p_st(a.blocks + (uint64_t)blockIdx.y * a.nblk + blockIdx.x, g0);
+    open_block_stage(open_item(a, blockIdx.y), a.m, lds);
 }
 __global__ __launch_bounds__(256) void pb_open_top_kernel(PbOpenArgs a) {
     __shared__ Fr lds[256];
-    const PbItem it = a.items[blockIdx.x];
-    const bool store = it.q != nullptr;
-    const Fr y = open_top_rounds(a.blocks + (uint64_t)blockIdx.x * a.nblk, a.nblk, a.zpow + it.zi * 32, store, lds);
-    if (!store && threadIdx.x == 0) p_st(it.y, y);
+    const OpenItem it = open_item(a, blockIdx.x);
+    open_top_stage(it, a.nblk, it.q != nullptr, lds);
 }
 __global__ __launch_bounds__(256) void pb_open_finish_kernel(PbOpenArgs a) {
     __shared__ Fr lds[256];
-    Fr loc[8], ci;
-    const PbItem it = a.items[blockIdx.y];
+    const OpenItem it = open_item(a, blockIdx.y);
     if (!it.q) return;  // whole workgroup
-    const Fr* zp = a.zpow + it.zi * 32;
-    const uint64_t base = (uint64_t)blockIdx.x * 2048;
-    const Fr seed = p_ld(a.blocks + (uint64_t)blockIdx.y * a.nblk + blockIdx.x);
-    horner_block(it.c, a.m, base, seed, zp, 0, lds, loc, &ci);
-    const Fr z = zp[0];
-    Fr h = ci;
-    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
-    for (int e = 7; e >= 0; --e) {
-        const uint64_t i = s0 + e;
-        h = fe_add(loc[e], fe_mul(z, h));
-        if (i < a.m) {
-            if (i == 0) p_st(it.y, h);
-            else p_st(it.q + i - 1, h);
-        }
-    }
+    open_finish_stage(it, a.m, lds);
 }
 void pb_launch_open(const PbItem* items, uint32_t count, const Fr* zpow, uint64_t m, Fr* blocks, hipStream_t s) {
     PbOpenArgs a{items, zpow, blocks, m, (uint32_t)((m + 2047) / 2048)};
@@ -179,7 +159,7 @@ void pb_launch_open(const PbItem* items, uint32_t count, const Fr* zpow, uint64_
     hipLaunchKernelGGL(pb_open_finish_kernel, dim3(a.nblk, count), dim3(256), 0, s, a);
 }
 
-// ---- round 3: the quotient's pointwise kernel for a wave (quotient.hip's formula) ------------------------------------------
+// ---- round 3: the quotient's pointwise kernel for a wave (quotient_point, scan_ops.hpp) -----------------------------------
 // One thread owns one point of the 4n coset and PB_QGROUP proofs: the circuit's nine coset constants and x_i are loaded once
 // and serve every proof of the group (each proof alone re-read them at all 4n points).
 struct PbQuotArgs {
@@ -212,31 +192,15 @@ __global__ __launch_bounds__(256) void pb_quotient_kernel(PbQuotArgs a) {
         const Fr* e = a.ext + p * a.stride;
         const Fr wa = p_ld(e + i), wb = p_ld(e + a.n4 + i), wc = p_ld(e + 2 * a.n4 + i);
         const Fr z = p_ld(e + 3 * a.n4 + i), zw = p_ld(e + 3 * a.n4 + iw);
-        Fr line1 = fe_mul(sel[0], wa);
-        line1 = fe_add(line1, fe_mul(sel[1], wb));
-        line1 = fe_sub(line1, fe_mul(sel[2], wc));
-        line1 = fe_add(line1, fe_mul(fe_mul(sel[3], wa), wb));
-        line1 = fe_add(line1, sel[4]);
-        if (q.has_pi) line1 = fe_add(line1, p_ld(e + 4 * a.n4 + i));
-        const Fr bx = fe_mul(q.beta, x);
-        Fr l2 = fe_add(fe_add(wa, a.k0_is_one ? bx : fe_mul(a.k[0], bx)), q.gamma);
-        l2 = fe_mul(l2, fe_add(fe_add(wb, fe_mul(a.k[1], bx)), q.gamma));
-        l2 = fe_mul(l2, fe_add(fe_add(wc, fe_mul(a.k[2], bx)), q.gamma));
-        l2 = fe_mul(l2, z);
-        Fr l3 = fe_add(fe_add(wa, fe_mul(q.beta, sig[0])), q.gamma);
-        l3 = fe_mul(l3, fe_add(fe_add(wb, fe_mul(q.beta, sig[1])), q.gamma));
-        l3 = fe_mul(l3, fe_add(fe_add(wc, fe_mul(q.beta, sig[2])), q.gamma));
-        l3 = fe_mul(l3, zw);
-        const Fr l4 = fe_mul(fe_sub(z, Fr::one()), l0);
-        Fr t = fe_add(line1, fe_mul(q.alpha, fe_sub(l2, l3)));
-        t = fe_add(t, fe_mul(q.alpha2, l4));
-        p_st(a.t + p * a.stride + i, fe_mul(t, zhi));
+        const Fr t = quotient_point(wa, wb, wc, z, zw, q.has_pi ? e + 4 * a.n4 + i : nullptr, sel, sig, l0, fe_mul(q.beta, x), a.k,
+                                    a.k0_is_one, q.beta, q.gamma, q.alpha, q.alpha2, zhi);
+        p_st(a.t + p * a.stride + i, t);
     }
 }
 
 // ---- round 3: r = sum_k scalar_k poly_k + constant for every proof (lincomb_kernel with per-proof terms) -------------------
 struct PbLinArgs {
-    const Fr* coef;      // the circuit's coefficient copies (8 n): q_l q_r q_o q_m q_c at 0..4, sigma_2 at 7
+    const Fr* coef;      // the circuit's coefficient copies (8 n)
     const Fr* z;         // proof p's Z: z + p * stride, its t: t + p * stride, its r: r + p * stride
     const Fr* t;
     Fr* r;
@@ -249,8 +213,8 @@ __global__ __launch_bounds__(256) void pb_lincomb_kernel(PbLinArgs a) {
     const uint32_t p = blockIdx.y;
     const PbLin& l = a.lin[p];
     const Fr* t = a.t + p * a.stride;
-    const Fr* polys[LIN_TERMS] = {a.coef, a.coef + a.n, a.coef + 2 * a.n, a.coef + 3 * a.n, a.coef + 4 * a.n,
-                                  a.z + p * a.stride, a.coef + 7 * a.n, t, t + a.n, t + 2 * a.n};
+    const Fr* polys[LIN_TERMS];
+    lin_polys(a.coef, a.z + p * a.stride, t, a.n, polys);
     Fr acc = (i == 0) ? l.constant : Fr::zero();
 #pragma unroll
     for (int k = 0; k < LIN_TERMS; ++k) acc = fe_add(acc, fe_mul(l.scalar[k], p_ld(polys[k] + i)));
@@ -260,7 +224,8 @@ __global__ __launch_bounds__(256) void pb_lincomb_kernel(PbLinArgs a) {
 // ---- round 3 of the compact shape: r and F = a + v b + v^2 c + v^3 Z + v^4 r + v^5 sigma_1 + v^6 sigma_2 in one pass ----------
 // One thread owns coefficient i and PB_FGROUP proofs: the circuit's eight coefficients at i are loaded once and serve every proof
 // of the group.  A single proof runs lincomb_kernel twice (17 n Fr read, r written and read back); here a proof reads its own
-// seven vectors and writes r and F.  Every value is a canonical residue of an exact field expression, so the order of the sums
+// seven vectors and writes r and F.  r's ten terms are lin_polys' (host.hpp), in its order: coefficients 0..4 and 7 of the
+// circuit, Z, t_lo t_mid t_hi.  Every value is a canonical residue of an exact field expression, so the order of the sums
 // does not show in the result.
 struct PbFoldArgs {
     const Fr* coef;      // the circuit's coefficient copies (8 n): q_l q_r q_o q_m q_c sigma_0 sigma_1 sigma_2
@@ -304,15 +269,6 @@ __global__ __launch_bounds__(256) void pb_fold_kernel(PbFoldArgs a) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-const uint64_t* coset_g(Fr* g_out) {
-    // the quotient's coset generator (prover.hip): Fr's multiplicative generator 7
-    static uint64_t limbs[4];
-    const Fr g = fr_from_u64(7);
-    memcpy(limbs, g.v, sizeof(limbs));
-    if (g_out) *g_out = g;
-    return limbs;
-}
-
 struct ColumnsIn {   // the caller's columns: device buffers or host arrays, proof-major
     const typlonk_buf* const* wire_bufs;
     const typlonk_buf* const* pi_bufs;
@@ -349,55 +305,15 @@ struct Wave {
     Fr* at(uint32_t p, uint64_t off) const { return mem + ((uint64_t)p * PB_STRIDE + off) * n; }
 };
 
-int hip_rc(typlonk_ctx* ctx, hipError_t e) {
-    if (e == hipSuccess) return TYPLONK_OK;
-    return fail(ctx, e == hipErrorOutOfMemory ? TYPLONK_ERR_OOM : TYPLONK_ERR_HIP, hipGetErrorString(e));
-}
 // copy one part of the staged tables to the device, stream-ordered
 int upload(const Wave& w, const void* host_part, size_t bytes) {
     const size_t off = (const char*)host_part - (const char*)w.host;
     return hip_rc(w.ctx, hipMemcpyAsync((char*)w.dev + off, host_part, bytes, hipMemcpyHostToDevice, w.ctx->stream));
 }
 
-// The Fiat-Shamir script of a proof shape over rounds 1 and 2: after_round1 hashes [a] [b] [c] and fills beta, gamma;
-// after_round2 hashes [Z] and fills alpha (the reference shape draws zeta with it, the compact shape only in round 3).
-struct RefScript {
-    using Proof = typlonk_proof;
-    ChallengeGenerator g;
-    void after_round1(Proof& o) {                      // (beta, gamma) <- H([a], [b], [c])      proof.rs:111
-        uint64_t ch[8];
-        for (int i = 0; i < 3; ++i) g.digest(o.commit_xy[i], o.commit_inf[i]);
-        g.generate(2, ch);
-        memcpy(o.beta, ch, 32);
-        memcpy(o.gamma, ch + 4, 32);
-    }
-    void after_round2(Proof& o) {                      // (alpha, zeta) <- H([a], [b], [c], [Z])  proof.rs:133-136
-        uint64_t ch[8];
-        g.digest(o.z_xy, o.z_inf);
-        g.generate(2, ch);
-        memcpy(o.alpha, ch, 32);
-        memcpy(o.zeta, ch + 4, 32);
-    }
-};
-struct CompactScript {
-    using Proof = typlonk_proof_compact;
-    CompactTranscript tr;
-    explicit CompactScript(const uint8_t d0[64]) : tr(d0) {}
-    void after_round1(Proof& o) {
-        for (int i = 0; i < 3; ++i) tr.point(o.commit_xy[i], o.commit_inf[i]);
-        const Fr beta = tr.squeeze('b'), gamma = tr.squeeze('g');
-        memcpy(o.beta, beta.v, 32);
-        memcpy(o.gamma, gamma.v, 32);
-    }
-    void after_round2(Proof& o) {
-        tr.point(o.z_xy, o.z_inf);
-        const Fr alpha = tr.squeeze('a');
-        memcpy(o.alpha, alpha.v, 32);
-    }
-};
-
 // Rounds 1 and 2 of a wave in either shape: [a] [b] [c] and [Z] of every proof, beta / gamma / alpha in out[], the coset
-// extensions of a, b, c, Z (and PI) queued, and the quotient's per-proof table (w.host->quot) filled.
+// extensions of a, b, c, Z (and PI) queued, and the quotient's per-proof table (w.host->quot) filled.  Script: the shape's
+// Fiat-Shamir script (proof_script.hpp), one per proof.
 template <class Script>
 int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typename Script::Proof* out, std::vector<Script>& tr) {
     typlonk_ctx* ctx = w.ctx;
@@ -405,7 +321,7 @@ int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typena
     const uint64_t n = w.n, n4 = 4 * n;
     const uint32_t log_n = w.log_n, log4 = log_n + 2;
     const uint64_t stride = PB_STRIDE * n;
-    const uint64_t* g_limbs = coset_g(nullptr);
+    const uint64_t* g_limbs = coset_g();
     int rc = TYPLONK_OK;
     bool* has_pi = w.has_pi;
     for (uint32_t p = 0; p < G; ++p) has_pi[p] = in.pi_rows(first + p, n) != 0;
@@ -516,6 +432,22 @@ int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typena
     return TYPLONK_OK;
 }
 
+// round 3's openings and evaluations of every proof of the wave (round3_openings) into the staged item table; returns how many
+uint32_t stage_round3_items(Wave& w, uint32_t G, const Round3Slots& slots, bool with_quotients) {
+    uint32_t nitems = 0;
+    Fr* q[5];
+    for (uint32_t p = 0; p < G; ++p) {
+        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        for (int i = 0; i < 5; ++i) q[i] = w.at(p, PB_Q + i);
+        const Round3Polys polys{{w.at(p, PB_CO), w.at(p, PB_CO + 1), w.at(p, PB_CO + 2)}, w.at(p, PB_Z),
+                                w.has_pi[p] ? w.at(p, PB_PI) : nullptr, q, w.ce->coef, w.n};
+        round3_openings(slots, with_quotients, polys, [&](const Fr* c, Fr* quot, int slot, uint32_t point) {
+            w.host->item[nitems++] = PbItem{c, quot, y + slot, 2ull * p + point};
+        });
+    }
+    return nitems;
+}
+
 // zeta_p^(2^k) and (zeta_p w)^(2^k) of proof p into the staged table
 void stage_zpow(Wave& w, uint32_t p, const Fr& zeta) {
     Fr* zp0 = w.host->zpow[2 * p];
@@ -538,8 +470,9 @@ int wave_quotient(Wave& w, uint32_t G) {
     int rc;
     if ((rc = upload(w, w.host->quot, G * sizeof(PbQuot)))) return rc;
     PbQuotArgs a{};
-    Fr g;
-    const uint64_t* g_limbs = coset_g(&g);
+    QuotientDomain d;
+    if ((rc = quotient_domain(ctx, log_n, &d))) return rc;
+    const uint64_t* g_limbs = d.g_limbs;
     a.ext = w.at(0, PB_EXT);
     a.cext = w.ce->ext;
     a.t = w.at(0, PB_T);
@@ -547,25 +480,12 @@ int wave_quotient(Wave& w, uint32_t G) {
     a.n4 = n4;
     a.stride = PB_STRIDE * n;
     a.count = G;
-    Table lo, hi;
-    const Fr w4 = fr_domain_root(log4);
-    if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &a.w_h))) return rc;
-    a.w_lo = lo.d;
-    const uint64_t n_hi = 1ull << (log4 - a.w_h);
-    if ((rc = ensure(ctx, ctx->quot_tab, n_hi * sizeof(Fr)))) return rc;
-    launch_fr_scale(hi.d, n_hi, g, (Fr*)ctx->quot_tab.p, s);
+    a.w_lo = d.w_lo;
+    a.w_h = d.w_h;
+    if ((rc = ensure(ctx, ctx->quot_tab, d.n_hi * sizeof(Fr)))) return rc;
+    launch_fr_scale(d.w_hi, d.n_hi, d.g, (Fr*)ctx->quot_tab.p, s);   // (beta is per proof: the kernel multiplies)
     a.gx_hi = (const Fr*)ctx->quot_tab.p;
-    // X^n - 1 on the coset: g^n iota^k - 1, iota = w_{4n}^n
-    Fr gn = g, iota = w4;
-    for (uint32_t i = 0; i < log_n; ++i) {
-        gn = fe_sqr(gn);
-        iota = fe_sqr(iota);
-    }
-    Fr cur = gn;
-    for (int k = 0; k < 4; ++k) {
-        a.zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
-        cur = fe_mul(cur, iota);
-    }
+    for (int k = 0; k < 4; ++k) a.zh_inv[k] = d.zh_inv[k];
     for (int k = 0; k < 3; ++k) a.k[k] = w.k[k];
     a.k0_is_one = w.k[0] == Fr::one();
     hipLaunchKernelGGL(pb_quotient_kernel, dim3((unsigned)((n4 + 255) / 256), (G + PB_QGROUP - 1) / PB_QGROUP), dim3(256), 0, s, a);
@@ -594,17 +514,7 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
 
     // ---- round 3: openings (:147-163), quotient (:139-145), linearisation (:165-175), nine commitments per proof (:181) ----
     Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
-    uint32_t nitems = 0;
-    for (uint32_t p = 0; p < G; ++p) {
-        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
-        auto item = [&](const Fr* c, Fr* q, int slot, uint32_t zi) { w.host->item[nitems++] = PbItem{c, q, y + slot, 2ull * p + zi}; };
-        for (int i = 0; i < 3; ++i) item(w.at(p, PB_CO + i), w.at(p, PB_Q + i), i, 0);
-        item(w.at(p, PB_Z), w.at(p, PB_Q + 3), 3, 0);
-        item(w.ce->coef + 5 * n, nullptr, 4, 0);             // sigma_0
-        item(w.ce->coef + 6 * n, nullptr, 5, 0);             // sigma_1
-        if (has_pi[p]) item(w.at(p, PB_PI), nullptr, 6, 0);
-        item(w.at(p, PB_Z), w.at(p, PB_Q + 4), 8, 1);        // Z at zeta * w
-    }
+    const uint32_t nitems = stage_round3_items(w, G, REF_SLOTS, /*with_quotients=*/true);
     if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
     if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
     pb_launch_open(w.dev->item, nitems, &w.dev->zpow[0][0], n, blocks, s);
@@ -616,14 +526,15 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p) {
         const Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
-        const Fr ev[5] = {y[0], y[1], y[2], y[3], y[8]};
-        const Fr pi_z = has_pi[p] ? y[6] : Fr::zero();
+        constexpr Round3Slots S = REF_SLOTS;
+        const Fr ev[5] = {y[S.wire], y[S.wire + 1], y[S.wire + 2], y[S.z], y[S.zw]};
+        const Fr pi_z = has_pi[p] ? y[S.pi] : Fr::zero();
         PbLin& l = w.host->lin[p];
-        lin_scalars(ev, y[4], y[5], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha[p], zeta[p], zn[p], zh[p], l0z[p],
-                    l.scalar, &l.constant);
+        lin_scalars(ev, y[S.sig0], y[S.sig1], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha[p], zeta[p], zn[p], zh[p],
+                    l0z[p], l.scalar, &l.constant);
         typlonk_proof_tail& t = out[first + p].tail;
         for (int i = 0; i < 5; ++i) memcpy(t.evals[i], ev[i].v, 32);
-        w.host->ritem[p] = PbItem{w.at(p, PB_R), w.at(p, PB_Q + 5), w.slots + (uint64_t)p * PB_SLOTS + 9, 2ull * p};
+        w.host->ritem[p] = PbItem{w.at(p, PB_R), w.at(p, PB_Q + 5), w.slots + (uint64_t)p * PB_SLOTS + PB_SLOT_R, 2ull * p};
     }
     if ((rc = upload(w, w.host->lin, G * sizeof(PbLin)))) return rc;
     if ((rc = upload(w, w.host->ritem, G * sizeof(PbItem)))) return rc;
@@ -652,7 +563,7 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p) {
-        const Fr rz = w.slots[(uint64_t)p * PB_SLOTS + 9];
+        const Fr rz = w.slots[(uint64_t)p * PB_SLOTS + PB_SLOT_R];
         memcpy(out[first + p].tail.evals[5], rz.v, 32);
         // r(zeta) != 0: the witness does not satisfy the circuit (proof.rs:234-235), as typlonk_prove reports it
         status[first + p] = rz.is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
@@ -711,26 +622,13 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     if (rc) return rc;
     std::vector<Fr> zeta(G);
     for (uint32_t p = 0; p < G; ++p) {
-        typlonk_proof_compact& o = out[first + p];
-        for (int i = 0; i < 3; ++i) tr[p].tr.point(o.t_xy[i], o.t_inf[i]);
-        zeta[p] = tr[p].tr.squeeze('z');
-        memcpy(o.zeta, zeta[p].v, 32);
+        zeta[p] = tr[p].after_quotient(out[first + p]);
         stage_zpow(w, p, zeta[p]);
     }
-    // ---- a, b, c, Z, sigma_1, sigma_2 (and PI) at zeta_p, Z at zeta_p w with its quotient: slots 0..6 are the proof's seven
-    // evaluations in order, 7 = PI(zeta); one wait for the whole wave ----
+    // ---- a, b, c, Z, sigma_1, sigma_2 (and PI) at zeta_p, Z at zeta_p w with its quotient (COMPACT_SLOTS: the first seven slots
+    // are the proof's evaluations in order); one wait for the whole wave ----
     Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
-    uint32_t nitems = 0;
-    for (uint32_t p = 0; p < G; ++p) {
-        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
-        auto item = [&](const Fr* c, Fr* q, int slot, uint32_t zi) { w.host->item[nitems++] = PbItem{c, q, y + slot, 2ull * p + zi}; };
-        for (int i = 0; i < 3; ++i) item(w.at(p, PB_CO + i), nullptr, i, 0);
-        item(w.at(p, PB_Z), nullptr, 3, 0);
-        item(w.ce->coef + 5 * n, nullptr, 5, 0);             // sigma_1
-        item(w.ce->coef + 6 * n, nullptr, 6, 0);             // sigma_2
-        if (has_pi[p]) item(w.at(p, PB_PI), nullptr, 7, 0);
-        item(w.at(p, PB_Z), w.at(p, PB_Q + 4), 4, 1);        // Z at zeta * w
-    }
+    const uint32_t nitems = stage_round3_items(w, G, COMPACT_SLOTS, /*with_quotients=*/false);
     if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
     if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
     pb_launch_open(w.dev->item, nitems, &w.dev->zpow[0][0], n, blocks, s);
@@ -741,23 +639,21 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     for (uint32_t p = 0; p < G; ++p) {
         Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
         typlonk_proof_compact& o = out[first + p];
-        for (int i = 0; i < 7; ++i) {
-            memcpy(o.evals[i], y[i].v, 32);
-            tr[p].tr.scalar(o.evals[i]);
-        }
-        const Fr v = tr[p].tr.squeeze('v');
-        memcpy(o.v, v.v, 32);
-        const Fr pi_z = has_pi[p] ? y[7] : Fr::zero();
+        constexpr Round3Slots S = COMPACT_SLOTS;
+        for (int i = 0; i < 7; ++i) memcpy(o.evals[i], y[i].v, 32);
+        const Fr v = tr[p].after_evals(o);
+        const Fr pi_z = has_pi[p] ? y[S.pi] : Fr::zero();
         Fr alpha;
         memcpy(alpha.v, o.alpha, 32);
         PbFold& f = w.host->fold[p];
-        lin_scalars(y, y[5], y[6], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha, zeta[p], zn[p], zh[p], l0z[p],
-                    f.lin.scalar, &f.lin.constant);
+        static_assert(S.wire == 0 && S.z == 3 && S.zw == 4, "lin_scalars reads a, b, c, Z, Z(zeta w) as ev[0..4]");
+        lin_scalars(y, y[S.sig0], y[S.sig1], pi_z, w.host->gp[p].beta, w.host->gp[p].gamma, w.k, alpha, zeta[p], zn[p], zh[p],
+                    l0z[p], f.lin.scalar, &f.lin.constant);
         f.vpow[0] = v;
         for (int j = 1; j < 6; ++j) f.vpow[j] = fe_mul(f.vpow[j - 1], v);
         // F (in q[1]) opened at zeta with its witness into q[0]; r evaluated there for the status (q[0..3] are free in this shape)
-        w.host->ritem[2 * p] = PbItem{w.at(p, PB_Q + 1), w.at(p, PB_Q), y + 8, 2ull * p};
-        w.host->ritem[2 * p + 1] = PbItem{w.at(p, PB_R), nullptr, y + 9, 2ull * p};
+        w.host->ritem[2 * p] = PbItem{w.at(p, PB_Q + 1), w.at(p, PB_Q), y + PB_SLOT_F, 2ull * p};
+        w.host->ritem[2 * p + 1] = PbItem{w.at(p, PB_R), nullptr, y + PB_SLOT_R, 2ull * p};
     }
     if ((rc = upload(w, w.host->fold, G * sizeof(PbFold)))) return rc;
     if ((rc = upload(w, w.host->ritem, 2 * G * sizeof(PbItem)))) return rc;
@@ -785,7 +681,7 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p)   // r(zeta) != 0: the witness does not satisfy the circuit, as typlonk_prove_compact reports it
-        status[first + p] = w.slots[(uint64_t)p * PB_SLOTS + 9].is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
+        status[first + p] = w.slots[(uint64_t)p * PB_SLOTS + PB_SLOT_R].is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
     return TYPLONK_OK;
 }
 

@@ -2,38 +2,60 @@
 // Part of the host driver of include/typlonk.h (see host.hpp for the shared state).  There is deliberately no CPU compute
 // fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #include "host.hpp"
-#include "transcript.hpp"
-#include "compact_transcript.hpp"
+#include "proof_script.hpp"
 
 using namespace ty;
 using namespace tyh;
 
 // (entry points: C linkage comes from their declarations in include/typlonk.h)
 
-namespace {
-const uint64_t* quotient_coset_g(Fr* g_out) {
-    // coset generator: Fr's multiplicative generator 7 (7^(4n) != 1, so X^n - 1 never vanishes on g*H_4n)
+namespace tyh {
+const uint64_t* coset_g(Fr* g_out) {
     static uint64_t limbs[4];
     const Fr g = fr_from_u64(7);
     memcpy(limbs, g.v, sizeof(limbs));
     if (g_out) *g_out = g;
     return limbs;
 }
+int quotient_domain(typlonk_ctx* ctx, uint32_t log_n, QuotientDomain* d) {
+    const uint32_t log4 = log_n + 2;
+    Table lo, hi;
+    const Fr w4 = fr_domain_root(log4);
+    const int rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &d->w_h);
+    if (rc) return rc;
+    d->w_lo = lo.d;
+    d->w_hi = hi.d;
+    d->n_hi = 1ull << (log4 - d->w_h);
+    d->g_limbs = coset_g(&d->g);
+    Fr gn = d->g, iota = w4;   // g^n; iota = w_{4n}^n, a primitive 4th root of unity
+    for (uint32_t i = 0; i < log_n; ++i) {
+        gn = fe_sqr(gn);
+        iota = fe_sqr(iota);
+    }
+    Fr cur = gn;
+    for (int k = 0; k < 4; ++k) {
+        d->zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
+        cur = fe_mul(cur, iota);
+    }
+    return TYPLONK_OK;
+}
+}  // namespace tyh
 
+namespace {
 // zero-extend an n-coefficient vector (or the constant-coefficient polynomial `fill`) to 4n and
 // evaluate it on the coset g*H_4n, in place in `e`
 int quotient_extend(typlonk_ctx* ctx, Fr* e, const Fr* src, const Fr* fill, uint64_t n, uint32_t log4) {
     hipStream_t s = ctx->stream;
     // the coefficients are read in place, zero-padded to 4n by the first pass itself (no copy + 3n-element memset + reads
     // of the zeros: 160 MB of traffic and two launches per extension at n = 2^20)
-    if (src) return ntt_run(ctx, e, log4, 0, quotient_coset_g(nullptr), /*sync=*/false, src, n);
+    if (src) return ntt_run(ctx, e, log4, 0, coset_g(), /*sync=*/false, src, n);
     launch_fr_fill(e, n, *fill, s);
     HIPCHK(hipMemsetAsync(e + n, 0, 3 * n * sizeof(Fr), s));
-    return ntt_run(ctx, e, log4, 0, quotient_coset_g(nullptr), /*sync=*/false);
+    return ntt_run(ctx, e, log4, 0, coset_g(), /*sync=*/false);
 }
 // the same for `count` coefficient vectors at once (one launch per pass for the whole group)
 int quotient_extend_batch(typlonk_ctx* ctx, Fr* const* e, const Fr* const* src, size_t count, uint64_t n, uint32_t log4) {
-    return ntt_run_batch(ctx, e, count, log4, 0, quotient_coset_g(nullptr), /*sync=*/false, src, n);
+    return ntt_run_batch(ctx, e, count, log4, 0, coset_g(), /*sync=*/false, src, n);
 }
 }  // namespace
 
@@ -76,8 +98,7 @@ int typlonk_circuit_load(typlonk_ctx* ctx, const typlonk_buf* const selectors[5]
         if (!rc) rc = ntt_run_batch(ctx, sig, 3, log_n, 0, nullptr, /*sync=*/false);   // proof.rs:334-338
     }
     if (!rc) {
-        hipError_t he = hipStreamSynchronize(ctx->stream);
-        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        rc = hip_rc(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (rc) return rc;
     guard.dismiss();
@@ -141,8 +162,6 @@ int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t l
     if (rc) return rc;
     Fr* ext = (Fr*)ctx->quot_ext.p;
     hipStream_t s = ctx->stream;
-    Fr g;
-    const uint64_t* g_limbs = quotient_coset_g(&g);
     ProfilingOff prof_off(ctx);  // stage events are per call
     const Fr ninv = fe_inv(fr_from_u64(n));
     {
@@ -173,31 +192,15 @@ int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t l
     qa.l0 = cbase + 8 * n4;
     qa.out = t_out->d;
     qa.n4 = n4;
-    {
-        Table lo, hi;
-        const Fr w4 = fr_domain_root(log4);
-        rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &qa.w_h);
-        if (rc) {
-            return rc;
-        }
-        qa.w_lo = lo.d;
-        const uint64_t n_hi = 1ull << (log4 - qa.w_h);
-        rc = ensure(ctx, ctx->quot_tab, n_hi * sizeof(Fr));
-        if (rc) return rc;
-        memcpy(qa.beta.v, args->beta, 32);
-        launch_fr_scale(hi.d, n_hi, fe_mul(qa.beta, g), (Fr*)ctx->quot_tab.p, s);
-        qa.bx_hi = (const Fr*)ctx->quot_tab.p;
-        // X^n - 1 on the coset: g^n * iota^k - 1 with iota = w_{4n}^n (a primitive 4th root of unity)
-        Fr gn = g;
-        for (uint32_t i = 0; i < log_n; ++i) gn = fe_sqr(gn);
-        Fr iota = w4;
-        for (uint32_t i = 0; i < log_n; ++i) iota = fe_sqr(iota);
-        Fr cur = gn;
-        for (int k = 0; k < 4; ++k) {
-            qa.zh_inv[k] = fe_inv(fe_sub(cur, Fr::one()));
-            cur = fe_mul(cur, iota);
-        }
-    }
+    QuotientDomain d;
+    if ((rc = quotient_domain(ctx, log_n, &d))) return rc;
+    qa.w_lo = d.w_lo;
+    qa.w_h = d.w_h;
+    if ((rc = ensure(ctx, ctx->quot_tab, d.n_hi * sizeof(Fr)))) return rc;
+    memcpy(qa.beta.v, args->beta, 32);
+    launch_fr_scale(d.w_hi, d.n_hi, fe_mul(qa.beta, d.g), (Fr*)ctx->quot_tab.p, s);   // beta * g folded into the upper level
+    qa.bx_hi = (const Fr*)ctx->quot_tab.p;
+    for (int k = 0; k < 4; ++k) qa.zh_inv[k] = d.zh_inv[k];
     memcpy(qa.alpha.v, args->alpha, 32);
     memcpy(qa.gamma.v, args->gamma, 32);
     qa.alpha2 = fe_sqr(qa.alpha);
@@ -205,7 +208,7 @@ int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t l
     qa.k0_is_one = qa.k[0] == Fr::one();
     launch_quotient_pointwise(qa, s);
     HIPCHK(hipGetLastError());
-    rc = ntt_run(ctx, t_out->d, log4, 1, g_limbs, /*sync=*/false);
+    rc = ntt_run(ctx, t_out->d, log4, 1, d.g_limbs, /*sync=*/false);
     return rc;
 }
 }  // namespace
@@ -395,6 +398,39 @@ int prover_open(typlonk_prover* p, const Fr* poly, uint64_t m, const Fr& z, Fr* 
     if (rc) return rc;
     return prover_fetch(p, y, 1);
 }
+// round 3's openings and evaluations (round3_openings) at ze and zw = ze * w in three launches, the results into `slots`' places
+int prover_open_round3(typlonk_prover* p, const CircuitEntry& ce, const Round3Slots& slots, bool with_quotients, const Fr& ze,
+                       const Fr& zw) {
+    Fr *blocks = nullptr, *res = nullptr;
+    const int rc = prover_ops_tmp(p, &blocks, &res);
+    if (rc) return rc;
+    const Fr* polys[8];
+    Fr* quots[8];
+    Fr* ys[8];
+    uint8_t zsel[8];
+    uint32_t cnt = 0;
+    const Round3Polys in{{p->co[0], p->co[1], p->co[2]}, p->z, p->has_pi ? p->pi : nullptr, p->q, ce.coef, p->n};
+    round3_openings(slots, with_quotients, in, [&](const Fr* poly, Fr* quot, int slot, uint8_t point) {
+        polys[cnt] = poly;
+        quots[cnt] = quot;
+        ys[cnt] = res + slot;
+        zsel[cnt++] = point;
+    });
+    launch_open_multi(polys, quots, ys, zsel, cnt, p->n, ze, zw, blocks, p->ctx->stream);
+    return hip_rc(p->ctx, hipGetLastError());
+}
+// r = sum_k scalar[k] * lin_polys[k] + constant into p->r, stream-ordered
+int prover_linearise(typlonk_prover* p, const CircuitEntry& ce, const Fr* scalar /* LIN_TERMS */, const Fr& constant) {
+    LincombArgs la{};
+    lin_polys(ce.coef, p->z, p->t, p->n, la.poly);
+    for (int k = 0; k < LIN_TERMS; ++k) la.scalar[k] = scalar[k];
+    la.constant = constant;
+    la.terms = LIN_TERMS;
+    la.out = p->r;
+    la.n = p->n;
+    launch_lincomb(la, p->ctx->stream);
+    return hip_rc(p->ctx, hipGetLastError());
+}
 }  // namespace
 
 namespace {
@@ -469,8 +505,7 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     // 0.3-0.5 ms per 2^20 proof here: they delay a commitment's start by the other columns' transforms, which were already
     // hidden beside the commitments' sorts, profiles/r06_ab_prover_ntt_batch.txt.)
     auto d2d = [&](Fr* dst, const Fr* src) -> int {
-        const hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(Fr), hipMemcpyDeviceToDevice, s);
-        return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
+        return hip_rc(ctx, hipMemcpyAsync(dst, src, n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
     };
     // a column into its place on the device: device -> device, or host -> device on the context's stream -- issued column by
     // column, each right before that column's transform and commitment are queued, so column i + 1 crosses PCIe while column i
@@ -480,11 +515,10 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
             hipError_t e = c.dev ? hipMemcpyAsync(dst, c.dev, c.rows * sizeof(Fr), hipMemcpyDeviceToDevice, s)
                                  : hipMemcpyAsync(dst, c.host, c.rows * sizeof(Fr), hipMemcpyHostToDevice, s);
             if (e == hipSuccess) e = hipMemsetAsync(dst + c.rows, 0, (n - c.rows) * sizeof(Fr), s);
-            return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
+            return hip_rc(ctx, e);
         }
         if (c.dev) return d2d(dst, c.dev);
-        const hipError_t e = hipMemcpyAsync(dst, c.host, n * sizeof(Fr), hipMemcpyHostToDevice, s);
-        return e == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(e));
+        return hip_rc(ctx, hipMemcpyAsync(dst, c.host, n * sizeof(Fr), hipMemcpyHostToDevice, s));
     };
     MsmQueue q(ctx, srs, /*first_lane=*/1);
     p->has_pi = pi_src.present();  // absent: public inputs [0] -> the zero polynomial
@@ -555,6 +589,24 @@ int typlonk_prover_round2(typlonk_prover* p, const uint64_t beta[4], const uint6
 }
 
 namespace {
+// The quotient t (proof.rs:139-145) into p->t, stream-ordered.  a, b, c, Z (and PI) were transformed to the coset domain in
+// rounds 1 and 2 (p->extended), so what is left is the pointwise kernel and one inverse transform.
+int prover_quotient(typlonk_prover* p, const Fr& alpha) {
+    const uint64_t n = p->n;
+    typlonk_buf b[5] = {{p->co[0], n}, {p->co[1], n}, {p->co[2], n}, {p->z, n}, {p->pi, n}};
+    typlonk_buf tb{p->t, 4 * n};
+    typlonk_quotient_args qa{};
+    for (int i = 0; i < 3; ++i) qa.wires[i] = &b[i];
+    qa.z = &b[3];
+    qa.public_inputs = p->has_pi ? &b[4] : nullptr;
+    memcpy(qa.alpha, alpha.v, 32);
+    memcpy(qa.beta, p->beta.v, 32);
+    memcpy(qa.gamma, p->gamma.v, 32);
+    for (int i = 0; i < 3; ++i) memcpy(qa.cosets[i], p->k[i].v, 32);
+    qa.circuit = p->circuit;
+    return quotient_run(p->ctx, &qa, p->log_n, &tb, p->extended);
+}
+
 // Round 3 in both shapes.  tail != NULL: the reference's six separate openings (proof.rs:147-175).
 // evals != NULL: evaluations only -- the quotients (p - p(zeta)) / (X - zeta) are not formed here; after
 // the caller has squeezed v from the evaluations, round4_batched opens a + v b + v^2 c + v^3 Z + v^4 r once.
@@ -582,10 +634,7 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     uint64_t xy[9][12];
     uint8_t inf[9];
     MsmQueue q(ctx, srs, /*first_lane=*/1);
-    struct WaitAll {
-        MsmQueue& q;
-        ~WaitAll() { (void)q.wait_all(); }
-    } wait_guard{q};
+    WaitAll wait_guard{q};
     // ---- openings of a, b, c at zeta; Z at zeta and zeta*w (proof.rs:147-163) ----
     Fr ev[6];
     const Fr w = fr_domain_root(log_n);
@@ -594,74 +643,28 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     const Fr one = Fr::one();
     Fr zn = ze, zh = one, l0z = one;   // zeta^n, Z_H(zeta), L0(zeta): filled under the kernels, before the wait
     {
-        // ONE synchronisation for everything evaluated here.  Result slots: 0..3 = a, b, c, Z at zeta (with their
-        // quotients unless batched), 4, 5 = sigma_0, sigma_1 and 6 = the public-input polynomial at zeta (for the
-        // linearisation, proof.rs:376-439, :138), 8 = Z at zeta*w (always with its quotient)
-        Fr host[9];
-        {
-            // all of them in three launches (launch_open_multi): quotients only where the proof shape opens separately
-            Fr *blocks = nullptr, *slots = nullptr;
-            rc = prover_ops_tmp(p, &blocks, &slots);
-            const Fr* polys[8];
-            Fr* quots[8];
-            Fr* ys[8];
-            uint8_t zsel[8];
-            uint32_t cnt = 0;
-            auto item = [&](const Fr* poly, Fr* quot, int slot, uint8_t at) {
-                polys[cnt] = poly;
-                quots[cnt] = quot;
-                ys[cnt] = slots + slot;
-                zsel[cnt++] = at;
-            };
-            for (int i = 0; i < 3; ++i) item(p->co[i], batched ? nullptr : p->q[i], i, 0);
-            item(p->z, batched ? nullptr : p->q[3], 3, 0);
-            item(ce.coef + 5 * n, nullptr, 4, 0);             // sigma_0
-            item(ce.coef + 6 * n, nullptr, 5, 0);             // sigma_1
-            if (p->has_pi) item(p->pi, nullptr, 6, 0);
-            item(p->z, p->q[4], 8, 1);                        // Z at zeta * w, always with its quotient
-            if (!rc) {
-                launch_open_multi(polys, quots, ys, zsel, cnt, n, ze, zw, blocks, ctx->stream);
-                const hipError_t he = hipGetLastError();
-                if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
-            }
-        }
-        // ---- quotient (proof.rs:139-145): queued behind the opening scans; a, b, c, Z (and PI) were transformed to the
-        // coset domain in rounds 1 and 2, so what is left is the pointwise kernel and one inverse transform ----
-        if (!rc) {
-            typlonk_buf b[5] = {{p->co[0], n}, {p->co[1], n}, {p->co[2], n}, {p->z, n}, {p->pi, n}};
-            typlonk_buf tb{p->t, 4 * n};
-            typlonk_quotient_args qa{};
-            for (int i = 0; i < 3; ++i) qa.wires[i] = &b[i];
-            qa.z = &b[3];
-            qa.public_inputs = p->has_pi ? &b[4] : nullptr;
-            memcpy(qa.alpha, alpha, 32);
-            memcpy(qa.beta, p->beta.v, 32);
-            memcpy(qa.gamma, p->gamma.v, 32);
-            for (int i = 0; i < 3; ++i) memcpy(qa.cosets[i], p->k[i].v, 32);
-            qa.circuit = p->circuit;
-            rc = quotient_run(ctx, &qa, log_n, &tb, p->extended);
-        }
+        // ONE synchronisation for everything evaluated here (REF_SLOTS): a, b, c, Z at zeta (with their quotients unless
+        // batched), sigma_0, sigma_1 and the public-input polynomial at zeta (for the linearisation, proof.rs:376-439, :138),
+        // Z at zeta*w (always with its quotient) -- all of them in three launches (launch_open_multi)
+        constexpr Round3Slots S = REF_SLOTS;
+        Fr host[S.count];
+        rc = prover_open_round3(p, ce, S, /*with_quotients=*/!batched, ze, zw);
+        // ---- quotient (proof.rs:139-145): queued behind the opening scans ----
+        if (!rc) rc = prover_quotient(p, al);
         // what the linearisation needs of zeta alone (one host inversion among it): while the kernels above run
         lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);
-        if (!rc) rc = prover_fetch(p, host, 9);
-        for (int i = 0; i < 4; ++i) ev[i] = host[i];
-        ev[4] = host[8];
-        s0 = host[4];
-        s1 = host[5];
-        if (p->has_pi) pi_z = host[6];
+        if (!rc) rc = prover_fetch(p, host, S.count);
+        for (int i = 0; i < 3; ++i) ev[i] = host[S.wire + i];
+        ev[3] = host[S.z];
+        ev[4] = host[S.zw];
+        s0 = host[S.sig0];
+        s1 = host[S.sig1];
+        if (p->has_pi) pi_z = host[S.pi];
     }
     if (!rc) {
-        LincombArgs la{};
-        lin_scalars(ev, s0, s1, pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, la.scalar, &la.constant);
-        const Fr* polys[LIN_TERMS] = {ce.coef + 0 * n, ce.coef + 1 * n, ce.coef + 2 * n, ce.coef + 3 * n, ce.coef + 4 * n,
-                                      p->z, ce.coef + 7 * n, p->t, p->t + n, p->t + 2 * n};
-        for (int k = 0; k < LIN_TERMS; ++k) la.poly[k] = polys[k];
-        la.terms = LIN_TERMS;
-        la.out = p->r;
-        la.n = n;
-        launch_lincomb(la, ctx->stream);
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        Fr scalar[LIN_TERMS], constant;
+        lin_scalars(ev, s0, s1, pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, scalar, &constant);
+        rc = prover_linearise(p, ce, scalar, constant);
     }
     // r(zeta) and its witness polynomial (proof.rs:175).  The reference shape does not wait for the value here: it is an
     // OUTPUT (and the r(zeta) != 0 check), nothing of this round's commitments depends on it -- it is read from its pinned slot
@@ -784,9 +787,7 @@ int typlonk_prover_round4_batched(typlonk_prover* p, const uint64_t v[4], typlon
     la.out = p->q[5];
     la.n = n;
     launch_lincomb(la, ctx->stream);
-    int rc = TYPLONK_OK;
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+    int rc = hip_rc(ctx, hipGetLastError());
     if (!rc) rc = prover_open_async(p, p->q[5], n, p->zeta, p->q[0], 0);  // F(zeta) itself is not needed: stream-ordered
     if (!rc) {
         // one batch: [t_lo], [t_mid], [t_hi] (proof.rs:181), the witness of Z at zeta*w, the batched witness at zeta
@@ -863,21 +864,12 @@ int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typ
         if (p) typlonk_prover_free(p);
         return rc;
     }
-    // (beta, gamma) <- H([a], [b], [c])                                                   proof.rs:111
-    ChallengeGenerator g;
-    for (int i = 0; i < 3; ++i) g.digest(out->commit_xy[i], out->commit_inf[i]);
-    uint64_t ch[8];
-    g.generate(2, ch);
-    memcpy(out->beta, ch, 32);
-    memcpy(out->gamma, ch + 4, 32);
+    RefScript script;   // the challenges of this shape, in its order (proof_script.hpp)
+    script.after_round1(*out);
     rc = typlonk_prover_round2(p, out->beta, out->gamma, cosets, out->z_xy, &out->z_inf);
     if (folds) rc = comm_fold(ctx, out->z_xy, &out->z_inf, 1, rc);
     if (!rc) {
-        // (alpha, zeta) <- H([a], [b], [c], [Z])                                          proof.rs:133-136
-        g.digest(out->z_xy, out->z_inf);
-        g.generate(2, ch);
-        memcpy(out->alpha, ch, 32);
-        memcpy(out->zeta, ch + 4, 32);
+        script.after_round2(*out);
         rc = typlonk_prover_round3(p, out->alpha, out->zeta, &out->tail);
         if (folds) {   // (an unsatisfied witness, r(zeta) != 0, is the same on every rank: the points are still folded)
             const int round_rc = rc;
@@ -909,14 +901,13 @@ namespace {
 // folds (an SRS shard on a context with a communicator): the two groups of commitments are folded over the ranks where the
 // host needs them -- [t_lo] [t_mid] [t_hi] before zeta (3 records), W_zeta and W_zeta_w at the end (2 records).  A rank that
 // fails joins the NEXT of the two collectives with flagged records and returns there, as its peers do (comm_fold).
-int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al, typlonk_proof_compact* out, bool folds) {
+int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proof_compact* out, bool folds) {
     typlonk_ctx* ctx = p->ctx;
     // every way out before zeta / after zeta: through that stage's collective when folding
     auto leave_t = [&](int rc) { return folds ? comm_fold(ctx, &out->t_xy[0][0], out->t_inf, 3, rc) : rc; };
     auto leave_w = [&](int rc) { return folds ? comm_fold(ctx, &out->w_xy[0][0], out->w_inf, 2, rc) : rc; };
-    auto hip_rc = [&](hipError_t he) { return he == hipSuccess ? TYPLONK_OK : fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)); };
     if (p->round != 2) return leave_t(fail(ctx, TYPLONK_ERR_INVALID_ARG, "round3 must follow round2"));
-    int rc = hip_rc(hipSetDevice(ctx->device));
+    int rc = hip_rc(ctx, hipSetDevice(ctx->device));
     if (rc) return leave_t(rc);
     auto cit = ctx->circuits.find(p->circuit);
     if (cit == ctx->circuits.end()) return leave_t(fail(ctx, TYPLONK_ERR_INVALID_ARG, "circuit was freed during the proof"));
@@ -927,35 +918,21 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
     ProverRound in_round(ctx);
     const SrsEntry* srs = nullptr;
     rc = msm_validate(ctx, p->srs_id, n, &srs);
-    if (!rc && !ctx->batch_fence) rc = hip_rc(hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
+    if (!rc && !ctx->batch_fence) rc = hip_rc(ctx, hipEventCreateWithFlags(&ctx->batch_fence, hipEventDisableTiming));
     if (rc) return leave_t(rc);
     // the queue outlives every early return (its destructor-side wait below): the MSMs write into `out`
     MsmQueue q(ctx, srs, /*first_lane=*/0);
-    struct WaitAll {
-        MsmQueue& q;
-        ~WaitAll() { (void)q.wait_all(); }
-    } wait_guard{q};
+    WaitAll wait_guard{q};
     auto record_fence = [&]() -> int {
-        const hipError_t he = hipEventRecord(ctx->batch_fence, ctx->stream);
-        if (he != hipSuccess) return fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        const int frc = hip_rc(ctx, hipEventRecord(ctx->batch_fence, ctx->stream));
+        if (frc) return frc;
         q.fence = ctx->batch_fence;   // the lanes wait for what is queued NOW, not for later work on the context's stream
         return TYPLONK_OK;
     };
     // ---- the quotient (proof.rs:139-145) as soon as alpha is known; its three slices (:181) committed behind a fence ----
-    {
-        typlonk_buf b[5] = {{p->co[0], n}, {p->co[1], n}, {p->co[2], n}, {p->z, n}, {p->pi, n}};
-        typlonk_buf tb{p->t, 4 * n};
-        typlonk_quotient_args qa{};
-        for (int i = 0; i < 3; ++i) qa.wires[i] = &b[i];
-        qa.z = &b[3];
-        qa.public_inputs = p->has_pi ? &b[4] : nullptr;
-        memcpy(qa.alpha, al.v, 32);
-        memcpy(qa.beta, p->beta.v, 32);
-        memcpy(qa.gamma, p->gamma.v, 32);
-        for (int i = 0; i < 3; ++i) memcpy(qa.cosets[i], p->k[i].v, 32);
-        qa.circuit = p->circuit;
-        rc = quotient_run(ctx, &qa, log_n, &tb, p->extended);
-    }
+    Fr al;
+    memcpy(al.v, out->alpha, 32);
+    rc = prover_quotient(p, al);
     if (!rc) rc = record_fence();
     if (!rc) {
         const Fr* polys[3] = {p->t, p->t + n, p->t + 2 * n};
@@ -969,62 +946,28 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
     rc = leave_t(rc);   // collective 3 of a sharded proof
     if (rc) return rc;
     // ---- zeta binds the quotient ----
-    for (int i = 0; i < 3; ++i) tr.point(out->t_xy[i], out->t_inf[i]);
-    const Fr ze = tr.squeeze('z');
+    const Fr ze = script.after_quotient(*out);
     const Fr zw = fe_mul(ze, fr_domain_root(log_n));
-    // ---- a, b, c, Z, sigma_1, sigma_2, PI at zeta and Z at zeta*w with its quotient: one launch_open_multi, one fetch.
-    // Result slots 0..6 = the seven evaluations of the proof in order, 7 = PI(zeta) ----
-    Fr host[8];
+    // ---- a, b, c, Z, sigma_1, sigma_2, PI at zeta and Z at zeta*w with its quotient: three launches, one fetch
+    // (COMPACT_SLOTS: the first seven slots are the proof's evaluations in order) ----
+    constexpr Round3Slots S = COMPACT_SLOTS;
+    Fr host[S.count];
     Fr zn, zh, l0z;
-    {
-        Fr *blocks = nullptr, *slots = nullptr;
-        rc = prover_ops_tmp(p, &blocks, &slots);
-        if (rc) return leave_w(rc);
-        const Fr* polys[8];
-        Fr* quots[8];
-        Fr* ys[8];
-        uint8_t zsel[8];
-        uint32_t cnt = 0;
-        auto item = [&](const Fr* poly, Fr* quot, int slot, uint8_t at) {
-            polys[cnt] = poly;
-            quots[cnt] = quot;
-            ys[cnt] = slots + slot;
-            zsel[cnt++] = at;
-        };
-        for (int i = 0; i < 3; ++i) item(p->co[i], nullptr, i, 0);
-        item(p->z, nullptr, 3, 0);
-        item(ce.coef + 5 * n, nullptr, 5, 0);             // sigma_1
-        item(ce.coef + 6 * n, nullptr, 6, 0);             // sigma_2
-        if (p->has_pi) item(p->pi, nullptr, 7, 0);
-        item(p->z, p->q[4], 4, 1);                        // Z at zeta * w, with its quotient
-        launch_open_multi(polys, quots, ys, zsel, cnt, n, ze, zw, blocks, ctx->stream);
-        const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return leave_w(fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)));
-        lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);   // while the kernels run
-        rc = prover_fetch(p, host, 8);
-        if (rc) return leave_w(rc);
-    }
-    const Fr pi_z = p->has_pi ? host[7] : Fr::zero();
-    for (int i = 0; i < 7; ++i) {
-        memcpy(out->evals[i], host[i].v, 32);
-        tr.scalar(out->evals[i]);
-    }
-    const Fr v = tr.squeeze('v');
-    memcpy(out->zeta, ze.v, 32);
-    memcpy(out->v, v.v, 32);
+    rc = prover_open_round3(p, ce, S, /*with_quotients=*/false, ze, zw);
+    if (rc) return leave_w(rc);
+    lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);   // while the kernels run
+    rc = prover_fetch(p, host, S.count);
+    if (rc) return leave_w(rc);
+    const Fr pi_z = p->has_pi ? host[S.pi] : Fr::zero();
+    for (int i = 0; i < 7; ++i) memcpy(out->evals[i], host[i].v, 32);
+    const Fr v = script.after_evals(*out);
     // ---- r (proof.rs:376-439, with +PI(zeta) as typlonk_prove); r(zeta) lands in slot 0 and is read after the commitments ----
     {
-        LincombArgs la{};
-        lin_scalars(host, host[5], host[6], pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, la.scalar, &la.constant);
-        const Fr* polys[LIN_TERMS] = {ce.coef + 0 * n, ce.coef + 1 * n, ce.coef + 2 * n, ce.coef + 3 * n, ce.coef + 4 * n,
-                                      p->z, ce.coef + 7 * n, p->t, p->t + n, p->t + 2 * n};
-        for (int k = 0; k < LIN_TERMS; ++k) la.poly[k] = polys[k];
-        la.terms = LIN_TERMS;
-        la.out = p->r;
-        la.n = n;
-        launch_lincomb(la, ctx->stream);
-        const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return leave_w(fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he)));
+        static_assert(S.wire == 0 && S.z == 3 && S.zw == 4, "lin_scalars reads a, b, c, Z, Z(zeta w) as ev[0..4]");
+        Fr scalar[LIN_TERMS], constant;
+        lin_scalars(host, host[S.sig0], host[S.sig1], pi_z, p->beta, p->gamma, p->k, al, ze, zn, zh, l0z, scalar, &constant);
+        rc = prover_linearise(p, ce, scalar, constant);
+        if (rc) return leave_w(rc);
     }
     rc = prover_open_async(p, p->r, n, ze, nullptr, 0);
     // ---- F as one 7-term combination in q[1], its witness polynomial in q[0] (q[0..3] are free in this shape) ----
@@ -1042,8 +985,7 @@ int prover_round3_compact(typlonk_prover* p, CompactTranscript& tr, const Fr& al
         fa.out = p->q[1];
         fa.n = n;
         launch_lincomb(fa, ctx->stream);
-        const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        rc = hip_rc(ctx, hipGetLastError());
     }
     if (!rc) rc = prover_open_async(p, p->q[1], n, ze, p->q[0], 1);   // F(zeta) itself is not needed
     // ---- W_zeta and W_zeta_w in one queue ----
@@ -1132,7 +1074,7 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
         pi_vals.resize(4 * pi_len);
         hipError_t he = hipMemcpyAsync(pi_vals.data(), pi.dev, pi_len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-        if (he != hipSuccess) rc = fail(ctx, TYPLONK_ERR_HIP, hipGetErrorString(he));
+        rc = hip_rc(ctx, he);
         piv = pi_vals.data();
     }
     if (rc && !folds) return rc;
@@ -1163,18 +1105,13 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
         if (p) typlonk_prover_free(p);
         return rc;
     }
-    CompactTranscript tr(d0);
-    for (int i = 0; i < 3; ++i) tr.point(out->commit_xy[i], out->commit_inf[i]);
-    const Fr beta = tr.squeeze('b'), gamma = tr.squeeze('g');
-    memcpy(out->beta, beta.v, 32);
-    memcpy(out->gamma, gamma.v, 32);
+    CompactScript script(d0);   // (a sharded proof has d0 only now, from the folded key)
+    script.after_round1(*out);
     rc = typlonk_prover_round2(p, out->beta, out->gamma, cosets, out->z_xy, &out->z_inf);
     if (folds) rc = comm_fold(ctx, out->z_xy, &out->z_inf, 1, rc);   // collective 2
     if (!rc) {
-        tr.point(out->z_xy, out->z_inf);
-        const Fr alpha = tr.squeeze('a');
-        memcpy(out->alpha, alpha.v, 32);
-        rc = prover_round3_compact(p, tr, alpha, out, folds);   // collectives 3 and 4
+        script.after_round2(*out);
+        rc = prover_round3_compact(p, script, out, folds);   // collectives 3 and 4
     }
     typlonk_prover_free(p);
     return rc;

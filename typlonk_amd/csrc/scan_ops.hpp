@@ -1,5 +1,7 @@
-// Device pieces shared by the prover's scan kernels (plonk_ops.hip: one proof; prove_batch.hip: a wave of proofs, the proof
-// index in blockIdx.y): 32-byte loads / stores, the product scan over Fr and the Horner suffix scan of open().
+// Device bodies shared by the prover's kernels for one proof (plonk_ops.hip, quotient.hip) and for a wave of proofs
+// (prove_batch.hip, the proof index in blockIdx.y): 32-byte loads / stores, the product scan over Fr, the grand product's
+// row term, the three stages of open() and the quotient's formula at one coset point.  The kernels around them differ only
+// in where their operands come from: by-value arguments for one proof, device tables for a wave.
 #pragma once
 #include "launch.hpp"
 
@@ -157,5 +159,87 @@ __device__ __forceinline__ Fr open_top_rounds(Fr* blocks, uint32_t nblk, const F
         __syncthreads();   // the next round's horner_block overwrites the LDS this one's lds[0] / carries came from
     }
     return run;
+}
+
+// One opening (q != null: y = p(z) and the m - 1 coefficients of (p - y) / (X - z)) or evaluation (q == null) of an
+// m-coefficient polynomial: zpow = the 32 powers z^(2^k), carries = one Fr per 2048-coefficient workgroup.
+struct OpenItem {
+    const Fr* c;
+    Fr* q;
+    Fr* y;
+    const Fr* zpow;
+    Fr* carries;
+};
+// sweep 1 (one workgroup per 2048 coefficients): H at the start of every workgroup assuming a zero carry
+__device__ __forceinline__ void open_block_stage(const OpenItem& it, uint64_t m, Fr* lds) {
+    Fr loc[8], ci;
+    const Fr g0 = horner_block(it.c, m, (uint64_t)blockIdx.x * 2048, Fr::zero(), it.zpow, 0, lds, loc, &ci);
+    if (threadIdx.x == 0) p_st(it.carries + blockIdx.x, g0);
+}
+// top stage (one workgroup): the true carries when a second sweep follows (store); otherwise p(z) = sum_b A_b (z^2048)^b
+// is complete here and goes to y
+__device__ __forceinline__ void open_top_stage(const OpenItem& it, uint32_t nblk, bool store, Fr* lds) {
+    const Fr y = open_top_rounds(it.carries, nblk, it.zpow, store, lds);
+    if (!store && threadIdx.x == 0) p_st(it.y, y);
+}
+// sweep 2: seeded with the true carry; writes y and, where there is one, q
+__device__ __forceinline__ void open_finish_stage(const OpenItem& it, uint64_t m, Fr* lds) {
+    Fr loc[8], ci;
+    const uint64_t base = (uint64_t)blockIdx.x * 2048;
+    const Fr seed = p_ld(it.carries + blockIdx.x);
+    horner_block(it.c, m, base, seed, it.zpow, 0, lds, loc, &ci);
+    const Fr z = it.zpow[0];
+    Fr h = ci;
+    const uint64_t s0 = base + (uint64_t)threadIdx.x * 8;
+    for (int e = 7; e >= 0; --e) {
+        const uint64_t i = s0 + e;
+        h = fe_add(loc[e], fe_mul(z, h));  // H_i
+        if (i < m) {
+            if (i == 0) p_st(it.y, h);
+            else if (it.q) p_st(it.q + i - 1, h);
+        }
+    }
+}
+
+// ---- grand product: row j's term and the finish -------------------------------------------------------------------
+// num_j = prod_i (w_ij + beta k_i x_j + gamma),  den_j = prod_i (w_ij + beta sigma_ij + gamma),  x_j = w^j: wire i's factors of
+// both, multiplied into num and den (which start at one).  w, sigma: where w_ij and sigma_ij lie; kbeta = k_i * beta.
+__device__ __forceinline__ void gp_term(const Fr* w, const Fr* sigma, const Fr& x, const Fr& beta, const Fr& gamma, const Fr& kbeta,
+                                        Fr& num, Fr& den) {
+    const Fr wg = fe_add(p_ld(w), gamma);
+    num = fe_mul(num, fe_add(wg, fe_mul(kbeta, x)));
+    den = fe_mul(den, fe_add(wg, fe_mul(beta, p_ld(sigma))));
+}
+// Z_j = N_j * S_j * S_0^-1 (N: exclusive prefix products of the numerators, S: suffix products of the denominators)
+__device__ __forceinline__ Fr gp_finish(const Fr& nprefix, const Fr& dsuffix, const Fr& inv_total) {
+    return fe_mul(fe_mul(nprefix, dsuffix), inv_total);
+}
+
+// ---- the quotient at one point x of the 4n coset (the formula is in quotient.hip's header) -------------------------
+// Everything is the value AT the point: the wires, Z and Z(w x), the selectors q_l q_r q_o q_m q_c, the sigmas, L0;
+// pi: where PI's value lies, null for the zero polynomial; bx = beta * x; zh_inv = 1 / (x^n - 1).
+__device__ __forceinline__ Fr quotient_point(const Fr& wa, const Fr& wb, const Fr& wc, const Fr& z, const Fr& zw, const Fr* pi,
+                                             const Fr (&sel)[5], const Fr (&sigma)[3], const Fr& l0, const Fr& bx, const Fr* k,
+                                             bool k0_is_one, const Fr& beta, const Fr& gamma, const Fr& alpha, const Fr& alpha2,
+                                             const Fr& zh_inv) {
+    // gate constraint
+    Fr line1 = fe_mul(sel[0], wa);
+    line1 = fe_add(line1, fe_mul(sel[1], wb));
+    line1 = fe_sub(line1, fe_mul(sel[2], wc));
+    line1 = fe_add(line1, fe_mul(fe_mul(sel[3], wa), wb));
+    line1 = fe_add(line1, sel[4]);
+    if (pi) line1 = fe_add(line1, p_ld(pi));
+    Fr l2 = fe_add(fe_add(wa, k0_is_one ? bx : fe_mul(k[0], bx)), gamma);
+    l2 = fe_mul(l2, fe_add(fe_add(wb, fe_mul(k[1], bx)), gamma));
+    l2 = fe_mul(l2, fe_add(fe_add(wc, fe_mul(k[2], bx)), gamma));
+    l2 = fe_mul(l2, z);
+    Fr l3 = fe_add(fe_add(wa, fe_mul(beta, sigma[0])), gamma);
+    l3 = fe_mul(l3, fe_add(fe_add(wb, fe_mul(beta, sigma[1])), gamma));
+    l3 = fe_mul(l3, fe_add(fe_add(wc, fe_mul(beta, sigma[2])), gamma));
+    l3 = fe_mul(l3, zw);
+    const Fr l4 = fe_mul(fe_sub(z, Fr::one()), l0);
+    Fr t = fe_add(line1, fe_mul(alpha, fe_sub(l2, l3)));
+    t = fe_add(t, fe_mul(alpha2, l4));
+    return fe_mul(t, zh_inv);
 }
 }  // namespace ty
