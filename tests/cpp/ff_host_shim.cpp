@@ -6,6 +6,7 @@
 #include "../../typlonk_amd/csrc/g1_host64.hpp"
 #include "../../typlonk_amd/csrc/fr_inv.hpp"
 #include "../../typlonk_amd/csrc/transcript.hpp"
+#include "../../typlonk_amd/csrc/lin_commit.hpp"
 #include <string.h>
 using namespace ty;
 
@@ -185,6 +186,15 @@ int shim_h64_chain(const uint32_t* pts, int n, int ndbl, const uint32_t* z, uint
 void shim_stdrng_words(const uint32_t key[8], uint64_t* out, int n) {   // StdRng::from_seed(key) -> n x next_u64
     ty::StdRng r = ty::StdRng::from_key(key);
     for (int i = 0; i < n; ++i) out[i] = r.next_u64();
+}
+// the verifiers' linearisation commitment as scalars on its eleven bases (csrc/lin_commit.hpp).  in: 15 Fr of 8 words each --
+// a b c Z(zeta w) sigma_1 sigma_2 alpha beta gamma zeta zeta^n k_0 k_1 k_2 pi_signed; out: LIN_BASES Fr in LinBase order
+void shim_lin_commit_scalars(const uint32_t* in, uint64_t n, uint32_t* out) {
+    auto f = [&](int i) { return ld<Fr>(in + 8 * i); };
+    const LinCommitIn lc{f(0), f(1), f(2), f(3), {f(4), f(5)}, f(6), f(7), f(8), f(9), f(10), n, {f(11), f(12), f(13)}, f(14)};
+    Fr r[LIN_BASES];
+    lin_commit_scalars(lc, r);
+    for (int i = 0; i < LIN_BASES; ++i) st(out + 8 * i, r[i]);
 }
 void shim_seed_from_u64(uint64_t state, uint32_t key_out[8]) {          // rand_core SeedableRng::seed_from_u64 expansion
     ty::StdRng r(state);

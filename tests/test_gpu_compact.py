@@ -362,6 +362,29 @@ def test_mixed_batch_rejects_exactly_the_tampered_proofs(ctx, chain12):
     assert "verify_eval" not in prof and {"verify_host", "verify_msm", "verify_pairing"} <= set(prof)
 
 
+def test_bisection_schedule_is_the_replayed_one(ctx, chain12):
+    """three rejected proofs and one that never enters the fold (a non-canonical evaluation), 16 proofs: the verdicts, and
+    exactly the folds of verify_ref.bisection_folds -- four levels of splitting"""
+    import verify_ref as V
+
+    c = chain12
+    batch = list(c.proofs[:16])
+    batch[1] = _tamper_point(c.proofs[1], "witness", 0)
+    batch[9] = dict(c.proofs[9], evals=[_limbs(7)] + c.proofs[9]["evals"][1:])
+    batch[15] = _tamper_point(c.proofs[15], "t_commit", 2)
+    batch[4] = dict(_tampered(c.proofs[4]))["non_canonical"]
+    ctx.set_profiling(1)
+    try:
+        got = ctx.verify_compact(c.vk, batch)
+        prof = dict(ctx.profile())
+    finally:
+        ctx.set_profiling(0)
+    assert got.tolist() == [k not in (1, 4, 9, 15) for k in range(16)]
+    want = V.bisection_folds([k != 4 for k in range(16)], [k in (1, 9, 15) for k in range(16)])
+    print("verify_folds", prof["verify_folds"], "replayed", want)
+    assert prof["verify_folds"] == want
+
+
 def test_fresh_context_needs_only_the_vk(built, chain12):
     """a context with no SRS and no circuit: the vk travels as bytes"""
     import typlonk_amd

@@ -292,6 +292,29 @@ def test_several_bad_proofs_in_one_batch(chain5):
     assert not c.verify([batch[1], batch[9]]).any()
 
 
+def test_bisection_schedule_is_the_replayed_one(ctx, chain5):
+    """three rejected proofs and one that never enters the fold (off the curve), 16 proofs: the verdicts, and exactly the
+    folds of verify_ref.bisection_folds -- four levels of splitting"""
+    import verify_ref as V
+
+    c = chain5
+    batch = list(c.proofs)
+    batch[1] = _tamper_point(c.proofs[1], "witness", 5)
+    batch[9] = dict(c.proofs[9], evals=[_limbs(7)] + c.proofs[9]["evals"][1:])
+    batch[15] = _tamper_point(c.proofs[15], "t_commit", 2)
+    batch[4] = dict(_tampered(c.proofs[4]))["off_curve"]
+    ctx.set_profiling(1)
+    try:
+        got = c.verify(batch)
+        prof = dict(ctx.profile())
+    finally:
+        ctx.set_profiling(0)
+    assert got.tolist() == [k not in (1, 4, 9, 15) for k in range(16)]
+    want = V.bisection_folds([k != 4 for k in range(16)], [k in (1, 9, 15) for k in range(16)])
+    print("verify_folds", prof["verify_folds"], "replayed", want)
+    assert prof["verify_folds"] == want
+
+
 def test_wrong_circuit_or_wrong_g2s_rejects(ctx, chain5):
     c = chain5
     # another circuit of the same size: the identity permutation instead of the chain's copy constraints

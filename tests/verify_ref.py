@@ -104,3 +104,19 @@ def batch_verify(checks_by_proof, live, rho, g2s, stats=None):
 
     decide([k for k in range(len(checks_by_proof)) if live[k]])
     return ok
+
+
+def bisection_folds(live, bad) -> int:
+    """how many folds the verifiers' bisection makes (csrc/verify.hip, FoldBisect::decide), replayed without any arithmetic:
+    a range with no live proof is skipped; otherwise one fold, which passes iff no bad live proof is in the range; a failed
+    fold over more than one live proof splits the range so that its first floor(live / 2) live proofs go left"""
+    def decide(lo, hi):
+        members = [k for k in range(lo, hi) if live[k]]
+        if not members:
+            return 0
+        if len(members) == 1 or not any(bad[k] for k in members):
+            return 1
+        mid = members[len(members) // 2]
+        return 1 + decide(lo, mid) + decide(mid, hi)
+
+    return decide(0, len(live))

@@ -6,7 +6,8 @@
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove; the steps it shares with prove_batch.hip
 //                 (declared below: coset_g, quotient_domain, round3_openings, lin_*); transcripts: proof_script.hpp
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
-//   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip)
+//   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip); which scalars and
+//                 points they and the wire format admit: host_checks.hpp; the linearisation commitment: lin_commit.hpp
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
@@ -23,6 +24,12 @@
 #include <map>
 #include <string>
 #include <vector>
+
+namespace typlonk {
+namespace pairing {
+struct G2Affine;   // host/pairing_host.hpp
+}
+}  // namespace typlonk
 
 namespace tyh {
 using namespace ty;
@@ -438,12 +445,17 @@ int circuit_commitments(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, 
 // commitments (cached per (circuit, SRS) like the above) and its P0 record -- the point on the rank that holds index 0, the
 // identity elsewhere.  Local: no collective inside.
 int circuit_statement_partial(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, uint64_t xy[9][12], uint8_t inf[9]);
-// a verifying key without [s]G2 (zero): log_n, cosets, the eight commitments, SRS point 0 (whole SRS)
+// THE assembly of a verifying key without [s]G2 (zero) from log_n, the cosets and the statement's nine records: the eight
+// commitments, then SRS point 0 (whole, or folded over the ranks)
+void vk_assemble(uint32_t log_n, const uint64_t cosets[3][4], const uint64_t (*rec_xy)[12], const uint8_t* rec_inf, typlonk_vk* vk);
+// that key of a circuit over a whole SRS
 int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t cosets[3][4], typlonk_vk* vk);
 // what typlonk_verify_compact refuses before it looks at a proof, in its order and with its codes: log_n outside 1..24, a
 // pi_len[k] > n or a null pi[k] with pi_len[k] != 0, a g2s off the twist, a vk point off the curve, a non-canonical coset
-// (typlonk_verify_compact_bytes judges its arguments by the same function, before it decodes anything)
-int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len);
+// (typlonk_verify_compact_bytes judges its arguments by the same function, before it decodes anything).  *g2s = the key's
+// [s]G2 as parsed.
+int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len,
+                              typlonk::pairing::G2Affine* g2s);
 
 // ---- witness_check.hip ----------------------------------------------------------------------------------------------
 // frees a circuit's recovered permutation and selector evaluations (typlonk_circuit_free, typlonk_destroy)

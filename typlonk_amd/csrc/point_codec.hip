@@ -4,7 +4,7 @@
 #include "host.hpp"
 #include "msm_common.hpp"
 #include "point_codec.hpp"
-#include "../host/pairing_host.hpp"
+#include "host_checks.hpp"
 
 using namespace ty;
 using namespace tyh;
@@ -84,18 +84,6 @@ const char* class_name(uint32_t cls) {
     return "unknown";
 }
 
-bool fr_canonical(const uint64_t* l) {
-    static const uint64_t R[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
-    for (int i = 3; i >= 0; --i)
-        if (l[i] != R[i]) return l[i] < R[i];
-    return false;
-}
-bool fq_canonical(const uint64_t* l) {
-    for (int i = 5; i >= 0; --i)
-        if (l[i] != h64::P[i]) return l[i] < h64::P[i];
-    return false;
-}
-
 // ---- host path of the point codec ----
 void host_decode(const uint8_t* in, size_t count, bool check_subgroup, uint64_t* xy, uint8_t* inf, uint8_t* status) {
     for (size_t i = 0; i < count; ++i) {
@@ -125,17 +113,6 @@ bool host_encode(const uint64_t* xy, uint8_t inf, uint8_t* out) {
     g1_encode(a, raw);
     memcpy(out, raw, 48);
     return true;
-}
-bool host_on_curve(const uint64_t* xy, uint8_t inf) {
-    if (inf) return true;
-    if (!fq_canonical(xy) || !fq_canonical(xy + 6)) return false;
-    h64::Fq x, y;
-    memcpy(x.v, xy, 48);
-    memcpy(y.v, xy + 6, 48);
-    const P::Fq four32 = P::fq_from_u64(4);
-    h64::Fq four;
-    memcpy(four.v, four32.v, 48);
-    return h64::eq(h64::mul(y, y), h64::add(h64::mul(h64::mul(x, x), x), four));
 }
 
 // ---- Fr ----
@@ -250,16 +227,6 @@ void fq_to_be(const P::Fq& a, uint8_t* out) {
     memcpy(l, c.v, 48);
     for (int i = 0; i < 6; ++i)
         for (int b = 0; b < 8; ++b) out[8 * (5 - i) + b] = (uint8_t)(l[i] >> (8 * (7 - b)));
-}
-bool g2_from_limbs(const uint64_t g2s_xy[24], P::G2Affine* q) {
-    for (int i = 0; i < 24; i += 6)
-        if (!fq_canonical(g2s_xy + i)) return false;
-    memcpy(q->x.a.v, g2s_xy, 48);
-    memcpy(q->x.b.v, g2s_xy + 6, 48);
-    memcpy(q->y.a.v, g2s_xy + 12, 48);
-    memcpy(q->y.b.v, g2s_xy + 18, 48);
-    q->infinity = false;
-    return P::g2_is_on_curve(*q);
 }
 void g2_encode(const P::G2Affine& q, uint8_t out[96]) {
     fq_to_be(q.x.b, out);
@@ -438,7 +405,7 @@ int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t o
     proof_points(p, pts);
     uint8_t buf[TYPLONK_PROOF_COMPACT_BYTES];
     for (int i = 0; i < PROOF_POINTS; ++i) {
-        if (!host_on_curve(pts[i].xy, *pts[i].inf) || !host_encode(pts[i].xy, *pts[i].inf, buf + 48 * i)) return TYPLONK_ERR_INVALID_ARG;
+        if (!g1_on_curve(pts[i].xy, *pts[i].inf) || !host_encode(pts[i].xy, *pts[i].inf, buf + 48 * i)) return TYPLONK_ERR_INVALID_ARG;
     }
     for (int i = 0; i < PROOF_SCALARS; ++i)
         if (!fr_encode(p.evals[i], buf + 48 * PROOF_POINTS + 32 * i)) return TYPLONK_ERR_INVALID_ARG;
@@ -457,7 +424,7 @@ int typlonk_vk_to_bytes(const typlonk_vk* vk, uint8_t out[TYPLONK_VK_WIRE_BYTES]
     for (int i = 0; i < 9; ++i, p += 48) {
         const uint64_t* xy = i < 8 ? vk->commit_xy[i] : vk->srs0_xy;
         const uint8_t inf = i < 8 ? vk->commit_inf[i] : vk->srs0_inf;
-        if (!host_on_curve(xy, inf) || !host_encode(xy, inf, p)) return TYPLONK_ERR_INVALID_ARG;
+        if (!g1_on_curve(xy, inf) || !host_encode(xy, inf, p)) return TYPLONK_ERR_INVALID_ARG;
     }
     P::G2Affine q;
     if (!g2_from_limbs(vk->g2s_xy, &q)) return TYPLONK_ERR_INVALID_ARG;
@@ -545,7 +512,8 @@ int typlonk_verify_compact_bytes(typlonk_ctx* ctx, const typlonk_vk* vk, const u
     if (!vk || !bytes || !ok) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     memset(ok, 0, count);
     // the key and the public-input arguments, as the verifier judges them: whichever proofs decode
-    int rc = verify_compact_check_args(ctx, vk, count, pi, pi_len);
+    P::G2Affine g2s;
+    int rc = verify_compact_check_args(ctx, vk, count, pi, pi_len, &g2s);
     if (rc) return rc;
     std::vector<typlonk_proof_compact> all(count);
     std::vector<uint32_t> st(count);

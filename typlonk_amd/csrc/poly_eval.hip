@@ -9,6 +9,7 @@
 // sums the chunk partials of every (polynomial, point).  Field arithmetic is exact, so the result is the same element
 // whatever the chunking: Horner's value, bit for bit.
 #include "host.hpp"
+#include "host_checks.hpp"
 
 using namespace ty;
 using namespace tyh;
@@ -103,13 +104,6 @@ __global__ __launch_bounds__(256) void poly_eval_sum_kernel(const Fr* part, uint
         __syncthreads();
     }
     if (threadIdx.x == 0) pe_st(out + (uint64_t)p * out_stride + k, red[0]);
-}
-
-bool fr_canonical(const uint64_t* l) {
-    static const uint64_t R[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
-    for (int i = 3; i >= 0; --i)
-        if (l[i] != R[i]) return l[i] < R[i];
-    return false;
 }
 
 }  // namespace

@@ -1091,13 +1091,7 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
         if (!rc) {
             memcpy(out->commit_xy, rec_xy, 3 * 96);
             memcpy(out->commit_inf, rec_inf, 3);
-            memset(&vk, 0, sizeof(vk));
-            vk.log_n = p->log_n;
-            memcpy(vk.cosets, cosets, sizeof(vk.cosets));
-            memcpy(vk.commit_xy, rec_xy + 3, sizeof(vk.commit_xy));
-            memcpy(vk.commit_inf, rec_inf + 3, sizeof(vk.commit_inf));
-            memcpy(vk.srs0_xy, rec_xy[11], sizeof(vk.srs0_xy));
-            vk.srs0_inf = rec_inf[11];
+            vk_assemble(p->log_n, cosets, rec_xy + 3, rec_inf + 3, &vk);
             compact_statement_digest(vk, piv, pi_len, d0);
         }
     }

@@ -18,6 +18,7 @@
 //   gate       fr30_mul(q, a) = q a * 2^242 for two data words, so every term is brought to the factor 2^242:
 //              q_m a b = fr30_mul(fr30_mul(fr30_mul(a, b), 2^284), q_m),   q_c + PI -> fr30_mul(q_c + PI, 2^256)
 #include "host.hpp"
+#include "host_checks.hpp"
 #include "fr30.hpp"
 #include "scan_ops.hpp"
 
@@ -222,11 +223,6 @@ Fr30 to_limbs30(const Fr& x) {
     }
     return r;
 }
-bool fr_canonical(const Fr& x) {
-    for (int i = 7; i >= 0; --i)
-        if (x.v[i] != FrParams::mod(i)) return x.v[i] < FrParams::mod(i);
-    return false;
-}
 
 void free_check_cache(CircuitEntry& e) {
     (void)hipFree(e.perm);
@@ -244,7 +240,7 @@ int ensure_perm(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]) 
     for (int i = 0; i < 3; ++i) {
         Fr k;
         memcpy(k.v, cosets[i], sizeof(k.v));
-        if (!fr_canonical(k)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "coset is not a canonical residue");
+        if (!fr_canonical(cosets[i])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "coset is not a canonical residue");
         a.kinv[i] = to_limbs30(fe_mul(fe_inv(k), fr_from_u64(1u << 28)));
     }
     const Fr c14 = fr_from_u64(1u << 14);
