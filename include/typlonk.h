@@ -240,7 +240,9 @@ int typlonk_ntt_fr_batch_devptr(typlonk_ctx* ctx, void* const* d_data, size_t co
  *   check cache (5 n Fr + 12 n B)          0.7 GiB    1.3 GiB    2.7 GiB   per circuit, only once typlonk_witness_check /
  *                                                                           typlonk_circuit_permutation has run on it: the
  *                                                                           selector evaluations and the 3n-entry permutation
- *                                                                           (160 MiB + 12 MiB at 2^20); not in the total
+ *                                                                           (160 MiB + 12 MiB at 2^20); not in the total.
+ *                                                                           A circuit made by typlonk_circuit_compile holds the
+ *                                                                           12 n-byte permutation from the start
  * typlonk_prove_batch keeps one wave's arena in prover_mem instead (39 n Fr per proof in flight, one proof per wave here):
  *   prover_mem (39 n Fr)                   4.9 GiB    9.8 GiB   19.5 GiB   (quot_ext is not used by a batch)
  *   ops_tmp (8 n / 2048 Fr) + slots        4 MiB      8 MiB     16 MiB
@@ -260,6 +262,39 @@ typedef struct typlonk_quotient_args {
  * L0) to the 4n coset domain once; they are fixed per CompiledCircuit (plonk/src/lib.rs:19-35). */
 int typlonk_circuit_load(typlonk_ctx* ctx, const typlonk_buf* const selectors[5], const typlonk_buf* const sigma[3],
                          uint32_t log_n, uint32_t* circuit_id);
+/* The same circuit from what a front end holds: the selector EVALUATIONS over the domain and the copy-constraint permutation
+ * itself (Permutation { perm }, permutation/src/lib.rs:95-98), instead of eight interpolated polynomials.  The call is
+ * Permutation::compile (permutation/src/lib.rs:101-128: sigma_i(w^j) = k_i' * w^j' for perm[i * n + j] = i' * n + j') on the
+ * device, one batched inverse transform of the eight columns, and typlonk_circuit_load's coset extensions.
+ *   selector_evals  q_l q_r q_o q_m q_c, n = 2^log_n evaluations each (Montgomery Fr, the contract of typlonk_ntt_fr_dev's
+ *                   input; left as they are).  A buffer shorter than n returns TYPLONK_ERR_RANGE.
+ *   perm            HOST array of 3n successors over the flat cells col * n + row (as typlonk_circuit_permutation returns it),
+ *                   or NULL = the identity (no copy constraints)
+ *   cosets          k_0 k_1 k_2.  TYPLONK_ERR_INVALID_ARG for a coset that is not a canonical residue, is zero, or meets
+ *                   another: (k_i / k_j)^n = 1 (three ladders on the host).
+ *   log_n           outside 1..TYPLONK_MAX_PROVER_LOG_N returns TYPLONK_ERR_DOMAIN
+ *   result          a circuit id every other call accepts.  The circuit is the one typlonk_circuit_load builds from the inverse
+ *                   transforms (typlonk_ntt_fr_dev) of the same selector evaluations and of the sigma evaluations
+ *                   k_col(perm[x]) * w^row(perm[x]), word for word: every sigma value is written as a canonical residue.
+ *   lint            *defects (may be NULL) = entries of perm that are not below 3n + cells that are the image of != 1 cells, the
+ *                   definition of typlonk_circuit_permutation.  With defects != 0 no circuit is made: the call returns
+ *                   TYPLONK_ERR_INVALID_ARG and typlonk_last_error names the lowest defective cell (as
+ *                   typlonk_srs_load_compressed treats a rejected point).  *defects is written only when the lint has run.
+ *   A refused call leaves the context and *circuit_id as they were.  Never a collective and no SRS involved: works on a
+ *   sharded context.  Blocks until the circuit is usable, as typlonk_circuit_load does.
+ *   The circuit keeps perm with the cosets it was compiled for (12 n bytes, device): typlonk_circuit_permutation and
+ *   typlonk_witness_check under those cosets run no recovery; other cosets recover it from the sigma values, as for a loaded
+ *   circuit.  The selector evaluations of the check cache are still made on the first check.
+ * One thread per cell, two field products each: w^row = hi[row >> h] * lo[row & (2^h - 1)] from the two-level twiddle tables
+ * (h = (log_n + 1) / 2), times the coset.  Device memory beyond the circuit's own: the permutation and, for the duration of the
+ * call, 12 n bytes of indegrees. */
+int typlonk_circuit_compile(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* perm,
+                            const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects);
+/* The same with the selector columns in HOST memory: each holds `rows` Fr elements, and rows must equal n (else
+ * TYPLONK_ERR_LENGTH). */
+int typlonk_circuit_compile_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows,
+                                 const uint32_t* perm, const uint64_t cosets[3][4], uint32_t log_n,
+                                 uint32_t* circuit_id, uint64_t* defects);
 int typlonk_circuit_free(typlonk_ctx* ctx, uint32_t circuit_id);
 int typlonk_quotient_dev(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out);
 
@@ -569,7 +604,8 @@ int typlonk_compact_challenges(const typlonk_vk* vk, const typlonk_proof_compact
  * while a round-by-round prover is open (they touch none of its arena).  Work runs on the context's stream; the calls block.
  * Cells are flat indices x = col * n + row, col in {0, 1, 2} (Tag::to_index, permutation/src/lib.rs).
  * Kept with the circuit after the first call (freed by typlonk_circuit_free / typlonk_destroy): the permutation (3n uint32) with
- * the cosets it was recovered for -- a call with other cosets recovers it again -- and the five selector columns as evaluations
+ * the cosets it was recovered for -- a call with other cosets recovers it again; a circuit made by typlonk_circuit_compile has
+ * the one it was compiled from, and no recovery runs under its own cosets -- and the five selector columns as evaluations
  * (5n Fr, one batch of five forward transforms of the coefficient copies typlonk_circuit_load keeps). */
 #define TYPLONK_CELL_NONE 0xffffffffu
 /* The successor map of the copy-constraint permutation, recovered from the circuit's sigma columns (compiled by

@@ -322,6 +322,26 @@ impl Backend {
         CircuitHandle { id, log_n }
     }
 
+    /// The same circuit from what the front end holds before `Permutation::compile` (permutation/src/lib.rs:101-128): the five
+    /// selector columns as EVALUATIONS over the domain and the permutation itself, `perm` = 3n successors over the flat cells
+    /// `col * n + row` (`None`: no copy constraints).  `typlonk_circuit_compile_host` makes the sigma columns and interpolates
+    /// all eight on the device, and keeps the permutation with the circuit, so `check_witnesses` never recovers it.
+    /// Panics, with the number of defects and the lowest defective cell, when `perm` is no permutation of the cells.
+    pub fn compile_circuit(&self, selector_evals: [&[Fr]; 5], perm: Option<&[u32]>, cosets: [Fr; 3], log_n: u32) -> CircuitHandle {
+        let n = 1usize << log_n;
+        assert!(selector_evals.iter().all(|c| c.len() == n), "selector columns of n evaluations");
+        assert!(perm.map_or(true, |p| p.len() == 3 * n), "perm holds 3n successors");
+        let cols: Vec<Vec<u64>> = selector_evals.iter().map(|c| c.iter().flat_map(|e| fr_limbs(e)).collect()).collect();
+        let colp: Vec<*const u64> = cols.iter().map(|c| c.as_ptr()).collect();
+        let ks = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let (mut id, mut defects) = (0u32, 0u64);
+        self.check(unsafe {
+            ffi::typlonk_circuit_compile_host(self.ctx, colp.as_ptr(), n, perm.map_or(ptr::null(), |p| p.as_ptr()), ks.as_ptr(), log_n,
+                                              &mut id, &mut defects)
+        });
+        CircuitHandle { id, log_n }
+    }
+
     /// `plonk::proof::prove` (plonk/src/proof.rs:96-194) in one native call: `wire_evals` are the three padded and
     /// blinded witness COLUMNS (what `CompiledCircuit::prove` builds at :43-49, before `.interpolate()`),
     /// `public_inputs` the padded public-input column (:52-53), `cosets` = `copy_constrains.cosets`.
@@ -682,6 +702,11 @@ pub struct OwnedCircuit {
 }
 impl OwnedCircuit {
     pub fn new(backend: std::rc::Rc<Backend>, handle: CircuitHandle) -> Self {
+        OwnedCircuit { backend, handle }
+    }
+    /// `Backend::compile_circuit`, owned: from selector evaluations and the permutation (`None`: the identity)
+    pub fn compile(backend: std::rc::Rc<Backend>, selector_evals: [&[Fr]; 5], perm: Option<&[u32]>, cosets: [Fr; 3], log_n: u32) -> Self {
+        let handle = backend.compile_circuit(selector_evals, perm, cosets, log_n);
         OwnedCircuit { backend, handle }
     }
     pub fn handle(&self) -> CircuitHandle {

@@ -5,6 +5,7 @@
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
   tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
+  tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk,wire,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
@@ -151,6 +152,16 @@ def build_fq30_pair_host(force: bool = False) -> str:
     return out
 
 
+def build_sigma_cell_host(force: bool = False) -> str:
+    """tests/cpp/libsigma_cell_host.so: sigma_cell (csrc/sigma_cell.hpp) as the host compiles it, over tables built on the host"""
+    src = os.path.join(ROOT, "tests", "cpp", "sigma_cell_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "libsigma_cell_host.so")
+    deps = [src, os.path.join(CSRC, "ff.hpp"), os.path.join(CSRC, "sigma_cell.hpp")]
+    if force or _stale(out, deps):
+        _run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out])
+    return out
+
+
 def build_device_pair(force: bool = False) -> str:
     """tests/cpp/libdevice_pair.so: the same functions' device code (the interleaved chains of fq30_pair.hpp) behind an
     element-wise test kernel.  Test-only; the flags are build_hip()'s."""
@@ -172,7 +183,7 @@ def build_host_tests(force: bool = False) -> list[str]:
            os.path.join(CSRC, "transcript.hpp"), LIB]
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
-                 "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host"):
+                 "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
         if force or _stale(out, [src] + hdr):
@@ -198,6 +209,7 @@ def build_all(force: bool = False) -> None:
     build_host_shim(force)
     build_device_arith(force)
     build_fq30_pair_host(force)
+    build_sigma_cell_host(force)
     build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)

@@ -37,6 +37,7 @@ SYMBOLS = [
     "typlonk_proof_compact_to_bytes", "typlonk_vk_to_bytes", "typlonk_vk_from_bytes", "typlonk_proof_compact_from_bytes",
     "typlonk_verify_compact_bytes",
     "typlonk_circuit_permutation", "typlonk_witness_check", "typlonk_witness_check_host",
+    "typlonk_circuit_compile", "typlonk_circuit_compile_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -345,6 +346,12 @@ def load_library() -> C.CDLL:
         lib.typlonk_witness_check_host.argtypes = [vp, C.c_uint32, C.POINTER(u64p), C.c_size_t, C.POINTER(u64p),
                                                    C.POINTER(C.c_size_t), C.c_size_t, C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32,
                                                    C.POINTER(WitnessReport), u32p, u32p]
+    if hasattr(lib, "typlonk_circuit_compile") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_circuit_compile.argtypes = [vp, C.POINTER(vp), u32p, C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32, u32p,
+                                                C.POINTER(C.c_uint64)]
+        lib.typlonk_circuit_compile_host.argtypes = [vp, C.POINTER(u64p), C.c_size_t, u32p, C.POINTER((C.c_uint64 * 4) * 3),
+                                                     C.c_uint32, u32p, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -1214,6 +1221,45 @@ class Context:
         sig = (C.c_void_p * 3)(*[b.handle.value for b in sigma])
         cid = C.c_uint32()
         self._chk(self.lib.typlonk_circuit_load(self.h, sel, sig, log_n, C.byref(cid)))
+        return cid.value
+
+    DEFAULT_COSETS = (2, 3, 4)   # Permutation::compile's (permutation/src/lib.rs:141-154)
+
+    def _compile_args(self, log_n: int, perm, cosets):
+        """(keep-alive, perm pointer or None, cosets) of circuit_compile / circuit_compile_host"""
+        if cosets is None:
+            r = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+            cosets = [np.array([((k << 256) % r >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+                      for k in self.DEFAULT_COSETS]
+        pp, keep = None, None
+        if perm is not None:
+            keep = np.ascontiguousarray(perm, dtype=np.uint32)
+            if keep.shape != (3 << log_n,):
+                raise ValueError("perm holds 3n successors over the flat cells col * n + row")
+            pp = keep.ctypes.data_as(C.POINTER(C.c_uint32))
+        return keep, pp, _cosets_arg(cosets)
+
+    def circuit_compile(self, log_n: int, selector_evals, perm=None, cosets=None) -> int:
+        """typlonk_circuit_compile: the circuit of five DeviceBuffers of selector evaluations (q_l q_r q_o q_m q_c) and the
+        3n-entry successor map `perm` over the flat cells col * n + row (None: no copy constraints); cosets = three 4-limb
+        Montgomery arrays (None: 2, 3, 4).  Returns the circuit id; a perm that is no permutation of the cells raises, with
+        the number of defects and the lowest defective cell in the message (typlonk_last_error's)."""
+        keep, pp, ks = self._compile_args(log_n, perm, cosets)
+        sel = (C.c_void_p * 5)(*[b.handle.value for b in selector_evals])
+        cid, defects = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.typlonk_circuit_compile(self.h, sel, pp, C.byref(ks), log_n, C.byref(cid), C.byref(defects)))
+        return cid.value
+
+    def circuit_compile_host(self, log_n: int, selector_evals, perm=None, cosets=None) -> int:
+        """typlonk_circuit_compile_host: the selector evaluations as five (rows, 4) u64 host arrays of equal length"""
+        keep, pp, ks = self._compile_args(log_n, perm, cosets)
+        cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in selector_evals]
+        if len(cols) != 5 or any(c.ndim != 2 or c.shape[1] != 4 or c.shape != cols[0].shape for c in cols):
+            raise ValueError("circuit_compile_host needs five (rows, 4) uint64 columns of equal length")
+        sel = (C.POINTER(C.c_uint64) * 5)(*[_u64p(c) for c in cols])
+        cid, defects = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.typlonk_circuit_compile_host(self.h, sel, cols[0].shape[0], pp, C.byref(ks), log_n, C.byref(cid),
+                                                        C.byref(defects)))
         return cid.value
 
     def circuit_free(self, cid: int):

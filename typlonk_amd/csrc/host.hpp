@@ -8,7 +8,8 @@
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip); which scalars and
 //                 points they and the wire format admit: host_checks.hpp; the linearisation commitment: lin_commit.hpp
-//   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails
+//   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
+//                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -75,7 +76,8 @@ struct CircuitEntry {
         uint8_t inf[8];
     };
     std::map<uint32_t, Commitments> commitments;
-    // typlonk_circuit_permutation / typlonk_witness_check (witness_check.hip), built on first use:
+    // typlonk_circuit_permutation / typlonk_witness_check (witness_check.hip), built on first use -- a circuit made by
+    // typlonk_circuit_compile holds the permutation it was compiled from, for the cosets it was compiled with, from the start:
     uint32_t* perm = nullptr;       // 3n : successor map of the cells recovered from sig_ev (TYPLONK_CELL_NONE: no cell id)
     uint64_t perm_cosets[3][4] = {};  //      the cosets it was recovered for (other cosets rebuild it)
     bool perm_ready = false;
@@ -433,6 +435,13 @@ void round3_openings(const Round3Slots& s, bool with_quotients, const Round3Poly
     if (p.pi) emit(p.pi, nullptr, s.pi, 0);
     emit(p.z, p.q[4], s.zw, 1);
 }
+
+// ---- prover.hip: the tail typlonk_circuit_load and typlonk_circuit_compile share ------------------------------------------
+// e.ext <- the coset evaluations of the eight coefficient vectors src[0..8) (n each; they may be e.coef's own) and of L0;
+// sigma_forward: e.sig_ev holds sigma's coefficients and is transformed to evaluations in place.  Blocks until the circuit is
+// usable, then enters `e` into the context and hands out its id.  On failure nothing is entered and the caller still owns
+// e's allocations.
+int circuit_finish(typlonk_ctx* ctx, CircuitEntry& e, const Fr* const src[8], bool sigma_forward, uint32_t* circuit_id);
 
 // ---- poly_eval.hip / verify.hip ----------------------------------------------------------------------------------------
 // out[(p * n_points + k) * 4 ..] = polys[p](points[k]) over m coefficients each (device pointers; points / out on the host,

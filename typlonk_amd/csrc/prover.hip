@@ -59,6 +59,33 @@ int quotient_extend_batch(typlonk_ctx* ctx, Fr* const* e, const Fr* const* src, 
 }
 }  // namespace
 
+namespace tyh {
+int circuit_finish(typlonk_ctx* ctx, CircuitEntry& e, const Fr* const src[8], bool sigma_forward, uint32_t* circuit_id) {
+    const uint32_t log_n = e.log_n;
+    const uint64_t n = 1ull << log_n, n4 = 4 * n;
+    ProfilingOff prof_off(ctx);  // stage events are per call
+    int rc = TYPLONK_OK;
+    const Fr ninv = fe_inv(fr_from_u64(n));
+    {
+        // the eight coefficient vectors (builder.rs:84-88's five selectors, the three sigmas) as one batch, then L0
+        Fr* dst[8];
+        for (int k = 0; k < 8; ++k) dst[k] = e.ext + (uint64_t)k * n4;
+        rc = quotient_extend_batch(ctx, dst, src, 8, n, log_n + 2);
+        if (!rc) rc = quotient_extend(ctx, e.ext + 8 * n4, nullptr, &ninv, n, log_n + 2);
+        Fr* sig[3] = {e.sig_ev, e.sig_ev + n, e.sig_ev + 2 * n};
+        if (!rc && sigma_forward) rc = ntt_run_batch(ctx, sig, 3, log_n, 0, nullptr, /*sync=*/false);   // proof.rs:334-338
+    }
+    if (!rc) {
+        rc = hip_rc(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (rc) return rc;
+    const uint32_t id = ctx->next_circuit++;
+    ctx->circuits[id] = e;
+    *circuit_id = id;
+    return TYPLONK_OK;
+}
+}  // namespace tyh
+
 int typlonk_circuit_load(typlonk_ctx* ctx, const typlonk_buf* const selectors[5], const typlonk_buf* const sigma[3],
                          uint32_t log_n, uint32_t* circuit_id) {
     if (!ctx || !selectors || !sigma || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
@@ -81,30 +108,11 @@ int typlonk_circuit_load(typlonk_ctx* ctx, const typlonk_buf* const selectors[5]
     for (int k = 0; k < 8; ++k)
         HIPCHK(hipMemcpyAsync(e.coef + (uint64_t)k * n, in[k]->d, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(e.sig_ev, e.coef + 5 * n, 3 * n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-    ProfilingOff prof_off(ctx);  // stage events are per call
-    int rc = TYPLONK_OK;
-    const Fr ninv = fe_inv(fr_from_u64(n));
-    {
-        // the eight coefficient vectors (builder.rs:84-88's five selectors, the three sigmas) as one batch, then L0
-        Fr* dst[8];
-        const Fr* src[8];
-        for (int k = 0; k < 8; ++k) {
-            dst[k] = e.ext + (uint64_t)k * n4;
-            src[k] = in[k]->d;
-        }
-        rc = quotient_extend_batch(ctx, dst, src, 8, n, log_n + 2);
-        if (!rc) rc = quotient_extend(ctx, e.ext + 8 * n4, nullptr, &ninv, n, log_n + 2);
-        Fr* sig[3] = {e.sig_ev, e.sig_ev + n, e.sig_ev + 2 * n};
-        if (!rc) rc = ntt_run_batch(ctx, sig, 3, log_n, 0, nullptr, /*sync=*/false);   // proof.rs:334-338
-    }
-    if (!rc) {
-        rc = hip_rc(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    const Fr* src[8];
+    for (int k = 0; k < 8; ++k) src[k] = in[k]->d;
+    const int rc = circuit_finish(ctx, e, src, /*sigma_forward=*/true, circuit_id);
     if (rc) return rc;
     guard.dismiss();
-    const uint32_t id = ctx->next_circuit++;
-    ctx->circuits[id] = e;
-    *circuit_id = id;
     return TYPLONK_OK;
 }
 

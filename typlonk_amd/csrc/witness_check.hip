@@ -17,10 +17,16 @@
 //   recovery   u = fr30_mul(v, k^-1 * 2^284) = (v / k) * 2^270: the 2^270 domain, closed under fr30_mul; one there is 2^270 mod r
 //   gate       fr30_mul(q, a) = q a * 2^242 for two data words, so every term is brought to the factor 2^242:
 //              q_m a b = fr30_mul(fr30_mul(fr30_mul(a, b), 2^284), q_m),   q_c + PI -> fr30_mul(q_c + PI, 2^256)
+//
+// typlonk_circuit_compile is the way forward, for a front end that holds the permutation itself: sigma_from_perm_kernel writes
+// sigma = k_col(perm[x]) * w^row(perm[x]) (sigma_cell.hpp, two products per cell), the indegree and defects kernels of step 1 lint
+// the permutation, one batched inverse transform interpolates the eight columns, and the circuit keeps the permutation it was
+// compiled from: step 1 never runs for it under the cosets it was compiled with.
 #include "host.hpp"
 #include "host_checks.hpp"
 #include "fr30.hpp"
 #include "scan_ops.hpp"
+#include "sigma_cell.hpp"
 
 using namespace ty;
 using namespace tyh;
@@ -113,6 +119,20 @@ __global__ __launch_bounds__(256) void perm_defects_kernel(const uint32_t* perm,
     const uint32_t c = __popcll(__ballot(none)) + __popcll(__ballot(deg));
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
     if (none || deg) atomicMin(out + 1, (unsigned long long)x);
+}
+
+// The forward direction of perm_recover_kernel.  One thread per cell x, cells in memory order: perm[x] is read (null: the
+// identity), sig[x] = k_col(y) * w^row(y) written, and the kept copy perm[x] set to TYPLONK_CELL_NONE where y is no cell (sig[x]
+// is then zero; such a permutation is refused before anything reads it).
+__global__ __launch_bounds__(256) void sigma_from_perm_kernel(SigmaTables t, const uint32_t* perm_in, uint32_t* perm, Fr* sig,
+                                                              uint64_t n3) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= n3) return;
+    const uint32_t y = perm_in ? perm_in[x] : (uint32_t)x;
+    Fr v = Fr::zero();
+    const bool cell = sigma_cell(t, y, &v);
+    perm[x] = cell ? y : CELL_NONE;
+    p_st(sig + x, v);
 }
 
 __global__ __launch_bounds__(WC_BLOCK) void witness_flags_kernel(CheckArgs a) {
@@ -231,6 +251,29 @@ void free_check_cache(CircuitEntry& e) {
     e.sel_ev = nullptr;
 }
 
+// Is the 3n-entry map `perm` (device; TYPLONK_CELL_NONE or a cell below 3n in every entry) a bijection of the cells?  ws: 3n
+// uint32 of indegrees and 16 bytes behind them.  *defects = cells without an image + cells that are the image of != 1 cells,
+// *first_bad = the lowest such cell (TYPLONK_CELL_NONE when there is none).  Blocks for the answer.
+int perm_lint(typlonk_ctx* ctx, const uint32_t* perm, uint32_t* ws, uint64_t n3, uint64_t* defects, uint32_t* first_bad) {
+    uint32_t* indeg = ws;
+    unsigned long long* d_out = (unsigned long long*)(indeg + n3);
+    const unsigned long long init[2] = {0, ~0ull};
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemsetAsync(indeg, 0, n3 * sizeof(uint32_t), s));
+    HIPCHK(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, s));
+    const dim3 grid((unsigned)((n3 + 255) / 256));
+    hipLaunchKernelGGL(perm_indegree_kernel, grid, dim3(256), 0, s, perm, indeg, n3);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(perm_defects_kernel, grid, dim3(256), 0, s, perm, (const uint32_t*)indeg, n3, d_out);
+    HIPCHK(hipGetLastError());
+    unsigned long long res[2];
+    HIPCHK(hipMemcpyAsync(res, d_out, sizeof(res), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *defects = res[0];
+    *first_bad = res[0] ? (uint32_t)res[1] : CELL_NONE;
+    return TYPLONK_OK;
+}
+
 // CircuitEntry::perm for these cosets: recovered on first use and again when the cosets change
 int ensure_perm(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]) {
     if (e.perm && e.perm_ready && memcmp(e.perm_cosets, cosets, sizeof(e.perm_cosets)) == 0) return TYPLONK_OK;
@@ -253,12 +296,7 @@ int ensure_perm(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]) 
     if (!e.perm) HIPCHK(hipMalloc((void**)&e.perm, n3 * sizeof(uint32_t)));
     const int rc = ensure(ctx, ctx->wc_ws, n3 * sizeof(uint32_t) + 16);
     if (rc) return rc;
-    uint32_t* indeg = (uint32_t*)ctx->wc_ws.p;
-    unsigned long long* d_out = (unsigned long long*)(indeg + n3);
-    const unsigned long long init[2] = {0, ~0ull};
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemsetAsync(indeg, 0, n3 * sizeof(uint32_t), s));
-    HIPCHK(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, s));
     a.sig = e.sig_ev;
     a.perm = e.perm;
     a.n3 = n3;
@@ -266,15 +304,8 @@ int ensure_perm(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]) 
     const dim3 grid((unsigned)((n3 + 255) / 256));
     hipLaunchKernelGGL(perm_recover_kernel, grid, dim3(256), 0, s, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(perm_indegree_kernel, grid, dim3(256), 0, s, (const uint32_t*)e.perm, indeg, n3);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(perm_defects_kernel, grid, dim3(256), 0, s, (const uint32_t*)e.perm, (const uint32_t*)indeg, n3, d_out);
-    HIPCHK(hipGetLastError());
-    unsigned long long res[2];
-    HIPCHK(hipMemcpyAsync(res, d_out, sizeof(res), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    e.perm_defects = res[0];
-    e.perm_first_bad = res[0] ? (uint32_t)res[1] : CELL_NONE;
+    const int lrc = perm_lint(ctx, e.perm, (uint32_t*)ctx->wc_ws.p, n3, &e.perm_defects, &e.perm_first_bad);
+    if (lrc) return lrc;
     memcpy(e.perm_cosets, cosets, sizeof(e.perm_cosets));
     e.perm_ready = true;
     return TYPLONK_OK;
@@ -464,6 +495,104 @@ int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const WitnessIn& i
     return TYPLONK_OK;
 }
 
+// ---- typlonk_circuit_compile ---------------------------------------------------------------------------------------------
+// the selector columns of a call: typlonk_buf handles, or host pointers of `rows` elements each
+struct SelectorsIn {
+    const typlonk_buf* const* bufs;
+    const uint64_t* const* host;
+    size_t rows;   // the host form's column length (must be n)
+};
+
+// k_0 H, k_1 H, k_2 H are cosets of the domain H, pairwise disjoint: canonical, non-zero, (k_i / k_j)^n != 1
+int check_cosets(typlonk_ctx* ctx, const uint64_t cosets[3][4], uint32_t log_n, Fr (&k)[3]) {
+    for (int i = 0; i < 3; ++i) {
+        if (!fr_canonical(cosets[i])) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "coset is not a canonical residue");
+        memcpy(k[i].v, cosets[i], sizeof(k[i].v));
+        if (k[i].is_zero()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "coset is zero");
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j) {
+            Fr t = fe_mul(k[i], fe_inv(k[j]));
+            for (uint32_t s = 0; s < log_n; ++s) t = fe_sqr(t);
+            if (t == Fr::one())
+                return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                            "cosets " + std::to_string(i) + " and " + std::to_string(j) + " are not disjoint: (k_i / k_j)^n = 1");
+        }
+    return TYPLONK_OK;
+}
+
+int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const uint32_t* perm, const uint64_t cosets[3][4], uint32_t log_n,
+                         uint32_t* circuit_id, uint64_t* defects) {
+    if (!ctx) return TYPLONK_ERR_INVALID_ARG;
+    if (!(in.bufs || in.host) || !cosets || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
+    const uint64_t n = 1ull << log_n, n3 = 3 * n;
+    for (int k = 0; k < 5; ++k) {
+        if (in.bufs ? !in.bufs[k] : !in.host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null selector column");
+        if (in.bufs && in.bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "selector column shorter than n");
+    }
+    if (in.host && in.rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "selector columns must hold exactly n rows");
+    SigmaTables t{};
+    int rc = check_cosets(ctx, cosets, log_n, t.k);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    ProfilingOff prof_off(ctx);
+    Table lo, hi;
+    rc = get_pow2l(ctx, "tw:f:" + std::to_string(log_n), fr_domain_root(log_n), Fr::one(), log_n, &lo, &hi, &t.h);
+    if (rc) return rc;
+    t.lo = lo.d;
+    t.hi = hi.d;
+    t.log_n = log_n;
+
+    CircuitEntry e;
+    e.log_n = log_n;
+    DevGuard guard;
+    HIPCHK(hipMalloc((void**)&e.ext, 36 * n * sizeof(Fr)));
+    guard.add(e.ext);
+    HIPCHK(hipMalloc((void**)&e.coef, 8 * n * sizeof(Fr)));
+    guard.add(e.coef);
+    HIPCHK(hipMalloc((void**)&e.sig_ev, n3 * sizeof(Fr)));
+    guard.add(e.sig_ev);
+    HIPCHK(hipMalloc((void**)&e.perm, n3 * sizeof(uint32_t)));
+    guard.add(e.perm);
+    hipStream_t s = ctx->stream;
+    {
+        // the lint's indegrees live for this block only
+        uint32_t* indeg = nullptr;
+        HIPCHK(hipMalloc((void**)&indeg, n3 * sizeof(uint32_t) + 16));
+        DevGuard transient;
+        transient.add(indeg);
+        // the caller's permutation goes into the kept copy; the kernel reads it there and rewrites an entry that is no cell
+        if (perm) HIPCHK(hipMemcpyAsync(e.perm, perm, n3 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(sigma_from_perm_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, t,
+                           perm ? (const uint32_t*)e.perm : (const uint32_t*)nullptr, e.perm, e.sig_ev, n3);
+        HIPCHK(hipGetLastError());
+        rc = perm_lint(ctx, e.perm, indeg, n3, &e.perm_defects, &e.perm_first_bad);
+        if (rc) return rc;
+    }
+    if (defects) *defects = e.perm_defects;
+    if (e.perm_defects)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                    "perm is not a permutation of the cells (" + std::to_string(e.perm_defects) + " defects, the lowest at cell " +
+                        std::to_string(e.perm_first_bad) + ")");
+    // the eight columns as evaluations in `coef`, interpolated there in one batch (builder.rs:84-88, proof.rs:334-338)
+    for (int k = 0; k < 5; ++k) {
+        if (in.bufs) HIPCHK(hipMemcpyAsync(e.coef + (uint64_t)k * n, in.bufs[k]->d, n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+        else HIPCHK(hipMemcpyAsync(e.coef + (uint64_t)k * n, in.host[k], n * sizeof(Fr), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(e.coef + 5 * n, e.sig_ev, n3 * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+    Fr* co[8];
+    for (int k = 0; k < 8; ++k) co[k] = e.coef + (uint64_t)k * n;
+    rc = ntt_run_batch(ctx, co, 8, log_n, 1, nullptr, /*sync=*/false);
+    if (rc) return rc;
+    memcpy(e.perm_cosets, cosets, sizeof(e.perm_cosets));
+    e.perm_ready = true;
+    rc = circuit_finish(ctx, e, co, /*sigma_forward=*/false, circuit_id);
+    if (rc) return rc;
+    guard.dismiss();
+    return TYPLONK_OK;
+}
+
 }  // namespace
 
 namespace tyh {
@@ -503,4 +632,14 @@ int typlonk_witness_check_host(typlonk_ctx* ctx, uint32_t circuit_id, const uint
     // (SIZE_MAX means "no row count stated" to witness_check_impl: as a caller's row count it is refused like any other != n)
     return witness_check_impl(ctx, circuit_id, in, rows == SIZE_MAX ? 0 : rows, count, cosets,
                               Outputs{cap, reports, gate_rows, copy_cells});
+}
+
+int typlonk_circuit_compile(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* perm,
+                            const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
+    return circuit_compile_impl(ctx, SelectorsIn{selector_evals, nullptr, 0}, perm, cosets, log_n, circuit_id, defects);
+}
+
+int typlonk_circuit_compile_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows, const uint32_t* perm,
+                                 const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
+    return circuit_compile_impl(ctx, SelectorsIn{nullptr, selector_evals, rows}, perm, cosets, log_n, circuit_id, defects);
 }

@@ -558,6 +558,42 @@ class CompiledCircuit {
         for (typlonk_buf* b : polys) typlonk_buf_free(c, b);
         check(rc, c);
     }
+    // The same from what a front end holds before Permutation::compile (permutation/src/lib.rs:101-128): the selector
+    // evaluations and the permutation itself, `perm` = 3n successors over the flat cells col * n + row (empty: no copy
+    // constraints).  typlonk_circuit_compile_host makes the sigma columns, interpolates all eight on the device and keeps
+    // the permutation with the circuit (check_witness never has to recover it); a perm that is no permutation of the cells
+    // throws with the number of defects and the lowest defective cell.  The eight commitments come from the library's cache
+    // (typlonk_circuit_commitments: on an SRS shard a collective, like the other constructor's MSMs).  Nothing of
+    // Permutation::compile runs on the host here; the first verify() of this mirror pays for it once (ensure_sigma_polys).
+    CompiledCircuit(const kzg::Srs& srs, uint32_t log_n, const std::vector<Fr> (&selector_evals)[5],
+                    const std::vector<uint32_t>& perm, const Fr (&cosets)[3])
+        : srs_(srs), log_n_(log_n), n_((size_t)1 << log_n) {
+        for (int i = 0; i < 3; ++i) cosets_[i] = cosets[i];
+        typlonk_ctx* c = srs.ctx().raw();
+        const uint64_t* sel[5];
+        for (int k = 0; k < 5; ++k) {
+            if (selector_evals[k].size() != n_) throw std::runtime_error("circuit table must hold n evaluations");
+            sel[k] = selector_evals[k][0].limbs();
+        }
+        if (!perm.empty() && perm.size() != 3 * n_) throw std::runtime_error("perm must hold 3n successors");
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        check(typlonk_circuit_compile_host(c, sel, n_, perm.empty() ? nullptr : perm.data(), ks, log_n, &circuit_, nullptr), c);
+        uint64_t xy[8][12];
+        uint8_t inf[8];
+        int rc = typlonk_circuit_commitments(c, srs.id(), circuit_, xy, inf);
+        if (rc < 0) {
+            typlonk_circuit_free(c, circuit_);
+            check(rc, c);
+        }
+        sigma_lazy_ = true;  // (the sigma polynomials are this mirror's verify()'s alone: ensure_sigma_polys makes them there)
+        for (int k = 0; k < 8; ++k) {
+            kzg::G1Point g;
+            std::memcpy(g.xy, xy[k], 96);
+            g.infinity = inf[k] != 0;
+            (k < 5 ? fixed_commitments[k] : sigma_commitments[k - 5]) = kzg::KzgCommitment{g};
+        }
+    }
     CompiledCircuit(const CompiledCircuit&) = delete;
     ~CompiledCircuit() {
         if (circuit_) typlonk_circuit_free(srs_.ctx().raw(), circuit_);
@@ -694,6 +730,7 @@ class CompiledCircuit {
         const Fr zw_eval = proof.permutation.zw.eval();
         const Fr advice[3] = {a, b, c};
         Fr sigma_evals[3];
+        ensure_sigma_polys();
         for (int i = 0; i < 3; ++i) sigma_evals[i] = sigma_polys_[i].evaluate(point);  // permutation/src/lib.rs:165-176
         Fr l2 = Fr::one();
         for (int i = 0; i < 3; ++i) l2 *= advice[i] + beta * cosets_[i] * point + gamma;
@@ -873,12 +910,35 @@ class CompiledCircuit {
         }
         return b;
     }
+    // verify() evaluates the sigma polynomials at zeta.  A circuit compiled from a permutation has none on the host until the
+    // first verify(): the permutation comes back from the library's cache (typlonk_circuit_permutation, no recovery under the
+    // circuit's own cosets), then Permutation::compile on the host (3n products) and one batch of three interpolations.
+    void ensure_sigma_polys() const {
+        if (!sigma_lazy_) return;
+        typlonk_ctx* c = srs_.ctx().raw();
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        std::vector<uint32_t> perm(3 * n_);
+        uint64_t defects = 0;
+        check(typlonk_circuit_permutation(c, circuit_, ks, perm.data(), &defects), c);
+        const poly::Radix2EvaluationDomain domain(srs_.ctx(), n_);
+        std::vector<Fr> roots(n_);
+        Fr x = Fr::one();
+        for (size_t j = 0; j < n_; ++j, x = x * domain.group_gen) roots[j] = x;
+        std::vector<std::vector<Fr>> sigma(3, std::vector<Fr>(n_));
+        for (size_t cell = 0; cell < 3 * n_; ++cell)
+            sigma[cell >> log_n_][cell & (n_ - 1)] = cosets_[perm[cell] >> log_n_] * roots[perm[cell] & (n_ - 1)];
+        const auto polys = poly::interpolate_batch(srs_.ctx(), sigma, domain);
+        for (int i = 0; i < 3; ++i) sigma_polys_[i] = polys[i];
+        sigma_lazy_ = false;
+    }
     const kzg::Srs& srs_;
     uint32_t log_n_;
     size_t n_;
     Fr cosets_[3];
     uint32_t circuit_ = 0;
-    poly::DensePolynomial sigma_polys_[3];
+    mutable poly::DensePolynomial sigma_polys_[3];
+    mutable bool sigma_lazy_ = false;
 };
 
 // typlonk_verify_compact: compact proofs against a verifying key, on any context -- it needs no SRS and no loaded circuit.
