@@ -45,6 +45,9 @@ extern "C" {
                                           proof its own verifier rejects (:234-235)                          */
 
 #define TYPLONK_ERR_COMM (-9)          /* an RCCL call failed or librccl could not be loaded; see typlonk_last_error */
+/* A bound that no input can reach was reached (the walks of typlonk_permutation_from_pairs): reported under
+ * TYPLONK_ERR_HIP's code, with the cause in typlonk_last_error. */
+#define TYPLONK_ERR_INTERNAL TYPLONK_ERR_HIP
 
 typedef struct typlonk_ctx typlonk_ctx; /* one HIP device + stream + workspaces + cached NTT plans */
 typedef struct typlonk_buf typlonk_buf; /* device-resident vector of Fr elements                   */
@@ -295,6 +298,42 @@ int typlonk_circuit_compile(typlonk_ctx* ctx, const typlonk_buf* const selector_
 int typlonk_circuit_compile_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows,
                                  const uint32_t* perm, const uint64_t cosets[3][4], uint32_t log_n,
                                  uint32_t* circuit_id, uint64_t* defects);
+/* The copy-constraint permutation from what a front end holds: `count` pairs of cells that must carry one value
+ * (PermutationBuilder::add_constrain and build, permutation/src/lib.rs:48-93), made on the device.
+ *   pairs           HOST array of 2 * count flat cells x = col * n + row, pair i = (pairs[2i], pairs[2i + 1]).  NULL with
+ *                   count != 0 returns TYPLONK_ERR_INVALID_ARG; count = 0 gives the identity (pairs may then be NULL);
+ *                   count > 2^32 - 1 returns TYPLONK_ERR_LENGTH.
+ *   log_n           outside 1..TYPLONK_MAX_PROVER_LOG_N returns TYPLONK_ERR_DOMAIN.  All of these are judged before a pair is read.
+ *   perm            HOST array of 3n successors (may be NULL): the CANONICAL permutation of the partition the pairs generate.
+ *                   Inside a class the cells ascend, x_0 < x_1 < ... < x_{k-1}, perm[x_i] = x_{i+1} and perm[x_{k-1}] = x_0; a
+ *                   cell in no pair is a fixed point.  It depends on the partition alone: the order, orientation and
+ *                   multiplicity of the pairs, self-pairs and redundant pairs change no word of it, nor does the run (the
+ *                   reference walks a HashMap, lib.rs:68, and gives one circuit another sigma every time).
+ *   classes         (may be NULL) the classes among the 3n cells, singletons included: the cells that are the lowest of theirs
+ *   a bad pair      A pair that names a cell >= 3n returns TYPLONK_ERR_INVALID_ARG; typlonk_last_error names how many pairs
+ *                   are bad, the lowest bad pair index and its cell (as the compile's lint names a cell).  perm and *classes
+ *                   are then left as they were and the context stays usable.  (The reference's check_tag, lib.rs:44-47, lets
+ *                   column 3 through and indexes out of bounds in build.)
+ * Never a collective and no SRS involved: works on a sharded context.  Blocks for the result.
+ * Kernels (perm_pairs.hip): one validation pass; a union-find over 3n parents, a thread per pair, the larger root hooked
+ * under the smaller so that a class's root is its lowest cell; ceil((log_n + 2) / 3) rounds of pointer jumping; a stable
+ * 8-bit LSD radix sort of the cells by root, ceil((log_n + 2) / 8) passes; one linking pass.  The launch count depends on
+ * log_n alone.  A walk that exceeds 2 * 3n steps (no input can cause it) returns TYPLONK_ERR_INTERNAL.
+ * Device memory for the duration of the call: 36.75 n + 8 * count bytes (+ 8 KiB), freed on return. */
+int typlonk_permutation_from_pairs(typlonk_ctx* ctx, const uint32_t* pairs, size_t count, uint32_t log_n, uint32_t* perm,
+                                   uint64_t* classes);
+/* typlonk_circuit_compile from the pairs: the circuit is, word for word, the one typlonk_circuit_compile makes from the
+ * canonical perm of the same pairs, and it keeps that perm with its cosets in the same way -- but the permutation is written
+ * into the kept copy by the kernels above and never crosses to the host.  pairs, count, log_n and *classes as for
+ * typlonk_permutation_from_pairs (refused first, in that order); selector_evals and cosets as for typlonk_circuit_compile,
+ * with its refusals.  A refused call leaves the context, *circuit_id and *classes as they were. */
+int typlonk_circuit_compile_pairs(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* pairs,
+                                  size_t count, const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id,
+                                  uint64_t* classes);
+/* The same with the selector columns in HOST memory, `rows` elements each (rows != n: TYPLONK_ERR_LENGTH). */
+int typlonk_circuit_compile_pairs_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows,
+                                       const uint32_t* pairs, size_t count, const uint64_t cosets[3][4], uint32_t log_n,
+                                       uint32_t* circuit_id, uint64_t* classes);
 int typlonk_circuit_free(typlonk_ctx* ctx, uint32_t circuit_id);
 int typlonk_quotient_dev(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out);
 

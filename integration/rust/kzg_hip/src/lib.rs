@@ -342,6 +342,35 @@ impl Backend {
         CircuitHandle { id, log_n }
     }
 
+    /// The same from what the front end holds before `PermutationBuilder::build` (permutation/src/lib.rs:48-93): the copy
+    /// constraints themselves, `pairs` of flat cells `col * n + row` that must carry one value.  The library makes the canonical
+    /// permutation of their classes on the device (every class ascending, the same for any order of the pairs and on every
+    /// run -- `build` walks a `HashMap`) and compiles from it without the map visiting the host.  Returns the circuit and the
+    /// number of classes among the 3n cells.  Panics, with the lowest bad pair named, when a pair names a cell outside the table.
+    pub fn compile_circuit_from_pairs(&self, selector_evals: [&[Fr]; 5], pairs: &[[u32; 2]], cosets: [Fr; 3], log_n: u32) -> (CircuitHandle, u64) {
+        let n = 1usize << log_n;
+        assert!(selector_evals.iter().all(|c| c.len() == n), "selector columns of n evaluations");
+        let cols: Vec<Vec<u64>> = selector_evals.iter().map(|c| c.iter().flat_map(|e| fr_limbs(e)).collect()).collect();
+        let colp: Vec<*const u64> = cols.iter().map(|c| c.as_ptr()).collect();
+        let ks = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let (mut id, mut classes) = (0u32, 0u64);
+        let pp = if pairs.is_empty() { ptr::null() } else { pairs.as_ptr() as *const u32 };
+        self.check(unsafe {
+            ffi::typlonk_circuit_compile_pairs_host(self.ctx, colp.as_ptr(), n, pp, pairs.len(), ks.as_ptr(), log_n, &mut id, &mut classes)
+        });
+        (CircuitHandle { id, log_n }, classes)
+    }
+
+    /// `typlonk_permutation_from_pairs`: the canonical permutation alone, as `(perm, classes)`.
+    pub fn permutation_from_pairs(&self, pairs: &[[u32; 2]], log_n: u32) -> (Vec<u32>, u64) {
+        assert!((1..=24).contains(&log_n), "1 <= log_n <= 24");
+        let mut perm = vec![0u32; 3usize << log_n];
+        let mut classes = 0u64;
+        let pp = if pairs.is_empty() { ptr::null() } else { pairs.as_ptr() as *const u32 };
+        self.check(unsafe { ffi::typlonk_permutation_from_pairs(self.ctx, pp, pairs.len(), log_n, perm.as_mut_ptr(), &mut classes) });
+        (perm, classes)
+    }
+
     /// `plonk::proof::prove` (plonk/src/proof.rs:96-194) in one native call: `wire_evals` are the three padded and
     /// blinded witness COLUMNS (what `CompiledCircuit::prove` builds at :43-49, before `.interpolate()`),
     /// `public_inputs` the padded public-input column (:52-53), `cosets` = `copy_constrains.cosets`.

@@ -6,6 +6,7 @@
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
   tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
+  tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
   tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk,wire,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
@@ -41,7 +42,7 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -162,6 +163,16 @@ def build_sigma_cell_host(force: bool = False) -> str:
     return out
 
 
+def build_perm_pairs_host(force: bool = False) -> str:
+    """tests/cpp/perm_pairs_host: the find, hook and jump bodies of csrc/perm_pairs.hpp as the host compiles them, run by threads"""
+    src = os.path.join(ROOT, "tests", "cpp", "perm_pairs_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "perm_pairs_host")
+    deps = [src, os.path.join(CSRC, "ff.hpp"), os.path.join(CSRC, "perm_pairs.hpp")]
+    if force or _stale(out, deps):
+        _run(["g++", "-O2", "-std=c++17", "-pthread", src, "-o", out])
+    return out
+
+
 def build_device_pair(force: bool = False) -> str:
     """tests/cpp/libdevice_pair.so: the same functions' device code (the interleaved chains of fq30_pair.hpp) behind an
     element-wise test kernel.  Test-only; the flags are build_hip()'s."""
@@ -183,7 +194,8 @@ def build_host_tests(force: bool = False) -> list[str]:
            os.path.join(CSRC, "transcript.hpp"), LIB]
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
-                 "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host"):
+                 "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
+                 "test_circuit_pairs_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
         if force or _stale(out, [src] + hdr):
@@ -210,6 +222,7 @@ def build_all(force: bool = False) -> None:
     build_device_arith(force)
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
+    build_perm_pairs_host(force)
     build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)

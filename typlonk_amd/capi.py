@@ -38,6 +38,7 @@ SYMBOLS = [
     "typlonk_verify_compact_bytes",
     "typlonk_circuit_permutation", "typlonk_witness_check", "typlonk_witness_check_host",
     "typlonk_circuit_compile", "typlonk_circuit_compile_host",
+    "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -352,6 +353,13 @@ def load_library() -> C.CDLL:
                                                 C.POINTER(C.c_uint64)]
         lib.typlonk_circuit_compile_host.argtypes = [vp, C.POINTER(u64p), C.c_size_t, u32p, C.POINTER((C.c_uint64 * 4) * 3),
                                                      C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "typlonk_permutation_from_pairs") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_permutation_from_pairs.argtypes = [vp, u32p, C.c_size_t, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+        lib.typlonk_circuit_compile_pairs.argtypes = [vp, C.POINTER(vp), u32p, C.c_size_t, C.POINTER((C.c_uint64 * 4) * 3),
+                                                      C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+        lib.typlonk_circuit_compile_pairs_host.argtypes = [vp, C.POINTER(u64p), C.c_size_t, u32p, C.c_size_t,
+                                                           C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32, u32p, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -1261,6 +1269,49 @@ class Context:
         self._chk(self.lib.typlonk_circuit_compile_host(self.h, sel, cols[0].shape[0], pp, C.byref(ks), log_n, C.byref(cid),
                                                         C.byref(defects)))
         return cid.value
+
+    @staticmethod
+    def _pairs_arg(pairs):
+        """(keep-alive, pointer or None, count) of a pair list: anything np.ascontiguousarray(..., dtype=np.uint32) turns into
+        shape (count, 2)"""
+        keep = np.ascontiguousarray(pairs, dtype=np.uint32)
+        if keep.ndim != 2 or keep.shape[1] != 2:
+            raise ValueError("pairs must have shape (count, 2): two flat cells col * n + row per copy constraint")
+        return keep, (keep.ctypes.data_as(C.POINTER(C.c_uint32)) if keep.shape[0] else None), keep.shape[0]
+
+    def permutation_from_pairs(self, log_n: int, pairs):
+        """typlonk_permutation_from_pairs: (perm, classes) -- the canonical 3n-entry successor map of the partition the pairs
+        of flat cells generate (every class ascending, its highest cell back to its lowest) and the number of classes.  A pair
+        that names a cell >= 3n raises, with the count of bad pairs, the lowest bad pair and its cell in the message."""
+        keep, pp, count = self._pairs_arg(pairs)
+        perm = np.empty(3 << log_n if 1 <= log_n <= 24 else 0, dtype=np.uint32)   # (any other log_n is refused before perm is touched)
+        classes = C.c_uint64()
+        self._chk(self.lib.typlonk_permutation_from_pairs(self.h, pp, count, log_n, perm.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                          C.byref(classes)))
+        return perm, int(classes.value)
+
+    def circuit_compile_pairs(self, log_n: int, selector_evals, pairs, cosets=None):
+        """typlonk_circuit_compile_pairs: (circuit id, classes) -- circuit_compile from copy constraints given as pairs of flat
+        cells; the permutation is made and kept on the device"""
+        keep, pp, count = self._pairs_arg(pairs)
+        _, _, ks = self._compile_args(log_n, None, cosets)
+        sel = (C.c_void_p * 5)(*[b.handle.value for b in selector_evals])
+        cid, classes = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.typlonk_circuit_compile_pairs(self.h, sel, pp, count, C.byref(ks), log_n, C.byref(cid), C.byref(classes)))
+        return cid.value, int(classes.value)
+
+    def circuit_compile_pairs_host(self, log_n: int, selector_evals, pairs, cosets=None):
+        """typlonk_circuit_compile_pairs_host: the selector evaluations as five (rows, 4) u64 host arrays of equal length"""
+        keep, pp, count = self._pairs_arg(pairs)
+        _, _, ks = self._compile_args(log_n, None, cosets)
+        cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in selector_evals]
+        if len(cols) != 5 or any(c.ndim != 2 or c.shape[1] != 4 or c.shape != cols[0].shape for c in cols):
+            raise ValueError("circuit_compile_pairs_host needs five (rows, 4) uint64 columns of equal length")
+        sel = (C.POINTER(C.c_uint64) * 5)(*[_u64p(c) for c in cols])
+        cid, classes = C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.typlonk_circuit_compile_pairs_host(self.h, sel, cols[0].shape[0], pp, count, C.byref(ks), log_n,
+                                                              C.byref(cid), C.byref(classes)))
+        return cid.value, int(classes.value)
 
     def circuit_free(self, cid: int):
         self._chk(self.lib.typlonk_circuit_free(self.h, cid))

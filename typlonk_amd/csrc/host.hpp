@@ -469,6 +469,22 @@ int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t cou
 // ---- witness_check.hip ----------------------------------------------------------------------------------------------
 // frees a circuit's recovered permutation and selector evaluations (typlonk_circuit_free, typlonk_destroy)
 void circuit_check_release(CircuitEntry& e);
+// the selector columns of a compile: typlonk_buf handles, or host pointers of `rows` elements each
+struct SelectorsIn {
+    const typlonk_buf* const* bufs;
+    const uint64_t* const* host;
+    size_t rows;   // the host form's column length (must be n)
+};
+// where the permutation a compile keeps comes from: 3n successors in HOST memory, or a producer that writes them into the
+// kept copy on the device (perm_pairs.hip), or neither: the identity
+struct PermSource {
+    const uint32_t* host = nullptr;
+    int (*fill)(typlonk_ctx* ctx, uint32_t* d_perm, void* arg) = nullptr;
+    void* arg = nullptr;
+};
+// typlonk_circuit_compile behind its entry points and behind typlonk_circuit_compile_pairs
+int circuit_compile_from(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
+                         uint32_t* circuit_id, uint64_t* defects);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------
 void comm_release(typlonk_ctx* ctx);

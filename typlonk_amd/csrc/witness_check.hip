@@ -21,7 +21,8 @@
 // typlonk_circuit_compile is the way forward, for a front end that holds the permutation itself: sigma_from_perm_kernel writes
 // sigma = k_col(perm[x]) * w^row(perm[x]) (sigma_cell.hpp, two products per cell), the indegree and defects kernels of step 1 lint
 // the permutation, one batched inverse transform interpolates the eight columns, and the circuit keeps the permutation it was
-// compiled from: step 1 never runs for it under the cosets it was compiled with.
+// compiled from: step 1 never runs for it under the cosets it was compiled with.  typlonk_circuit_compile_pairs (perm_pairs.hip)
+// enters the same code with a producer that writes the kept copy on the device, where the caller's array would be uploaded.
 #include "host.hpp"
 #include "host_checks.hpp"
 #include "fr30.hpp"
@@ -496,13 +497,6 @@ int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const WitnessIn& i
 }
 
 // ---- typlonk_circuit_compile ---------------------------------------------------------------------------------------------
-// the selector columns of a call: typlonk_buf handles, or host pointers of `rows` elements each
-struct SelectorsIn {
-    const typlonk_buf* const* bufs;
-    const uint64_t* const* host;
-    size_t rows;   // the host form's column length (must be n)
-};
-
 // k_0 H, k_1 H, k_2 H are cosets of the domain H, pairwise disjoint: canonical, non-zero, (k_i / k_j)^n != 1
 int check_cosets(typlonk_ctx* ctx, const uint64_t cosets[3][4], uint32_t log_n, Fr (&k)[3]) {
     for (int i = 0; i < 3; ++i) {
@@ -521,7 +515,7 @@ int check_cosets(typlonk_ctx* ctx, const uint64_t cosets[3][4], uint32_t log_n, 
     return TYPLONK_OK;
 }
 
-int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const uint32_t* perm, const uint64_t cosets[3][4], uint32_t log_n,
+int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
                          uint32_t* circuit_id, uint64_t* defects) {
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     if (!(in.bufs || in.host) || !cosets || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
@@ -562,10 +556,16 @@ int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const uint32_t
         HIPCHK(hipMalloc((void**)&indeg, n3 * sizeof(uint32_t) + 16));
         DevGuard transient;
         transient.add(indeg);
-        // the caller's permutation goes into the kept copy; the kernel reads it there and rewrites an entry that is no cell
-        if (perm) HIPCHK(hipMemcpyAsync(e.perm, perm, n3 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        // the permutation goes into the kept copy, from the caller's array or from a producer on the device; the kernel reads
+        // it there and rewrites an entry that is no cell
+        const bool given = from.host || from.fill;
+        if (from.host) HIPCHK(hipMemcpyAsync(e.perm, from.host, n3 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (from.fill) {
+            rc = from.fill(ctx, e.perm, from.arg);
+            if (rc) return rc;
+        }
         hipLaunchKernelGGL(sigma_from_perm_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, t,
-                           perm ? (const uint32_t*)e.perm : (const uint32_t*)nullptr, e.perm, e.sig_ev, n3);
+                           given ? (const uint32_t*)e.perm : (const uint32_t*)nullptr, e.perm, e.sig_ev, n3);
         HIPCHK(hipGetLastError());
         rc = perm_lint(ctx, e.perm, indeg, n3, &e.perm_defects, &e.perm_first_bad);
         if (rc) return rc;
@@ -597,6 +597,10 @@ int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const uint32_t
 
 namespace tyh {
 void circuit_check_release(CircuitEntry& e) { free_check_cache(e); }
+int circuit_compile_from(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
+                         uint32_t* circuit_id, uint64_t* defects) {
+    return circuit_compile_impl(ctx, in, from, cosets, log_n, circuit_id, defects);
+}
 }  // namespace tyh
 
 int typlonk_circuit_permutation(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t cosets[3][4], uint32_t* perm,
@@ -636,10 +640,14 @@ int typlonk_witness_check_host(typlonk_ctx* ctx, uint32_t circuit_id, const uint
 
 int typlonk_circuit_compile(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* perm,
                             const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
-    return circuit_compile_impl(ctx, SelectorsIn{selector_evals, nullptr, 0}, perm, cosets, log_n, circuit_id, defects);
+    PermSource from{};
+    from.host = perm;
+    return circuit_compile_impl(ctx, SelectorsIn{selector_evals, nullptr, 0}, from, cosets, log_n, circuit_id, defects);
 }
 
 int typlonk_circuit_compile_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows, const uint32_t* perm,
                                  const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
-    return circuit_compile_impl(ctx, SelectorsIn{nullptr, selector_evals, rows}, perm, cosets, log_n, circuit_id, defects);
+    PermSource from{};
+    from.host = perm;
+    return circuit_compile_impl(ctx, SelectorsIn{nullptr, selector_evals, rows}, from, cosets, log_n, circuit_id, defects);
 }

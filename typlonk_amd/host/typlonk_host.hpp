@@ -495,6 +495,26 @@ struct Proof {
 // (copy_constrains, permutation/src/lib.rs:141-154).  The tables come from the front end
 // (CircuitDescription::build; circuit_host.hpp) as EVALUATIONS over the domain, exactly as builder.rs:85 interpolates
 // them; they are interpolated on the device once and cached for every later proof (typlonk_circuit_load).
+// a copy constraint: two flat cells col * n + row that must carry one value (PermutationBuilder::add_constrain)
+struct CellPair {
+    uint32_t a, b;
+};
+static_assert(sizeof(CellPair) == 8, "a pair list is the C ABI's array of 2 * count cells");
+
+// Permutation { perm } (permutation/src/lib.rs:95-98) as PermutationBuilder::build would make it from the pairs, but canonical:
+// every class of cells ascending, its highest cell back to its lowest (typlonk_permutation_from_pairs; on the device)
+struct CellPermutation {
+    std::vector<uint32_t> perm;   // 3n successors
+    uint64_t classes = 0;         // classes among the 3n cells, singletons included
+    static CellPermutation from_pairs(const Context& ctx, uint32_t log_n, const std::vector<CellPair>& pairs) {
+        CellPermutation out;
+        if (log_n >= 1 && log_n <= TYPLONK_MAX_PROVER_LOG_N) out.perm.resize((size_t)3 << log_n);
+        check(typlonk_permutation_from_pairs(ctx.raw(), pairs.empty() ? nullptr : &pairs[0].a, pairs.size(), log_n,
+                                             out.perm.empty() ? nullptr : out.perm.data(), &out.classes), ctx.raw());
+        return out;
+    }
+};
+
 class CompiledCircuit {
    public:
     CompiledCircuit(const kzg::Srs& srs, uint32_t log_n, const std::vector<Fr> (&selector_evals)[5],
@@ -579,26 +599,35 @@ class CompiledCircuit {
         uint64_t ks[3][4];
         for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
         check(typlonk_circuit_compile_host(c, sel, n_, perm.empty() ? nullptr : perm.data(), ks, log_n, &circuit_, nullptr), c);
-        uint64_t xy[8][12];
-        uint8_t inf[8];
-        int rc = typlonk_circuit_commitments(c, srs.id(), circuit_, xy, inf);
-        if (rc < 0) {
-            typlonk_circuit_free(c, circuit_);
-            check(rc, c);
+        fetch_commitments();
+    }
+    // The same from what a front end holds before PermutationBuilder::build (permutation/src/lib.rs:48-93): the copy
+    // constraints themselves, pairs of flat cells that must carry one value.  typlonk_circuit_compile_pairs_host makes the
+    // canonical permutation of their classes on the device (every class ascending; CellPermutation::from_pairs returns the
+    // same map) and compiles from it; a pair outside the table throws with the lowest bad pair named.  classes() is the
+    // number of classes among the 3n cells.
+    CompiledCircuit(const kzg::Srs& srs, uint32_t log_n, const std::vector<Fr> (&selector_evals)[5],
+                    const std::vector<CellPair>& pairs, const Fr (&cosets)[3])
+        : srs_(srs), log_n_(log_n), n_((size_t)1 << log_n) {
+        for (int i = 0; i < 3; ++i) cosets_[i] = cosets[i];
+        typlonk_ctx* c = srs.ctx().raw();
+        const uint64_t* sel[5];
+        for (int k = 0; k < 5; ++k) {
+            if (selector_evals[k].size() != n_) throw std::runtime_error("circuit table must hold n evaluations");
+            sel[k] = selector_evals[k][0].limbs();
         }
-        sigma_lazy_ = true;  // (the sigma polynomials are this mirror's verify()'s alone: ensure_sigma_polys makes them there)
-        for (int k = 0; k < 8; ++k) {
-            kzg::G1Point g;
-            std::memcpy(g.xy, xy[k], 96);
-            g.infinity = inf[k] != 0;
-            (k < 5 ? fixed_commitments[k] : sigma_commitments[k - 5]) = kzg::KzgCommitment{g};
-        }
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        check(typlonk_circuit_compile_pairs_host(c, sel, n_, pairs.empty() ? nullptr : &pairs[0].a, pairs.size(), ks, log_n, &circuit_,
+                                                 &classes_), c);
+        fetch_commitments();
     }
     CompiledCircuit(const CompiledCircuit&) = delete;
     ~CompiledCircuit() {
         if (circuit_) typlonk_circuit_free(srs_.ctx().raw(), circuit_);
     }
     size_t rows() const { return n_; }
+    uint64_t classes() const { return classes_; }   // of the constructor from pairs (0 for the others)
     kzg::KzgCommitment fixed_commitments[5];  // [q_l], [q_r], [q_o], [q_m], [q_c]  (GateConstrains::fixed_commitments)
     kzg::KzgCommitment sigma_commitments[3];  // what CompiledPermutation::sigma_commitments returns
 
@@ -910,6 +939,25 @@ class CompiledCircuit {
         }
         return b;
     }
+    // the eight commitments of a compiled circuit from the library's cache; the sigma polynomials stay to be made
+    void fetch_commitments() {
+        typlonk_ctx* c = srs_.ctx().raw();
+        uint64_t xy[8][12];
+        uint8_t inf[8];
+        const int rc = typlonk_circuit_commitments(c, srs_.id(), circuit_, xy, inf);
+        if (rc < 0) {
+            typlonk_circuit_free(c, circuit_);
+            circuit_ = 0;
+            check(rc, c);
+        }
+        sigma_lazy_ = true;  // (the sigma polynomials are this mirror's verify()'s alone: ensure_sigma_polys makes them there)
+        for (int k = 0; k < 8; ++k) {
+            kzg::G1Point g;
+            std::memcpy(g.xy, xy[k], 96);
+            g.infinity = inf[k] != 0;
+            (k < 5 ? fixed_commitments[k] : sigma_commitments[k - 5]) = kzg::KzgCommitment{g};
+        }
+    }
     // verify() evaluates the sigma polynomials at zeta.  A circuit compiled from a permutation has none on the host until the
     // first verify(): the permutation comes back from the library's cache (typlonk_circuit_permutation, no recovery under the
     // circuit's own cosets), then Permutation::compile on the host (3n products) and one batch of three interpolations.
@@ -937,6 +985,7 @@ class CompiledCircuit {
     size_t n_;
     Fr cosets_[3];
     uint32_t circuit_ = 0;
+    uint64_t classes_ = 0;
     mutable poly::DensePolynomial sigma_polys_[3];
     mutable bool sigma_lazy_ = false;
 };
