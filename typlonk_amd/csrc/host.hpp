@@ -466,15 +466,116 @@ int circuit_vk_fill(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, cons
 int verify_compact_check_args(typlonk_ctx* ctx, const typlonk_vk* vk, size_t count, const uint64_t* const* pi, const size_t* pi_len,
                               typlonk::pairing::G2Affine* g2s);
 
+// ---- the columns of a call (the provers, the witness check, the compiles) ----------------------------------------------
+// One column: `rows` elements on the device or still on the HOST; the rest of the n it stands for are zero.
+struct ColumnSrc {
+    const Fr* dev = nullptr;
+    const uint64_t* host = nullptr;
+    uint64_t rows = 0;
+    bool present() const { return dev || host; }
+};
+// dst[0, n) <- the column: its rows with the copy its place asks for, zeros behind them; stream-ordered
+inline hipError_t column_to_device(Fr* dst, const ColumnSrc& c, uint64_t n, hipStream_t s) {
+    hipError_t e = c.dev ? hipMemcpyAsync(dst, c.dev, c.rows * sizeof(Fr), hipMemcpyDeviceToDevice, s)
+                         : hipMemcpyAsync(dst, c.host, c.rows * sizeof(Fr), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && c.rows < n) e = hipMemsetAsync(dst + c.rows, 0, (n - c.rows) * sizeof(Fr), s);
+    return e;
+}
+// What a caller handed in: `count` items (witnesses, or the one circuit of a compile) of `k` columns each, item-major, as
+// typlonk_buf handles or as host pointers; per item an optional public-input column, read by one of two rules.  A single
+// proof is count == 1 over the addresses of the caller's own arguments.
+struct ColumnsOf {
+    enum PiRule {
+        NO_PI,
+        PI_FULL,    // the reference shape: the n rows of the column, where there is one
+        PI_FIRST,   // the compact shape: the column's first pi_len[item] rows
+    };
+    struct Names {   // what the refusals call the columns
+        const char *null_column, *short_column, *rows_not_n;
+    };
+    static constexpr Names WIRES{"null wire column", "wire column shorter than n", "wire columns must hold exactly n rows"};
+    static constexpr Names SELECTORS{"null selector column", "selector column shorter than n",
+                                     "selector columns must hold exactly n rows"};
+    size_t count = 0;
+    int k = 3;
+    const Names* names = &WIRES;
+    const typlonk_buf* const* bufs = nullptr;   // count * k handles, or
+    const uint64_t* const* host = nullptr;      // count * k host pointers
+    const typlonk_buf* const* pi_bufs = nullptr;   // null, or one (handle or null) per item
+    const uint64_t* const* pi_host = nullptr;
+    const size_t* pi_len = nullptr;             // PI_FIRST: null = no item has public inputs
+    PiRule rule = NO_PI;
+    bool rows_stated = false;                   // a host form that passes its columns' length: it must be n (admit_rows)
+    size_t rows = 0;
+
+    ColumnsOf(const typlonk_buf* const* cols, size_t items, PiRule r = NO_PI, const typlonk_buf* const* pi = nullptr, const size_t* len = nullptr)
+        : count(items), bufs(cols), pi_bufs(pi), pi_len(len), rule(r) {}
+    ColumnsOf(const uint64_t* const* cols, size_t items, PiRule r = NO_PI, const uint64_t* const* pi = nullptr, const size_t* len = nullptr)
+        : count(items), host(cols), pi_host(pi), pi_len(len), rule(r) {}
+    ColumnsOf& with_rows(size_t r) {
+        rows_stated = true;
+        rows = r;
+        return *this;
+    }
+    ColumnsOf& selectors() {
+        k = 5;
+        names = &SELECTORS;
+        return *this;
+    }
+
+    bool given() const { return bufs || host; }
+    bool on_device() const { return bufs != nullptr; }
+    ColumnSrc column(size_t item, int i, uint64_t n) const {
+        ColumnSrc c;
+        if (bufs) c.dev = bufs[k * item + i]->d;
+        else c.host = host[k * item + i];
+        c.rows = n;
+        return c;
+    }
+    bool has_pi(size_t item) const { return bufs ? (pi_bufs && pi_bufs[item]) : (pi_host && pi_host[item]); }
+    // rows of the item's public-input column that are read (0: the zero polynomial)
+    uint64_t pi_rows(size_t item, uint64_t n) const {
+        if (rule == PI_FIRST) return pi_len ? pi_len[item] : 0;
+        return rule == PI_FULL && has_pi(item) ? n : 0;
+    }
+    ColumnSrc pi(size_t item, uint64_t n) const {   // (of admitted columns)
+        ColumnSrc c;
+        if (!(c.rows = pi_rows(item, n))) return c;
+        if (bufs) c.dev = pi_bufs[item]->d;
+        else c.host = pi_host[item];
+        return c;
+    }
+};
+// THE admission of a call's columns for a domain of n rows: the first refusal, or TYPLONK_OK.  Column by column a null one,
+// then a handle of fewer than n elements; then item by item the public inputs.  tests/golden/column_refusals.json pins where
+// each entry point places this among its other refusals, and which refusal wins when a call makes two mistakes.
+inline int admit_columns(typlonk_ctx* ctx, const ColumnsOf& in, uint64_t n) {
+    for (size_t c = 0; c < in.k * in.count; ++c) {
+        if (in.bufs ? !in.bufs[c] : !in.host[c]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, in.names->null_column);
+        if (in.bufs && in.bufs[c]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, in.names->short_column);
+    }
+    for (size_t item = 0; item < in.count; ++item) {
+        if (in.rule == ColumnsOf::PI_FULL && in.bufs && in.has_pi(item) && in.pi_bufs[item]->n < n)
+            return fail(ctx, TYPLONK_ERR_RANGE, "public-input column shorter than n");
+        const uint64_t len = in.rule == ColumnsOf::PI_FIRST ? in.pi_rows(item, n) : 0;
+        if (!len) continue;
+        if (!in.has_pi(item)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "pi_len != 0 without public inputs");
+        if (in.bufs && in.pi_bufs[item]->n < len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
+        if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
+    }
+    return TYPLONK_OK;
+}
+// ... and of the length a host form states for its columns.  (A function of its own: the entry points judge it at three
+// different places -- the compact prover before the columns, the witness check and the compiles right behind them, the batch
+// provers behind the SRS.)
+inline int admit_rows(typlonk_ctx* ctx, const ColumnsOf& in, uint64_t n) {
+    if (in.rows_stated && in.rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, in.names->rows_not_n);
+    return TYPLONK_OK;
+}
+
 // ---- witness_check.hip ----------------------------------------------------------------------------------------------
 // frees a circuit's recovered permutation and selector evaluations (typlonk_circuit_free, typlonk_destroy)
 void circuit_check_release(CircuitEntry& e);
-// the selector columns of a compile: typlonk_buf handles, or host pointers of `rows` elements each
-struct SelectorsIn {
-    const typlonk_buf* const* bufs;
-    const uint64_t* const* host;
-    size_t rows;   // the host form's column length (must be n)
-};
 // where the permutation a compile keeps comes from: 3n successors in HOST memory, or a producer that writes them into the
 // kept copy on the device (perm_pairs.hip), or neither: the identity
 struct PermSource {
@@ -483,7 +584,7 @@ struct PermSource {
     void* arg = nullptr;
 };
 // typlonk_circuit_compile behind its entry points and behind typlonk_circuit_compile_pairs
-int circuit_compile_from(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
+int circuit_compile_from(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
                          uint32_t* circuit_id, uint64_t* defects);
 
 // ---- comm.hip -------------------------------------------------------------------------------------------------------

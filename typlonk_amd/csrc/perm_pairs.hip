@@ -316,7 +316,7 @@ int fill_from_pairs(typlonk_ctx* ctx, uint32_t* d_perm, void* arg) {
     return perm_from_pairs(ctx, a->pairs, a->count, a->log_n, d_perm, nullptr, &a->classes);
 }
 
-int compile_pairs_impl(typlonk_ctx* ctx, const SelectorsIn& in, const uint32_t* pairs, size_t count, const uint64_t cosets[3][4],
+int compile_pairs_impl(typlonk_ctx* ctx, const ColumnsOf& in, const uint32_t* pairs, size_t count, const uint64_t cosets[3][4],
                        uint32_t log_n, uint32_t* circuit_id, uint64_t* classes) {
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     int rc = check_pairs_args(ctx, pairs, count, log_n);
@@ -346,11 +346,11 @@ int typlonk_permutation_from_pairs(typlonk_ctx* ctx, const uint32_t* pairs, size
 int typlonk_circuit_compile_pairs(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* pairs,
                                   size_t count, const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id,
                                   uint64_t* classes) {
-    return compile_pairs_impl(ctx, SelectorsIn{selector_evals, nullptr, 0}, pairs, count, cosets, log_n, circuit_id, classes);
+    return compile_pairs_impl(ctx, ColumnsOf(selector_evals, 1).selectors(), pairs, count, cosets, log_n, circuit_id, classes);
 }
 
 int typlonk_circuit_compile_pairs_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows,
                                        const uint32_t* pairs, size_t count, const uint64_t cosets[3][4], uint32_t log_n,
                                        uint32_t* circuit_id, uint64_t* classes) {
-    return compile_pairs_impl(ctx, SelectorsIn{nullptr, selector_evals, rows}, pairs, count, cosets, log_n, circuit_id, classes);
+    return compile_pairs_impl(ctx, ColumnsOf(selector_evals, 1).selectors().with_rows(rows), pairs, count, cosets, log_n, circuit_id, classes);
 }

@@ -269,26 +269,6 @@ __global__ __launch_bounds__(256) void pb_fold_kernel(PbFoldArgs a) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-struct ColumnsIn {   // the caller's columns: device buffers or host arrays, proof-major
-    const typlonk_buf* const* wire_bufs;
-    const typlonk_buf* const* pi_bufs;
-    const uint64_t* const* wire_host;
-    const uint64_t* const* pi_host;
-    const size_t* pi_len = nullptr;   // the compact shape: proof k's column is its first pi_len[k] rows, the rest zero
-    bool compact = false;
-    const void* wire(size_t k, int i) const { return wire_bufs ? (const void*)wire_bufs[3 * k + i]->d : (const void*)wire_host[3 * k + i]; }
-    const void* pi(size_t k) const {
-        if (wire_bufs) return pi_bufs && pi_bufs[k] ? (const void*)pi_bufs[k]->d : nullptr;
-        return pi_host ? (const void*)pi_host[k] : nullptr;
-    }
-    // rows of proof k's public-input column that are read (0: the zero polynomial)
-    uint64_t pi_rows(size_t k, uint64_t n) const {
-        if (compact) return pi_len ? pi_len[k] : 0;
-        return pi(k) ? n : 0;
-    }
-    hipMemcpyKind kind() const { return wire_bufs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
-};
-
 struct Wave {
     typlonk_ctx* ctx;
     const SrsEntry* srs;
@@ -315,7 +295,7 @@ int upload(const Wave& w, const void* host_part, size_t bytes) {
 // extensions of a, b, c, Z (and PI) queued, and the quotient's per-proof table (w.host->quot) filled.  Script: the shape's
 // Fiat-Shamir script (proof_script.hpp), one per proof.
 template <class Script>
-int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typename Script::Proof* out, std::vector<Script>& tr) {
+int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typename Script::Proof* out, std::vector<Script>& tr) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = w.n, n4 = 4 * n;
@@ -332,14 +312,12 @@ int wave_rounds12(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typena
     std::vector<const Fr*> ext_src;
     for (uint32_t p = 0; p < G && !rc; ++p) {
         for (int i = 0; i < 3 && !rc; ++i) {
-            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_EV + i), in.wire(first + p, i), n * sizeof(Fr), in.kind(), s));
+            rc = hip_rc(ctx, column_to_device(w.at(p, PB_EV + i), in.column(first + p, i, n), n, s));
             if (!rc) rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_CO + i), w.at(p, PB_EV + i), n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
             co.push_back(w.at(p, PB_CO + i));
         }
-        if (!rc && has_pi[p]) {
-            const uint64_t rows = in.pi_rows(first + p, n);   // (the compact shape reads pi_len rows; the rest are zero)
-            rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_PI), in.pi(first + p), rows * sizeof(Fr), in.kind(), s));
-            if (!rc && rows < n) rc = hip_rc(ctx, hipMemsetAsync(w.at(p, PB_PI) + rows, 0, (n - rows) * sizeof(Fr), s));
+        if (!rc && has_pi[p]) {   // (the compact shape reads pi_len rows; the rest are zero)
+            rc = hip_rc(ctx, column_to_device(w.at(p, PB_PI), in.pi(first + p, n), n, s));
             co.push_back(w.at(p, PB_PI));
         }
     }
@@ -495,7 +473,7 @@ int wave_quotient(Wave& w, uint32_t G) {
     return ntt_run_batch(ctx, ts.data(), G, log4, 1, g_limbs, /*sync=*/false);
 }
 
-int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
+int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = w.n, stride = PB_STRIDE * n;
@@ -573,7 +551,7 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
 
 // A wave in the compact shape (typlonk_prove_compact's order, prover.hip prover_round3_compact).  The host waits four times --
 // round 1's, round 2's and the quotient's commitments, round 3's evaluations -- plus the final read.
-int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_proof_compact* out, int* status) {
+int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_proof_compact* out, int* status) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = w.n, stride = PB_STRIDE * n;
@@ -586,19 +564,19 @@ int run_wave(Wave& w, const ColumnsIn& in, size_t first, uint32_t G, typlonk_pro
     std::vector<CompactScript> tr;
     tr.reserve(G);
     {
-        std::vector<std::vector<uint64_t>> fetched(in.wire_bufs ? G : 0);
+        std::vector<std::vector<uint64_t>> fetched(in.on_device() ? G : 0);
         bool any = false;
-        for (uint32_t p = 0; p < G && in.wire_bufs; ++p) {
-            const uint64_t rows = in.pi_rows(first + p, n);
-            if (!rows) continue;
-            fetched[p].resize(4 * rows);
-            HIPCHK(hipMemcpyAsync(fetched[p].data(), in.pi(first + p), rows * sizeof(Fr), hipMemcpyDeviceToHost, s));
+        for (uint32_t p = 0; p < G && in.on_device(); ++p) {
+            const ColumnSrc pi = in.pi(first + p, n);
+            if (!pi.rows) continue;
+            fetched[p].resize(4 * pi.rows);
+            HIPCHK(hipMemcpyAsync(fetched[p].data(), pi.dev, pi.rows * sizeof(Fr), hipMemcpyDeviceToHost, s));
             any = true;
         }
         if (any) HIPCHK(hipStreamSynchronize(s));
         for (uint32_t p = 0; p < G; ++p) {
             const uint64_t rows = in.pi_rows(first + p, n);
-            const uint64_t* vals = !rows ? nullptr : in.wire_bufs ? fetched[p].data() : (const uint64_t*)in.pi(first + p);
+            const uint64_t* vals = !rows ? nullptr : in.on_device() ? fetched[p].data() : in.pi(first + p, n).host;
             uint8_t d0[64];
             compact_statement_digest(*w.vk, vals, rows, d0);
             tr.emplace_back(d0);
@@ -693,34 +671,20 @@ struct BusyGuard {
     }
 };
 
-// rows: the compact host form's column length (must be n), SIZE_MAX where the form does not state one
 template <class Proof>
-int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsIn& in, size_t rows, size_t count,
-                     const uint64_t cosets[3][4], Proof* out, int* status) {
+int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsOf& in, const uint64_t cosets[3][4],
+                     Proof* out, int* status) {
+    const size_t count = in.count;
+    const bool compact = in.rule == ColumnsOf::PI_FIRST;
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     if (count == 0) return TYPLONK_OK;
-    if (!cosets || !out || !status || !(in.wire_bufs || in.wire_host)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (!cosets || !out || !status || !in.given()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     auto ci = ctx->circuits.find(circuit_id);
     if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
     const uint32_t log_n = ci->second.log_n;
-    if (in.compact && log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "prover supports up to 2^24 rows");
+    if (compact && log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "prover supports up to 2^24 rows");
     const uint64_t n = 1ull << log_n;
-    for (size_t k = 0; k < 3 * count; ++k) {
-        if (in.wire_bufs ? !in.wire_bufs[k] : !in.wire_host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
-        if (in.wire_bufs && in.wire_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
-    }
-    if (in.compact) {
-        for (size_t k = 0; k < count; ++k) {
-            const uint64_t len = in.pi_rows(k, n);
-            if (!len) continue;
-            if (!in.pi(k)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "pi_len != 0 without public inputs");
-            if (in.wire_bufs && in.pi_bufs[k]->n < len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
-            if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
-        }
-    } else if (in.wire_bufs && in.pi_bufs) {
-        for (size_t k = 0; k < count; ++k)
-            if (in.pi_bufs[k] && in.pi_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "public-input column shorter than n");
-    }
+    if (const int arc = admit_columns(ctx, in, n)) return arc;
     auto si = ctx->srs.find(srs_id);
     if (si == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown srs id");
     if (si->second.total_len || comm_folds(ctx, srs_id))
@@ -730,11 +694,11 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
                     "batched proving needs a whole SRS on one GPU, not a shard (shard single large proofs with "
                     "typlonk_prove / typlonk_prove_compact; give each GPU its own batch)");
     if (si->second.len < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
-    if (rows != SIZE_MAX && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
+    if (const int arc = admit_rows(ctx, in, n)) return arc;
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
     HIPCHK(hipSetDevice(ctx->device));
     typlonk_vk vk;
-    if (in.compact) {
+    if (compact) {
         // the statement's shared part: the circuit's commitments (one batch of eight MSMs the first time per circuit and SRS,
         // then cached) and P0 -- once per call, not per proof or wave
         memset((void*)out, 0, count * sizeof(Proof));
@@ -770,7 +734,7 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
     w.host = (PbTables*)ctx->batch_host;
     w.dev = (PbTables*)ctx->batch_tab.p;
     w.slots = ctx->eval_slots_host;
-    w.vk = in.compact ? &vk : nullptr;
+    w.vk = compact ? &vk : nullptr;
     for (int i = 0; i < 3; ++i) memcpy(w.k[i].v, cosets[i], 32);
     for (size_t first = 0; first < count && !rc; first += G) {
         const uint32_t g = (uint32_t)std::min<size_t>(G, count - first);
@@ -784,28 +748,25 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
 int typlonk_prove_batch(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
                         const typlonk_buf* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
                         int* status) {
-    const ColumnsIn in{wire_evals, pi_evals, nullptr, nullptr};
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FULL, pi_evals), cosets, out, status);
 }
 
 int typlonk_prove_batch_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
                              const uint64_t* const* pi_evals, size_t count, const uint64_t cosets[3][4], typlonk_proof* out,
                              int* status) {
-    const ColumnsIn in{nullptr, nullptr, wire_evals, pi_evals};
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FULL, pi_evals), cosets, out, status);
 }
 
 int typlonk_prove_batch_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
                                 const typlonk_buf* const* pi, const size_t* pi_len, size_t count, const uint64_t cosets[3][4],
                                 typlonk_proof_compact* out, int* status) {
-    const ColumnsIn in{wire_evals, pi, nullptr, nullptr, pi_len, true};
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, SIZE_MAX, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FIRST, pi, pi_len), cosets, out,
+                            status);
 }
 
 int typlonk_prove_batch_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const* wire_evals,
                                      size_t rows, const uint64_t* const* pi, const size_t* pi_len, size_t count,
                                      const uint64_t cosets[3][4], typlonk_proof_compact* out, int* status) {
-    const ColumnsIn in{nullptr, nullptr, wire_evals, pi, pi_len, true};
-    // (SIZE_MAX means "no row count stated" to prove_batch_impl: as a caller's row count it is refused like any other != n)
-    return prove_batch_impl(ctx, srs_id, circuit_id, in, rows == SIZE_MAX ? 0 : rows, count, cosets, out, status);
+    return prove_batch_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FIRST, pi, pi_len).with_rows(rows),
+                            cosets, out, status);
 }

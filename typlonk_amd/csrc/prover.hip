@@ -439,41 +439,20 @@ int prover_linearise(typlonk_prover* p, const CircuitEntry& ce, const Fr* scalar
     launch_lincomb(la, p->ctx->stream);
     return hip_rc(p->ctx, hipGetLastError());
 }
-}  // namespace
-
-namespace {
-// One column of round 1's input: n evaluations on the device (a typlonk_buf) or still on the HOST (typlonk_prove_host: the
-// reference's prove() holds its padded, blinded columns as Vec<Fr>, plonk/src/proof.rs:43-49).
-struct ColumnSrc {
-    const Fr* dev = nullptr;
-    const uint64_t* host = nullptr;
-    uint64_t rows = ~0ull;   // rows read from dev / host (the compact shape's public inputs); the rest of the n are zero
-    bool present() const { return dev || host; }
-};
-int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnSrc (&wires)[3], const ColumnSrc& pi,
-                       typlonk_prover** out, uint64_t commit_xy[3][12], uint8_t commit_inf[3]);
-}  // namespace
-
-int typlonk_prover_round1(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
-                          const typlonk_buf* pi_evals, typlonk_prover** out, uint64_t commit_xy[3][12],
-                          uint8_t commit_inf[3]) {
-    if (!ctx || !wire_evals || !out || !commit_xy || !commit_inf) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    auto ci = ctx->circuits.find(circuit_id);
-    if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
-    const uint64_t n = 1ull << ci->second.log_n;
-    ColumnSrc w[3], pi;
-    for (int i = 0; i < 3; ++i) {
-        if (!wire_evals[i] || wire_evals[i]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
-        w[i].dev = wire_evals[i]->d;
-    }
-    if (pi_evals) {
-        if (pi_evals->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "public-input column shorter than n");
-        pi.dev = pi_evals->d;
-    }
-    return prover_round1_impl(ctx, srs_id, circuit_id, w, pi, out, commit_xy, commit_inf);
+// typlonk_prover_round1, typlonk_prove and typlonk_prove_compact answer a null wire HANDLE with TYPLONK_ERR_RANGE, as a column
+// of no rows (the other entry points: admit_columns' TYPLONK_ERR_INVALID_ARG); a null host column they refuse first of all
+int null_handle_is_short(typlonk_ctx* ctx, const ColumnsOf& in) {
+    for (int i = 0; i < 3 && in.bufs; ++i)
+        if (!in.bufs[i]) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
+    return TYPLONK_OK;
 }
-
-namespace {
+int null_host_column(typlonk_ctx* ctx, const uint64_t* const wire_evals[3]) {
+    for (int i = 0; i < 3; ++i)
+        if (!wire_evals[i]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
+    return TYPLONK_OK;
+}
+// wires, pi_src: n evaluations each on the device (a typlonk_buf) or still on the HOST (typlonk_prove_host: the reference's
+// prove() holds its padded, blinded columns as Vec<Fr>, plonk/src/proof.rs:43-49); pi_src may be absent
 int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnSrc (&wires)[3], const ColumnSrc& pi_src,
                        typlonk_prover** out, uint64_t commit_xy[3][12], uint8_t commit_inf[3]) {
     HIPCHK(hipSetDevice(ctx->device));
@@ -512,32 +491,19 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     // of the quotient inputs run while it is being sorted and accumulated.  (Batched transforms, ntt_run_batch, LOSE
     // 0.3-0.5 ms per 2^20 proof here: they delay a commitment's start by the other columns' transforms, which were already
     // hidden beside the commitments' sorts, profiles/r06_ab_prover_ntt_batch.txt.)
-    auto d2d = [&](Fr* dst, const Fr* src) -> int {
-        return hip_rc(ctx, hipMemcpyAsync(dst, src, n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
-    };
-    // a column into its place on the device: device -> device, or host -> device on the context's stream -- issued column by
-    // column, each right before that column's transform and commitment are queued, so column i + 1 crosses PCIe while column i
-    // is being transformed, sorted and accumulated
-    auto fetch = [&](Fr* dst, const ColumnSrc& c) -> int {
-        if (c.rows < n) {
-            hipError_t e = c.dev ? hipMemcpyAsync(dst, c.dev, c.rows * sizeof(Fr), hipMemcpyDeviceToDevice, s)
-                                 : hipMemcpyAsync(dst, c.host, c.rows * sizeof(Fr), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemsetAsync(dst + c.rows, 0, (n - c.rows) * sizeof(Fr), s);
-            return hip_rc(ctx, e);
-        }
-        if (c.dev) return d2d(dst, c.dev);
-        return hip_rc(ctx, hipMemcpyAsync(dst, c.host, n * sizeof(Fr), hipMemcpyHostToDevice, s));
-    };
+    // Each column goes into its place (column_to_device: device -> device, or host -> device on the context's stream) right
+    // before that column's transform and commitment are queued, so column i + 1 crosses PCIe while column i is being
+    // transformed, sorted and accumulated
     MsmQueue q(ctx, srs, /*first_lane=*/1);
     p->has_pi = pi_src.present();  // absent: public inputs [0] -> the zero polynomial
     for (int i = 0; i < 3 && !rc; ++i) {
-        if ((rc = fetch(p->ev[i], wires[i]))) break;
-        if ((rc = d2d(p->co[i], p->ev[i]))) break;
+        if ((rc = hip_rc(ctx, column_to_device(p->ev[i], wires[i], n, s)))) break;
+        if ((rc = hip_rc(ctx, hipMemcpyAsync(p->co[i], p->ev[i], n * sizeof(Fr), hipMemcpyDeviceToDevice, s)))) break;
         if ((rc = ntt_run(ctx, p->co[i], log_n, 1, nullptr, false))) break;
         rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
     }
     if (!rc && p->has_pi) {
-        rc = fetch(p->pi, pi_src);
+        rc = hip_rc(ctx, column_to_device(p->pi, pi_src, n, s));
         if (!rc) rc = ntt_run(ctx, p->pi, log_n, 1, nullptr, false);  // proof.rs:105-106
     }
     // the coset transforms of the quotient's per-proof inputs run beside the commitments (measured: -1 % per proof;
@@ -557,7 +523,28 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     *out = p;
     return TYPLONK_OK;
 }
+
+// round 1 of one proof from the caller's columns (the reference shape's rule for the public inputs)
+int prover_round1_from(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsOf& in, typlonk_prover** out,
+                       uint64_t commit_xy[3][12], uint8_t commit_inf[3]) {
+    auto ci = ctx->circuits.find(circuit_id);
+    if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
+    const uint64_t n = 1ull << ci->second.log_n;
+    int rc = null_handle_is_short(ctx, in);
+    if (!rc) rc = admit_columns(ctx, in, n);
+    if (rc) return rc;
+    const ColumnSrc w[3] = {in.column(0, 0, n), in.column(0, 1, n), in.column(0, 2, n)};
+    return prover_round1_impl(ctx, srs_id, circuit_id, w, in.pi(0, n), out, commit_xy, commit_inf);
+}
 }  // namespace
+
+int typlonk_prover_round1(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
+                          const typlonk_buf* pi_evals, typlonk_prover** out, uint64_t commit_xy[3][12],
+                          uint8_t commit_inf[3]) {
+    if (!ctx || !wire_evals || !out || !commit_xy || !commit_inf) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    return prover_round1_from(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, 1, ColumnsOf::PI_FULL, &pi_evals), out, commit_xy,
+                              commit_inf);
+}
 
 int typlonk_prover_round2(typlonk_prover* p, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t cosets[3][4],
                           uint64_t z_xy[12], uint8_t* z_inf) {
@@ -826,47 +813,16 @@ int typlonk_transcript_challenges(const uint64_t* xy, const uint8_t* inf, size_t
 }
 
 namespace {
-int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs, const typlonk_buf* pi_buf,
-               const uint64_t* const* wire_host, const uint64_t* pi_host, const uint64_t cosets[3][4], typlonk_proof* out);
-}  // namespace
-
-int typlonk_prove(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
-                  const typlonk_buf* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out) {
-    if (!ctx || !wire_evals || !cosets || !out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    return prove_impl(ctx, srs_id, circuit_id, wire_evals, pi_evals, nullptr, nullptr, cosets, out);
-}
-
-int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
-                       const uint64_t* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out) {
-    if (!ctx || !wire_evals || !cosets || !out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    for (int i = 0; i < 3; ++i)
-        if (!wire_evals[i]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
-    return prove_impl(ctx, srs_id, circuit_id, nullptr, nullptr, wire_evals, pi_evals, cosets, out);
-}
-
-namespace {
-int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs, const typlonk_buf* pi_buf,
-               const uint64_t* const* wire_host, const uint64_t* pi_host, const uint64_t cosets[3][4], typlonk_proof* out) {
+int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsOf& in, const uint64_t cosets[3][4],
+               typlonk_proof* out) {
     typlonk_prover* p = nullptr;
     // An SRS shard on a context with a communicator: every round's partial commitments are folded over the ranks (one
     // all-gather per round), so all ranks hash the same points and end with the same proof.  A rank whose round fails
     // (an OOM, say) still joins that round's collective with flagged records, so its peers return TYPLONK_ERR_COMM
     // instead of waiting for ever (comm_fold).
     const bool folds = comm_folds(ctx, srs_id);
-    int rc;
-    if (wire_host) {   // the columns are on the host: each is uploaded right before its transform and commitment are queued
-        auto ci = ctx->circuits.find(circuit_id);
-        if (ci == ctx->circuits.end()) {
-            rc = fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
-        } else {
-            ColumnSrc w[3], pi;
-            for (int i = 0; i < 3; ++i) w[i].host = wire_host[i];
-            pi.host = pi_host;
-            rc = prover_round1_impl(ctx, srs_id, circuit_id, w, pi, &p, out->commit_xy, out->commit_inf);
-        }
-    } else {
-        rc = typlonk_prover_round1(ctx, srs_id, circuit_id, wire_bufs, pi_buf, &p, out->commit_xy, out->commit_inf);
-    }
+    // (columns on the host: each is uploaded right before its transform and commitment are queued)
+    int rc = prover_round1_from(ctx, srs_id, circuit_id, in, &p, out->commit_xy, out->commit_inf);
     if (folds) rc = comm_fold(ctx, &out->commit_xy[0][0], out->commit_inf, 3, rc);
     if (rc) {
         if (p) typlonk_prover_free(p);
@@ -900,6 +856,19 @@ int prove_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typ
     return rc;
 }
 }  // namespace
+
+int typlonk_prove(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
+                  const typlonk_buf* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out) {
+    if (!ctx || !wire_evals || !cosets || !out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    return prove_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, 1, ColumnsOf::PI_FULL, &pi_evals), cosets, out);
+}
+
+int typlonk_prove_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
+                       const uint64_t* pi_evals, const uint64_t cosets[3][4], typlonk_proof* out) {
+    if (!ctx || !wire_evals || !cosets || !out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (const int rc = null_host_column(ctx, wire_evals)) return rc;
+    return prove_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, 1, ColumnsOf::PI_FULL, &pi_evals), cosets, out);
+}
 
 // ================================================================================================
 // The compact shape (include/typlonk.h, typlonk_prove_compact): rounds 1 and 2 as in typlonk_prove, then round 3 in the
@@ -1017,10 +986,7 @@ int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proo
 }
 
 // what typlonk_prove_compact refuses before it queues anything, in this order; fills the column sources
-// rows: the host form's column length (must be n), SIZE_MAX for the device form
-int prove_compact_args(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
-                       const uint64_t* const* wire_host, size_t rows, const typlonk_buf* pi_buf, const uint64_t* pi_host,
-                       size_t pi_len, ColumnSrc (&w)[3], ColumnSrc& pi) {
+int prove_compact_args(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsOf& in, ColumnSrc (&w)[3], ColumnSrc& pi) {
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
     auto ci = ctx->circuits.find(circuit_id);
@@ -1035,22 +1001,14 @@ int prove_compact_args(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
                     "a compact proof on an SRS shard needs a communicator on the context (typlonk_comm_init): its commitments are "
                     "folded over the ranks inside the call, before each challenge");
     if (si->second.total() < n) return fail(ctx, TYPLONK_ERR_LENGTH, "SRS shorter than the circuit's n");
-    if (pi_len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
-    if (!wire_bufs && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
-    for (int i = 0; i < 3; ++i) {
-        if (wire_bufs) {
-            if (!wire_bufs[i] || wire_bufs[i]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
-            w[i].dev = wire_bufs[i]->d;
-        } else {
-            w[i].host = wire_host[i];
-        }
-    }
-    if (pi_len) {
-        if (pi_buf && pi_buf->n < pi_len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
-        pi.dev = pi_buf ? pi_buf->d : nullptr;
-        pi.host = pi_host;
-        pi.rows = pi_len;
-    }
+    // (this entry point judges pi_len > n and the stated row count before it looks at the columns)
+    if (in.pi_rows(0, n) > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
+    int rc = admit_rows(ctx, in, n);
+    if (!rc) rc = null_handle_is_short(ctx, in);
+    if (!rc) rc = admit_columns(ctx, in, n);
+    if (rc) return rc;
+    for (int i = 0; i < 3; ++i) w[i] = in.column(0, i, n);
+    pi = in.pi(0, n);
     return TYPLONK_OK;
 }
 
@@ -1061,12 +1019,11 @@ int prove_compact_args(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
 // The counts depend on nothing a rank could see differently from its peers: not on its cache, not on which argument it
 // refuses.  From here on every path of a member ends in the next collective: a rank that fails joins it with flagged records
 // and returns its own code there, its peers return TYPLONK_ERR_COMM there (comm_fold), the prover is freed on every path.
-int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const* wire_bufs,
-                       const uint64_t* const* wire_host, size_t rows, const typlonk_buf* pi_buf, const uint64_t* pi_host,
-                       size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
+int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const ColumnsOf& in, const uint64_t cosets[3][4],
+                       typlonk_proof_compact* out) {
     const bool folds = comm_folds(ctx, srs_id);
     ColumnSrc w[3], pi;
-    int rc = prove_compact_args(ctx, srs_id, circuit_id, wire_bufs, wire_host, rows, pi_buf, pi_host, pi_len, w, pi);
+    int rc = prove_compact_args(ctx, srs_id, circuit_id, in, w, pi);
     if (rc && !folds) return rc;
     if (!rc) memset(out, 0, sizeof(*out));
     // the statement: the circuit's commitments (one batch of eight MSMs the first time per circuit and SRS, then cached), P0,
@@ -1077,7 +1034,8 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     if (!rc) rc = folds ? circuit_statement_partial(ctx, srs_id, circuit_id, rec_xy + 3, rec_inf + 3)
                         : circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
     std::vector<uint64_t> pi_vals;
-    const uint64_t* piv = pi_host;
+    const uint64_t* piv = pi.host;
+    const size_t pi_len = pi.rows;
     if (!rc && pi.dev) {
         pi_vals.resize(4 * pi_len);
         hipError_t he = hipMemcpyAsync(pi_vals.data(), pi.dev, pi_len * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
@@ -1123,16 +1081,16 @@ int prove_compact_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
 int typlonk_prove_compact(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const typlonk_buf* const wire_evals[3],
                           const typlonk_buf* pi, size_t pi_len, const uint64_t cosets[3][4], typlonk_proof_compact* out) {
     if (!ctx || !wire_evals || !cosets || !out || (pi_len && !pi)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    return prove_compact_impl(ctx, srs_id, circuit_id, wire_evals, nullptr, SIZE_MAX, pi, nullptr, pi_len, cosets, out);
+    return prove_compact_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, 1, ColumnsOf::PI_FIRST, &pi, &pi_len), cosets, out);
 }
 
 int typlonk_prove_compact_host(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, const uint64_t* const wire_evals[3],
                                size_t rows, const uint64_t* pi, size_t pi_len, const uint64_t cosets[3][4],
                                typlonk_proof_compact* out) {
     if (!ctx || !wire_evals || !cosets || !out || (pi_len && !pi)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
-    for (int i = 0; i < 3; ++i)
-        if (!wire_evals[i]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
-    return prove_compact_impl(ctx, srs_id, circuit_id, nullptr, wire_evals, rows, nullptr, pi, pi_len, cosets, out);
+    if (const int rc = null_host_column(ctx, wire_evals)) return rc;
+    return prove_compact_impl(ctx, srs_id, circuit_id, ColumnsOf(wire_evals, 1, ColumnsOf::PI_FIRST, &pi, &pi_len).with_rows(rows),
+                              cosets, out);
 }
 
 void typlonk_prover_free(typlonk_prover* p) {

@@ -331,17 +331,6 @@ int ensure_selectors(typlonk_ctx* ctx, CircuitEntry& e) {
     return TYPLONK_OK;
 }
 
-// the columns of a call: typlonk_buf handles, or host pointers
-struct WitnessIn {
-    const typlonk_buf* const* wire_bufs;
-    const typlonk_buf* const* pi_bufs;
-    const uint64_t* const* wire_host;
-    const uint64_t* const* pi_host;
-    const size_t* pi_len;
-    uint64_t pi_rows(size_t k) const { return pi_len ? pi_len[k] : 0; }
-    bool has_pi(size_t k) const { return wire_bufs ? (pi_bufs && pi_bufs[k]) : (pi_host && pi_host[k]); }
-};
-
 struct Outputs {
     uint32_t cap;
     typlonk_witness_report* reports;
@@ -421,32 +410,22 @@ int check_chunk(typlonk_ctx* ctx, const CircuitEntry& e, const std::vector<WcWit
     return TYPLONK_OK;
 }
 
-// rows: the host form's column length (must be n), SIZE_MAX for the device form
-int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const WitnessIn& in, size_t rows, size_t count,
-                       const uint64_t cosets[3][4], const Outputs& o) {
+int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const ColumnsOf& in, const uint64_t cosets[3][4], const Outputs& o) {
+    const size_t count = in.count;
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     if (count == 0) return TYPLONK_OK;
-    if (!cosets || !o.reports || !(in.wire_bufs || in.wire_host) || (o.cap && (!o.gate_rows || !o.copy_cells)))
+    if (!cosets || !o.reports || !in.given() || (o.cap && (!o.gate_rows || !o.copy_cells)))
         return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     auto ci = ctx->circuits.find(circuit_id);
     if (ci == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
     CircuitEntry& e = ci->second;
     const uint64_t n = 1ull << e.log_n;
-    for (size_t k = 0; k < 3 * count; ++k) {
-        if (in.wire_bufs ? !in.wire_bufs[k] : !in.wire_host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null wire column");
-        if (in.wire_bufs && in.wire_bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "wire column shorter than n");
-    }
-    for (size_t k = 0; k < count; ++k) {
-        const uint64_t len = in.pi_rows(k);
-        if (!len) continue;
-        if (!in.has_pi(k)) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "pi_len != 0 without public inputs");
-        if (in.wire_bufs && in.pi_bufs[k]->n < len) return fail(ctx, TYPLONK_ERR_RANGE, "public-input buffer shorter than pi_len");
-        if (len > n) return fail(ctx, TYPLONK_ERR_LENGTH, "more public inputs than rows");
-    }
-    if (rows != SIZE_MAX && rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "wire columns must hold exactly n rows");
+    int rc = admit_columns(ctx, in, n);
+    if (!rc) rc = admit_rows(ctx, in, n);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ProfilingOff prof_off(ctx);
-    int rc = ensure_perm(ctx, e, cosets);
+    rc = ensure_perm(ctx, e, cosets);
     if (rc) return rc;
     if (e.perm_defects)
         return fail(ctx, TYPLONK_ERR_INVALID_ARG,
@@ -456,39 +435,33 @@ int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const WitnessIn& i
     if (rc) return rc;
     // witnesses per launch: bounded by the workspace (masks, counts, lists) and, for the host form, by the staged columns
     const uint32_t cap_copy = (uint32_t)std::min<uint64_t>(o.cap, 3 * n);
-    const uint64_t per = n / 2 + n / 16 + 64 + 12ull * cap_copy + (in.wire_host ? 4 * n * sizeof(Fr) : 0);
+    const uint64_t per = n / 2 + n / 16 + 64 + 12ull * cap_copy + (in.on_device() ? 0 : 4 * n * sizeof(Fr));
     const size_t G = (size_t)std::min<uint64_t>({(uint64_t)count, 1024, std::max<uint64_t>(1, ((uint64_t)512 << 20) / per)});
     std::vector<WcWitness> tab;
     for (size_t first = 0; first < count; first += G) {
         const size_t g = std::min(G, count - first);
         tab.assign(g, WcWitness{});
-        if (in.wire_host) {
-            // stage the chunk: three columns per witness, then its public values
+        Fr* d = nullptr;
+        if (!in.on_device()) {
+            // the chunk is staged: three columns per witness, then its public values (only the rows that are read)
             size_t elems = 0;
-            for (size_t k = 0; k < g; ++k) elems += 3 * n + in.pi_rows(first + k);
+            for (size_t k = 0; k < g; ++k) elems += 3 * n + in.pi_rows(first + k, n);
             rc = ensure(ctx, ctx->wc_stage, elems * sizeof(Fr));
             if (rc) return rc;
-            Fr* d = (Fr*)ctx->wc_stage.p;
-            for (size_t k = 0; k < g; ++k) {
-                for (int i = 0; i < 3; ++i) {
-                    HIPCHK(hipMemcpyAsync(d, in.wire_host[3 * (first + k) + i], n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-                    tab[k].w[i] = d;
-                    d += n;
-                }
-                const uint64_t len = in.pi_rows(first + k);
-                if (len) {
-                    HIPCHK(hipMemcpyAsync(d, in.pi_host[first + k], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-                    tab[k].pi = d;
-                    d += len;
-                }
-                tab[k].pi_len = len;
-            }
-        } else {
-            for (size_t k = 0; k < g; ++k) {
-                for (int i = 0; i < 3; ++i) tab[k].w[i] = in.wire_bufs[3 * (first + k) + i]->d;
-                tab[k].pi_len = in.pi_rows(first + k);
-                tab[k].pi = tab[k].pi_len ? in.pi_bufs[first + k]->d : nullptr;
-            }
+            d = (Fr*)ctx->wc_stage.p;
+        }
+        // a column where the kernels read it: in its buffer, or copied into the next `rows` elements of the stage
+        auto place = [&](const ColumnSrc& c, const Fr** at) -> hipError_t {
+            *at = c.dev;
+            if (!c.host) return hipSuccess;   // in its buffer already, or absent
+            *at = d;
+            d += c.rows;
+            return column_to_device(d - c.rows, c, c.rows, ctx->stream);
+        };
+        for (size_t k = 0; k < g; ++k) {
+            for (int i = 0; i < 3; ++i) HIPCHK(place(in.column(first + k, i, n), &tab[k].w[i]));
+            tab[k].pi_len = in.pi_rows(first + k, n);
+            HIPCHK(place(in.pi(first + k, n), &tab[k].pi));
         }
         rc = check_chunk(ctx, e, tab, first, o);
         if (rc) return rc;
@@ -515,19 +488,17 @@ int check_cosets(typlonk_ctx* ctx, const uint64_t cosets[3][4], uint32_t log_n, 
     return TYPLONK_OK;
 }
 
-int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
+int circuit_compile_impl(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
                          uint32_t* circuit_id, uint64_t* defects) {
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
-    if (!(in.bufs || in.host) || !cosets || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    if (!in.given() || !cosets || !circuit_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
     const uint64_t n = 1ull << log_n, n3 = 3 * n;
-    for (int k = 0; k < 5; ++k) {
-        if (in.bufs ? !in.bufs[k] : !in.host[k]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null selector column");
-        if (in.bufs && in.bufs[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "selector column shorter than n");
-    }
-    if (in.host && in.rows != n) return fail(ctx, TYPLONK_ERR_LENGTH, "selector columns must hold exactly n rows");
+    int rc = admit_columns(ctx, in, n);
+    if (!rc) rc = admit_rows(ctx, in, n);
+    if (rc) return rc;
     SigmaTables t{};
-    int rc = check_cosets(ctx, cosets, log_n, t.k);
+    rc = check_cosets(ctx, cosets, log_n, t.k);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ProfilingOff prof_off(ctx);
@@ -576,10 +547,7 @@ int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const PermSour
                     "perm is not a permutation of the cells (" + std::to_string(e.perm_defects) + " defects, the lowest at cell " +
                         std::to_string(e.perm_first_bad) + ")");
     // the eight columns as evaluations in `coef`, interpolated there in one batch (builder.rs:84-88, proof.rs:334-338)
-    for (int k = 0; k < 5; ++k) {
-        if (in.bufs) HIPCHK(hipMemcpyAsync(e.coef + (uint64_t)k * n, in.bufs[k]->d, n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
-        else HIPCHK(hipMemcpyAsync(e.coef + (uint64_t)k * n, in.host[k], n * sizeof(Fr), hipMemcpyHostToDevice, s));
-    }
+    for (int k = 0; k < 5; ++k) HIPCHK(column_to_device(e.coef + (uint64_t)k * n, in.column(0, k, n), n, s));
     HIPCHK(hipMemcpyAsync(e.coef + 5 * n, e.sig_ev, n3 * sizeof(Fr), hipMemcpyDeviceToDevice, s));
     Fr* co[8];
     for (int k = 0; k < 8; ++k) co[k] = e.coef + (uint64_t)k * n;
@@ -597,7 +565,7 @@ int circuit_compile_impl(typlonk_ctx* ctx, const SelectorsIn& in, const PermSour
 
 namespace tyh {
 void circuit_check_release(CircuitEntry& e) { free_check_cache(e); }
-int circuit_compile_from(typlonk_ctx* ctx, const SelectorsIn& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
+int circuit_compile_from(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
                          uint32_t* circuit_id, uint64_t* defects) {
     return circuit_compile_impl(ctx, in, from, cosets, log_n, circuit_id, defects);
 }
@@ -625,29 +593,28 @@ int typlonk_circuit_permutation(typlonk_ctx* ctx, uint32_t circuit_id, const uin
 int typlonk_witness_check(typlonk_ctx* ctx, uint32_t circuit_id, const typlonk_buf* const* wire_evals,
                           const typlonk_buf* const* pi, const size_t* pi_len, size_t count, const uint64_t cosets[3][4],
                           uint32_t cap, typlonk_witness_report* reports, uint32_t* gate_rows, uint32_t* copy_cells) {
-    const WitnessIn in{wire_evals, pi, nullptr, nullptr, pi_len};
-    return witness_check_impl(ctx, circuit_id, in, SIZE_MAX, count, cosets, Outputs{cap, reports, gate_rows, copy_cells});
+    return witness_check_impl(ctx, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FIRST, pi, pi_len), cosets,
+                              Outputs{cap, reports, gate_rows, copy_cells});
 }
 
 int typlonk_witness_check_host(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t* const* wire_evals, size_t rows,
                                const uint64_t* const* pi, const size_t* pi_len, size_t count, const uint64_t cosets[3][4],
                                uint32_t cap, typlonk_witness_report* reports, uint32_t* gate_rows, uint32_t* copy_cells) {
-    const WitnessIn in{nullptr, nullptr, wire_evals, pi, pi_len};
-    // (SIZE_MAX means "no row count stated" to witness_check_impl: as a caller's row count it is refused like any other != n)
-    return witness_check_impl(ctx, circuit_id, in, rows == SIZE_MAX ? 0 : rows, count, cosets,
-                              Outputs{cap, reports, gate_rows, copy_cells});
+    return witness_check_impl(ctx, circuit_id, ColumnsOf(wire_evals, count, ColumnsOf::PI_FIRST, pi, pi_len).with_rows(rows),
+                              cosets, Outputs{cap, reports, gate_rows, copy_cells});
 }
 
 int typlonk_circuit_compile(typlonk_ctx* ctx, const typlonk_buf* const selector_evals[5], const uint32_t* perm,
                             const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
     PermSource from{};
     from.host = perm;
-    return circuit_compile_impl(ctx, SelectorsIn{selector_evals, nullptr, 0}, from, cosets, log_n, circuit_id, defects);
+    return circuit_compile_impl(ctx, ColumnsOf(selector_evals, 1).selectors(), from, cosets, log_n, circuit_id, defects);
 }
 
 int typlonk_circuit_compile_host(typlonk_ctx* ctx, const uint64_t* const selector_evals[5], size_t rows, const uint32_t* perm,
                                  const uint64_t cosets[3][4], uint32_t log_n, uint32_t* circuit_id, uint64_t* defects) {
     PermSource from{};
     from.host = perm;
-    return circuit_compile_impl(ctx, SelectorsIn{nullptr, selector_evals, rows}, from, cosets, log_n, circuit_id, defects);
+    return circuit_compile_impl(ctx, ColumnsOf(selector_evals, 1).selectors().with_rows(rows), from, cosets, log_n, circuit_id,
+                                defects);
 }
