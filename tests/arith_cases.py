@@ -7,6 +7,7 @@ Operand forms (what the harness tests/cpp/device_arith.hip takes):
   Fq30   one int < 2^390, 13 normalised 30-bit limbs (x * 2^390 mod p, possibly lifted by multiples of p)
   Fr30   a list of 9 limbs, each < 2^32 (lazy forms carry limbs above 2^30)
   G1     tuples of Fq30 ints: XYZZ (X, Y, ZZ, ZZZ), Jacobian (X, Y, Z), affine (x, y)
+  wave   64 XYZZ tuples, one per lane of a wavefront (the cross-lane additions of msm_common.hpp)
 
 Every list is deterministic (fixed seeds) and starts with whole 64-lane waves of one kind (all zero, all easy) before the
 mixed ones, so that the wave-uniform early exit of the divsteps inversions and the exceptional branches of the group law
@@ -653,3 +654,143 @@ def g1_check(name: str, a, b, flag, out: list[int]) -> None:
         return
     assert _xyzz_ok(out), "XYZZ invariants X < 5.1p, Y < 3.2p, ZZ, ZZZ < 1.1p"
     assert xyzz_point(out) == want, "point"
+
+
+# ---- wavefront butterflies (msm_common.hpp) ----------------------------------------------------------------------------
+# One case = (label, param, wave): 64 XYZZ tuples, lane by lane, for butterfly_add(v, mask), butterfly_add4(v, mask)
+# (identical on lanes l and l ^ 1: its precondition) or butterfly_reduce(v, lanes).  Every kind of wave is built twice: with
+# random lifts of the coordinates and with the largest lifts the XYZZ invariants admit (`top`).
+WAVE_OPS = {"butterfly_add": 0, "butterfly_add4": 1, "butterfly_reduce": 2}
+WAVE_PARAMS = {"butterfly_add": (1, 2, 4, 8, 16, 32), "butterfly_add4": (2, 4, 8, 16, 32), "butterfly_reduce": (1, 2, 4, 8, 16, 32, 64)}
+_WAVE_POOL: list = []
+
+
+def wave_pool() -> list:
+    """random points of E(Fp), made once (a square root each)"""
+    if not _WAVE_POOL:
+        rnd = random.Random(0xB077E7F1)
+        while len(_WAVE_POOL) < 3 * WAVE:
+            q = random_point(rnd)
+            if q not in _WAVE_POOL and O.g1_neg(q) not in _WAVE_POOL:
+                _WAVE_POOL.append(q)
+    return _WAVE_POOL
+
+
+def _pair_units(rnd, units: int, pm: int, top: bool) -> list[tuple[str, list]]:
+    """the waves of one butterfly step as `units` operands, unit u meeting unit u ^ pm (butterfly_add: a unit is a lane and
+    pm the mask; butterfly_add4: a unit is the lane pair {2u, 2u + 1} and pm = mask / 2)"""
+    pool = wave_pool()
+    lower = [u for u in range(units) if not u & pm]
+
+    def ordinary():
+        return [xyzz_of(q, rnd, top) for q in rnd.sample(pool, units)]
+
+    def inf(alt=False):
+        return xyzz_of(None, rnd, top != alt)
+
+    def with_z(q, z):
+        return xyzz_of(q, rnd, top, z)
+
+    out = [("random", ordinary())]
+    out.append(("identity", [inf() for _ in range(units)]))
+    if not top:   # both encodings of the identity in one wave, also as partners
+        out.append(("identity, both encodings", [inf(rnd.random() < 0.5) for _ in range(units)]))
+    w = ordinary()
+    out.append(("identity below", [inf(u % 3 == 0) if not u & pm else w[u] for u in range(units)]))
+    out.append(("identity above", [inf(u % 3 == 0) if u & pm else w[u] for u in range(units)]))
+    out.append(("identity on a random subset", [inf(rnd.random() < 0.5) if rnd.random() < 0.4 else w[u] for u in range(units)]))
+    w = ordinary()
+    out.append(("same point, different Z", [xyzz_of(pool[min(u, u ^ pm)], rnd, top) for u in range(units)]))
+    for u in lower:
+        w[u ^ pm] = w[u]
+    out.append(("same point, identical words", list(w)))
+    out.append(("opposite points, different Z",
+                [xyzz_of(pool[u] if not u & pm else O.g1_neg(pool[u ^ pm]), rnd, top) for u in range(units)]))
+    # exactly one exceptional pair among ordinary ones: the wave-uniform branch runs for it alone
+    for where, u in (("first", lower[0]), ("last", lower[-1]), ("middle", lower[len(lower) // 2])):
+        for kind in ("equal", "opposite", "identity"):
+            w = ordinary()
+            a = xyzz_point(w[u])
+            w[u ^ pm] = with_z(a, None) if kind == "equal" else with_z(O.g1_neg(a), None) if kind == "opposite" else inf()
+            if kind == "identity" and where == "middle":
+                w[u], w[u ^ pm] = w[u ^ pm], w[u]
+            out.append((f"one {kind} pair, {where}", w))
+    return out
+
+
+def _reduce_waves(rnd, top: bool) -> list[tuple[str, list]]:
+    pool = wave_pool()
+    lane = lambda q: xyzz_of(q, rnd, top)   # noqa: E731
+    inf = lambda: xyzz_of(None, rnd, top != (rnd.random() < 0.3))   # noqa: E731
+    out = [("random", [lane(q) for q in rnd.sample(pool, WAVE)])]
+    out.append(("identity", [inf() for _ in range(WAVE)]))
+    w = [lane(q) for q in rnd.sample(pool, WAVE)]
+    out.append(("identity on a random subset", [inf() if rnd.random() < 0.4 else w[i] for i in range(WAVE)]))
+    out.append(("same point on lane pairs, different Z", [lane(pool[i // 2]) for i in range(WAVE)]))
+    out.append(("opposite points on lane pairs", [lane(pool[i // 2] if i % 2 == 0 else O.g1_neg(pool[i // 2])) for i in range(WAVE)]))
+    # the exception arises at the second step: P + Q meets Q + P in another representation; P + Q meets -(P + Q)
+    out.append(("P Q Q P", [lane(pool[2 * (i // 4) + (1 if i % 4 in (1, 2) else 0)]) for i in range(WAVE)]))
+    out.append(("P Q -P -Q", [lane(pool[2 * (i // 4) + i % 2] if i % 4 < 2 else O.g1_neg(pool[2 * (i // 4) + i % 2])) for i in range(WAVE)]))
+    out.append(("one point, a Z per lane", [lane(pool[7]) for _ in range(WAVE)]))
+    out.append(("one point, identical words", [lane(pool[8])] * WAVE))
+    # 2A on lanes 0 and 1 in two representations, then a step that takes its operand from both lanes
+    w = [lane(q) for q in rnd.sample(pool[16:], WAVE)]
+    w[0], w[1], w[2], w[3] = lane(pool[9]), lane(pool[9]), lane(pool[10]), inf()
+    out.append(("A A H identity, then random", w))
+    return out
+
+
+def wave_cases(name: str) -> list[tuple]:
+    rnd = random.Random(sum(map(ord, name)))
+    cases = []
+    for param in WAVE_PARAMS[name]:
+        for top in (False, True):
+            tag = ", top lift" if top else ""
+            if name == "butterfly_add":
+                cases += [(label + tag, param, w) for label, w in _pair_units(rnd, WAVE, param, top)]
+            elif name == "butterfly_add4":
+                cases += [(label + tag, param, [u for u in w for _ in range(2)]) for label, w in _pair_units(rnd, WAVE // 2, param // 2, top)]
+            else:
+                cases += [(label + tag, param, w) for label, w in _reduce_waves(rnd, top)]
+    return cases
+
+
+def wave_min_distinct(name: str) -> int:
+    """the fewest distinct waves an op's list may hold"""
+    return {"butterfly_add": 200, "butterfly_add4": 170, "butterfly_reduce": 130}[name]
+
+
+def wave_pre(name: str, param: int, wave) -> bool:
+    ok = len(wave) == WAVE and param in WAVE_PARAMS[name] and all(_xyzz_ok(c) and _on_curve(xyzz_point(c)) for c in wave)
+    if name == "butterfly_add4":
+        ok = ok and all(wave[i] == wave[i ^ 1] for i in range(WAVE))
+    return ok
+
+
+def wave_expected(name: str, param: int, wave) -> list:
+    """the group element every lane holds afterwards"""
+    pts = [xyzz_point(c) for c in wave]
+    if name != "butterfly_reduce":
+        return [O.g1_add(pts[i], pts[i ^ param]) for i in range(WAVE)]
+    sums = []
+    for g in range(0, WAVE, param):
+        acc = None
+        for q in pts[g:g + param]:
+            acc = O.g1_add(acc, q)
+        sums += [acc] * param
+    return sums
+
+
+def wave_check(name: str, param: int, wave, out: list) -> None:
+    """out: per lane the four coordinates as integers.  Every lane holds the sum (butterfly_reduce: of its group of `param`
+    lanes, the first lane of a group being the one the kernels store) within the XYZZ invariants, and lanes l and l ^ 1 hold
+    identical words wherever a four-lane step may follow: after butterfly_add (on the two lanes of a pair, whatever the
+    mask), after butterfly_add4, and after butterfly_reduce over more than one lane."""
+    want = wave_expected(name, param, wave)
+    for i in range(WAVE):
+        assert _xyzz_ok(out[i]), f"lane {i}: XYZZ invariants X < 5.1p, Y < 3.2p, ZZ, ZZZ < 1.1p"
+        assert xyzz_point(out[i]) == want[i], f"lane {i}: point"
+    partner = param if name == "butterfly_add" else 1
+    if name != "butterfly_reduce" or param > 1:
+        for i in range(WAVE):
+            assert out[i] == out[i ^ partner], f"lanes {i} and {i ^ partner} hold different words"

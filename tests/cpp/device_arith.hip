@@ -5,11 +5,14 @@
 // chains).  Every entry point takes host arrays in the RAW internal form of its family -- 8 x u32 for Fr (arkworks
 // Montgomery words), 9 x 30-bit limbs for Fr30, 13 x 30-bit limbs for Fq30, 4 x 13 for an XYZZ point, 3 x 13 for a
 // Jacobian one, 2 x 13 for an affine one -- runs one thread per case in 64-thread blocks, and returns the HIP error code.
+// da_wave runs the cross-lane additions of msm_common.hpp (butterfly_add, butterfly_add4, butterfly_reduce) on whole
+// wavefronts of chosen points, one wavefront per block, and returns EVERY lane's result.
 // Tests build operands at the exact limits of each function's contract and check results against Python integers.
 // Not linked into libtyplonk_hip.so.
 #include "../../typlonk_amd/csrc/g1.hpp"
 #include "../../typlonk_amd/csrc/fr30.hpp"
 #include "../../typlonk_amd/csrc/fr_inv.hpp"
+#include "../../typlonk_amd/csrc/msm_common.hpp"
 
 using namespace ty;
 
@@ -221,6 +224,25 @@ __global__ __launch_bounds__(64) void g1_kernel(int op, const uint32_t* a, const
     aux[t] = k;
 }
 
+// ---- wavefront butterflies (msm_common.hpp) ------------------------------------------------------------------------------
+// Lane t of a wavefront loads point t of `in` as raw limbs (no ld_xyzz: lazily reduced operands stay as given) and stores
+// its own result, so that the caller sees what every lane holds after the step, not only the lane a kernel would store.
+enum { WAVE_ADD, WAVE_ADD4, WAVE_REDUCE };
+
+__global__ __launch_bounds__(64) void wave_kernel(int op, int param, const uint32_t* in, uint32_t* out, int32_t* aux) {
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+    G1Xyzz v = ld_xyzz(in + t * G1_W);
+    int32_t k = 0;
+    switch (op) {   // op and param are kernel arguments: the whole wavefront takes the same branch
+        case WAVE_ADD: v = butterfly_add(v, param); break;
+        case WAVE_ADD4: v = butterfly_add4(v, param); break;
+        case WAVE_REDUCE: v = butterfly_reduce(v, (uint32_t)param); break;
+        default: k = -1;
+    }
+    st_xyzz(out + t * G1_W, v);
+    aux[t] = k;
+}
+
 // ---- host side: allocate, copy, launch, synchronise, copy back, free ---------------------------------------------------
 struct DevBufs {
     void* p[8] = {};
@@ -311,6 +333,25 @@ extern "C" int da_g1(int op, const uint32_t* a, const uint32_t* b, const uint32_
     uint32_t* dout = m.zeros<uint32_t>(w);
     int32_t* daux = m.zeros<int32_t>(n);
     if (m.err == hipSuccess) hipLaunchKernelGGL(g1_kernel, grid_of(n), dim3(64), 0, 0, op, da, db, df, dout, daux, n);
+    m.launched();
+    m.out(out, dout, w);
+    m.out(aux, daux, n);
+    return (int)m.err;
+}
+
+// One wavefront per block over n = 64 * waves points of 52 words.  op 0: butterfly_add(v, param), param = the lane mask 1..32;
+// op 1: butterfly_add4(v, param), mask 2..32 (the caller keeps lanes l and l ^ 1 identical); op 2: butterfly_reduce(v, param),
+// param = lanes 1..64.  A param outside those (or not a power of two), or n not a multiple of 64: hipErrorInvalidValue.
+extern "C" int da_wave(int op, int param, const uint32_t* in, uint32_t* out, int32_t* aux, int n) {
+    if (n <= 0) return 0;
+    const int lo = op == WAVE_ADD4 ? 2 : 1, hi = op == WAVE_REDUCE ? 64 : 32;
+    if (n % 64 != 0 || param < lo || param > hi || (param & (param - 1)) != 0) return (int)hipErrorInvalidValue;
+    DevBufs m;
+    const size_t w = (size_t)n * G1_W;
+    const uint32_t* din = m.in(in, w);
+    uint32_t* dout = m.zeros<uint32_t>(w);
+    int32_t* daux = m.zeros<int32_t>(n);
+    if (m.err == hipSuccess) hipLaunchKernelGGL(wave_kernel, dim3((unsigned)(n / 64)), dim3(64), 0, 0, op, param, din, dout, daux);
     m.launched();
     m.out(out, dout, w);
     m.out(aux, daux, n);

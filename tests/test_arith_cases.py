@@ -10,7 +10,7 @@ import arith_cases as C
 from helpers import ROOT
 
 HARNESS = os.path.join(ROOT, "tests", "cpp", "libdevice_arith.so")
-ENTRY_POINTS = ("da_fr", "da_fq30", "da_fr30", "da_g1")
+ENTRY_POINTS = ("da_fr", "da_fq30", "da_fr30", "da_g1", "da_wave")
 
 
 def _exports(path):
@@ -58,6 +58,48 @@ def test_fr30_cases(name):
 @pytest.mark.parametrize("name", list(C.G1_OPS))
 def test_g1_cases(name):
     _check(name, lambda a, b, f: C.g1_pre(name, a, b, f), C.g1_cases(name))
+
+
+@pytest.mark.parametrize("name", list(C.WAVE_OPS))
+def test_wave_cases(name):
+    """whole wavefronts for the butterflies of msm_common.hpp: every lane within the XYZZ invariants and on the curve, the
+    four-lane step's operands identical on lanes l and l ^ 1, and the kinds of wave the checks are about really there"""
+    cases = C.wave_cases(name)
+    n = len({repr((param, wave)) for _, param, wave in cases})
+    assert n >= C.wave_min_distinct(name), f"{name}: only {n} distinct waves"
+    bad = [label for label, param, wave in cases if not C.wave_pre(name, param, wave)]
+    assert not bad, f"{name}: waves {bad[:5]} break the precondition"
+    assert {param for _, param, _ in cases} == set(C.WAVE_PARAMS[name])
+    for param in C.WAVE_PARAMS[name]:
+        mine = [(label, wave) for label, p, wave in cases if p == param]
+        tops = [wave for label, wave in mine if label.endswith("top lift")]
+        assert len(tops) * 2 + (name != "butterfly_reduce") == len(mine)   # (one wave mixes both identity encodings)
+        # the largest lift: X, Y, ZZ, ZZZ of every point within one p of the invariants' limits (the identity: ZZ = 0 or p)
+        assert all(C.X_MAX - c[0] <= C.P and C.Y_MAX - c[1] <= C.P and C.Z_MAX - c[2] <= C.P and C.Z_MAX - c[3] <= C.P
+                   for wave in tops for c in wave if c[2] % C.P)
+        if name == "butterfly_reduce":
+            continue
+        # partner lanes: the same point in two representations, in identical words, opposite, and both identity encodings
+        pm = param
+        kinds = set()
+        for _, wave in mine:
+            pts = [C.xyzz_point(c) for c in wave]
+            for i in range(C.WAVE):
+                a, b = wave[i], wave[i ^ pm]
+                if pts[i] is None and pts[i ^ pm] is None:
+                    kinds.add("identities" if a[2] == b[2] else "identities, two encodings")
+                elif pts[i] is not None and pts[i] == pts[i ^ pm]:
+                    kinds.add("equal words" if a == b else "equal, two representations")
+                elif pts[i] is not None and pts[i ^ pm] == C.O.g1_neg(pts[i]):
+                    kinds.add("opposite")
+        assert kinds == {"identities", "identities, two encodings", "equal words", "equal, two representations", "opposite"}
+        # a wave with exactly one exceptional pair, for each kind
+        for kind in ("equal", "opposite", "identity"):
+            for where in ("first", "last", "middle"):
+                wave = next(w for label, w in mine if label == f"one {kind} pair, {where}")
+                pts = [C.xyzz_point(c) for c in wave]
+                exc = [i for i in range(C.WAVE) if pts[i] is None or pts[i ^ pm] is None or pts[i][0] == pts[i ^ pm][0]]
+                assert len(exc) == (2 if name == "butterfly_add" else 4), (kind, where, exc)
 
 
 def test_fr30_cases_reach_the_limits():

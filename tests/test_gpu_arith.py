@@ -1,5 +1,5 @@
-"""The shipped device arithmetic -- ff.hpp's Fr, fq30.hpp, fr30.hpp, fr_inv.hpp, g1.hpp, compiled for gfx950 exactly as the
-library's units compile them -- on chosen inputs, through the test-only harness tests/cpp/libdevice_arith.so.  Every
+"""The shipped device arithmetic -- ff.hpp's Fr, fq30.hpp, fr30.hpp, fr_inv.hpp, g1.hpp and the wavefront butterflies of
+msm_common.hpp, compiled for gfx950 exactly as the library's units compile them -- on chosen inputs, through the test-only harness tests/cpp/libdevice_arith.so.  Every
 result is checked against Python integers: its residue, its limb form, and the value bound the function's comment
 promises.  Case lists and checks: tests/arith_cases.py (their preconditions are asserted on the CPU too,
 tests/test_arith_cases.py).  tests/test_host.py covers the host branches of the same headers."""
@@ -24,6 +24,8 @@ def lib(built):
     for fn, n in (("da_fr", 6), ("da_fq30", 8), ("da_fr30", 6), ("da_g1", 7)):
         getattr(lib, fn).restype = ctypes.c_int
         getattr(lib, fn).argtypes = [ctypes.c_int] + [U32P] * (n - 3) + [I32P, ctypes.c_int]
+    lib.da_wave.restype = ctypes.c_int
+    lib.da_wave.argtypes = [ctypes.c_int, ctypes.c_int, U32P, U32P, I32P, ctypes.c_int]
     return lib
 
 
@@ -135,6 +137,44 @@ def test_g1(lib, name):
         except AssertionError as e:
             fails.append(f"#{i}: {e}")
     _report(name, fails, n)
+
+
+@pytest.mark.parametrize("name,param", [(name, param) for name in C.WAVE_OPS for param in C.WAVE_PARAMS[name]])
+def test_wave(lib, name, param):
+    """butterfly_add / butterfly_add4 / butterfly_reduce (msm_common.hpp) on whole wavefronts of chosen points, every lane's
+    result read back: the sum as a group element, the XYZZ invariants, ZZ^3 = ZZZ^2, and identical words on the lanes the
+    next four-lane step reads as one operand -- in the formula's path and in every exceptional one (equal points in two
+    representations or in the same words, opposite points, the identity in either encoding on one or both sides; on every
+    pair of a wave, and on one pair of an otherwise ordinary wave)."""
+    cases = [(label, wave) for label, p, wave in C.wave_cases(name) if p == param]
+    bad = [label for label, wave in cases if not C.wave_pre(name, param, wave)]
+    assert not bad, f"{name}: waves {bad[:5]} break the precondition (the case list is wrong, not the kernel)"
+    n = len(cases) * C.WAVE
+    pack = lambda coords: [limb for v in coords for limb in C.limbs(v, 13)]  # noqa: E731
+    a = _arr([pack(c) for _, wave in cases for c in wave], 52)
+    out = np.zeros((n, 52), dtype=np.uint32)
+    aux = np.full(n, -7, dtype=np.int32)
+    rc = lib.da_wave(C.WAVE_OPS[name], param, a.ctypes.data_as(U32P), out.ctypes.data_as(U32P), aux.ctypes.data_as(I32P), n)
+    assert rc == 0, f"HIP error {rc}"
+    assert (aux == 0).all(), "harness did not run every lane"
+    fails = []
+    for k, (label, wave) in enumerate(cases):
+        rows = out[k * C.WAVE:(k + 1) * C.WAVE]
+        try:
+            assert (rows <= C.M30).all(), "limbs not normalised (< 2^30)"
+            C.wave_check(name, param, wave, [tuple(C.val(r[13 * j:13 * j + 13]) for j in range(4)) for r in rows])
+        except AssertionError as e:
+            fails.append(f"{label}: {e}")
+    _report(f"{name}({param})", fails, len(cases))
+
+
+def test_wave_refuses_what_the_butterflies_do_not_take(lib):
+    """a mask or lane count outside the wavefront (or not a power of two) and a partial wavefront never reach the device"""
+    buf = np.zeros((C.WAVE, 52), dtype=np.uint32)
+    aux = np.zeros(C.WAVE, dtype=np.int32)
+    args = (buf.ctypes.data_as(U32P), buf.ctypes.data_as(U32P), aux.ctypes.data_as(I32P))
+    for op, param, n in ((0, 64, 64), (0, 3, 64), (0, 0, 64), (1, 1, 64), (1, 64, 64), (2, 128, 64), (2, 0, 64), (0, 1, 63)):
+        assert lib.da_wave(op, param, *args, n) == 1
 
 
 @pytest.mark.parametrize("name,limit", [("fq30_inv_divsteps", 37), ("fr_inv_divsteps", 25)])

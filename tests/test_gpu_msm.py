@@ -113,6 +113,24 @@ def test_srs_all_equal_points(ctx):
     ctx.srs_free(sid)
 
 
+def test_equal_buckets_in_two_representations_side_by_side(ctx):
+    """Two buckets that sit on partner lanes of the reduction's first butterfly step and hold the SAME point in different
+    XYZZ words: bases (G, G, 2G, 5G) with scalars (d, d, d + 1, d + 2), d odd, in table mode with c = 15 (one shared set of
+    2^14 buckets, 128 rows x 128 columns).  Bucket d - 1 collects G + G (the mixed addition's doubling: ZZ = (2y)^2), bucket d
+    holds 2G as loaded (ZZ = 1), bucket d + 1 holds 5G.  The first step doubles 2G on both lanes, and the four-lane step after
+    it reads the pair as ONE operand (X, ZZ from one lane, Y, ZZZ from the other), so both lanes must have doubled the same
+    words.  d = 129 puts the three buckets at the start of row 1; in row 0 (d < 128) the row sum has weight 0 and only the
+    column sums -- one bucket each here -- carry the result."""
+    pts = [O.G1, O.G1, O.g1_mul(O.G1, 2), O.g1_mul(O.G1, 5)]
+    xy, inf = g1_pack(pts)
+    sid = ctx.srs_load(xy, inf)
+    ctx.srs_precompute(sid, 15)
+    for d in (129, 255, 8191, 16381, 1, 127):
+        out, oinf = ctx.msm(sid, fr_pack([d, d, d + 1, d + 2]))
+        assert g1_unpack_one(out, oinf) == O.g1_mul(O.G1, 2 * d + 2 * (d + 1) + 5 * (d + 2)), d
+    ctx.srs_free(sid)
+
+
 def test_scalar_mul_homomorphism(ctx):
     """kzg/src/lib.rs:160-171: commit(9 p) == 9 commit(p)."""
     sid, pts = load_srs(ctx, 2, 103)

@@ -4,6 +4,7 @@
   tests/cpp/hooks/libtyplonk_hip.so  the same library with the fault-injection hook (-DTYPLONK_TEST_HOOKS, tests only) -- hipcc
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
+  tests/cpp/libdevice_reduce.so   device harness over msm_reduce.hip, the bucket reduction (tests/test_gpu_reduce.py) -- hipcc
   tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
@@ -143,6 +144,18 @@ def build_device_arith(force: bool = False) -> str:
     return out
 
 
+def build_device_reduce(force: bool = False) -> str:
+    """tests/cpp/libdevice_reduce.so: csrc/harness/device_reduce.hip, msm_reduce.hip compiled as a unit behind an entry point that runs its launchers on a
+    caller-made bucket array (tests/test_gpu_reduce.py).  Test-only and not linked into the shipped library; the flags are
+    build_hip()'s."""
+    src = os.path.join(CSRC, "harness", "device_reduce.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_reduce.so")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "msm_reduce.hip")]
+    if force or _stale(out, [src] + deps):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
 def build_fq30_pair_host(force: bool = False) -> str:
     """tests/cpp/libfq30_pair_host.so: fq30_mul_pair / fq30_sqr_pair / fq30_mul2_add as the host compiles them"""
     src = os.path.join(ROOT, "tests", "cpp", "fq30_pair_host.cpp")
@@ -220,6 +233,7 @@ def build_all(force: bool = False) -> None:
     build_hip_test_hooks(force)
     build_host_shim(force)
     build_device_arith(force)
+    build_device_reduce(force)
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
     build_perm_pairs_host(force)

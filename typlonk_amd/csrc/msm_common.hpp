@@ -101,6 +101,8 @@ __device__ __forceinline__ Fq30 fq_sel(bool c, const Fq30& a, const Fq30& b) {
 //   step 4  lower: R * (Q - X3) and ZZ12 * PP, upper: S1 * PPP and ZZZ12 * PPP        -> exchange
 // Bounds are those of g1_add (g1.hpp).  An identity operand selects the other point at the end; equal points are
 // doubled and opposite points give the identity there too (wave-uniform branch, taken only when some pair needs it).
+// Both lanes of a pair end with the SAME WORDS, in every path: the four-lane step below reads the lanes l and l ^ 1 as one
+// operand, X and ZZ from one and Y and ZZZ from the other.
 __device__ __forceinline__ G1Xyzz butterfly_add(const G1Xyzz& v, int mask) {
     const bool lower = (threadIdx.x & (uint32_t)mask) == 0;
     const bool v_inf = v.is_inf();
@@ -143,11 +145,13 @@ __device__ __forceinline__ G1Xyzz butterfly_add(const G1Xyzz& v, int mask) {
     out.zz = fq_sel(lower, z_own, z_oth);
     out.zzz = fq_sel(lower, z_oth, z_own);
     // An identity operand selects the other point (the formulas above then ran on zeros, harmlessly); equal points
-    // double, opposite points cancel -- both lanes of such a pair hold the same point, so each settles it alone.
+    // double, opposite points cancel.  Two equal points may come in two representations ((X, Y, ZZ, ZZZ) and
+    // (l^2 X, l^3 Y, l^2 ZZ, l^3 ZZZ)), and two identities in two encodings (ZZ = 0 or p), so a lane does not settle
+    // the pair from its own copy: both double the LOWER lane's copy and both write the same identity.
     if (__any(v_inf || o_inf || exc)) {
         const G1Xyzz o = shfl_xor_point(v, mask);
-        if (exc) out = same ? g1_dbl(v) : G1Xyzz::inf();
-        else if (v_inf) out = o;
+        if (exc) out = same ? g1_dbl(lower ? v : o) : G1Xyzz::inf();
+        else if (v_inf) out = o_inf ? G1Xyzz::inf() : o;
         else if (o_inf) out = v;
     }
     return out;
@@ -166,8 +170,10 @@ __device__ __forceinline__ G1Xyzz butterfly_add(const G1Xyzz& v, int mask) {
 //   round 3   q0: Q = U1 PP        q1: --                q2: PPP = P PP       q3: --                   (1 exchange: PP <-> ZZ12)
 //   round 4   q0: ZZ3 = ZZ12 PP    q1: R (Q - X3)        q2: ZZZ3 = ZZZ12 PPP q3: S1 PPP               (3 exchanges)
 // and a gather of X3, Y3 = R(Q - X3) - S1 PPP, ZZ3, ZZZ3 onto all four lanes (5 exchanges).  Bounds: those of butterfly_add.
-// Identity operands, equal and opposite points are settled at the end exactly as there (every lane of a side holds the
-// whole point, so each lane settles its own copy).  Precondition: v is identical on lanes l and l ^ 1.
+// Identity operands, equal and opposite points are settled at the end as there: every lane of a side holds the whole
+// point in its side's words, so the lanes l and l ^ 1 -- one side -- settle it alike and end with the same words (the two
+// SIDES may then hold two representations of the sum, which is what the next step's precondition allows).
+// Precondition: v is identical, word for word, on lanes l and l ^ 1 -- butterfly_add and this function both leave it so.
 __device__ __forceinline__ Fq30 shfl_fq(const Fq30& a, int src_lane) {
     Fq30 r;
 #pragma unroll
