@@ -190,6 +190,30 @@ def test_srs_generate_matches_reference_faithful_generator(ctx):
     ctx.srs_free(sid)
 
 
+@pytest.mark.parametrize("m", [1 << 20, (1 << 20) - 1])
+def test_first_msm_of_a_cold_context_over_host_scalars(built, m):
+    """A fresh context whose FIRST MSM takes host scalars of 2^20 terms, plain SRS: the smallest length with the short first
+    chunk (2^18 terms, then two of 3 * 2^17), so the later chunks need larger sort buffers than the first -- which were once
+    regrown while the first chunk was still being accumulated from them; 2^20 - 1 terms take two equal chunks.  The workspace
+    is sized for the whole call before anything is queued (msm_plan.hpp); the commitment is [p(2)]G by the C oracle."""
+    import typlonk_amd
+    from oracle import coracle as CO
+
+    s_limbs = np.array(O.fr_to_mont_limbs(2), dtype=np.uint64)
+    rng = np.random.default_rng(m)
+    sc = rng.integers(0, 1 << 63, size=(m, 4), dtype=np.uint64) * 2 + rng.integers(0, 2, size=(m, 4), dtype=np.uint64)
+    sc[:, 3] &= np.uint64(0x3FFFFFFFFFFFFFFF)
+    exp, einf = CO.g1_mul_generator(CO.poly_eval(sc, s_limbs))
+    cold = typlonk_amd.Context(0)
+    try:
+        sid = cold.srs_generate(s_limbs, 1 << 20)
+        out, inf = cold.msm(sid, sc)
+        assert (out == exp).all() and inf == einf
+        cold.srs_free(sid)
+    finally:
+        cold.close()
+
+
 @pytest.mark.parametrize("log_m,delta", [(16, 0), (16, -1), (20, 0), (20, -3), (20, -1), (22, 0), (22, -3)])
 def test_commit_identity_large(ctx, log_m, delta):
     """BASELINE configs 2-3 sizes (and the n-1 / n-3 lengths prove() uses): commit(p) == [p(s)]G,

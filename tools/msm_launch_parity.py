@@ -1,0 +1,99 @@
+"""Launch parity of two builds of the library (profiles/r21_msm_plan_launch_parity.txt): the same MSMs under
+`rocprofv3 --kernel-trace` with each build, then the ordered kernel name, grid, workgroup size and LDS bytes compared per stream.
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR_A -- python3 tools/msm_launch_parity.py run     (TYPLONK_LIB_PATH: build A)
+    rocprofv3 --kernel-trace --output-format csv -d DIR_B -- python3 tools/msm_launch_parity.py run
+    python tools/msm_launch_parity.py compare DIR_A DIR_B [OUT]
+
+run: one MSM at 2^14 terms over a plain SRS, 2^17 with c = 17 tables, 2^20 with c = 20 tables from device and from host
+scalars, and 2^21 with c = 20 tables queued in a batch of three."""
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def run():
+    import numpy as np
+    import typlonk_amd
+
+    ctx = typlonk_amd.Context(0)
+    two = np.array([2, 0, 0, 0], dtype=np.uint64)   # any secret: the launches do not depend on it
+    rng = np.random.default_rng(21)
+    for log_m, window, how in ((14, 0, "dev"), (17, 17, "dev"), (20, 20, "dev host"), (21, 20, "batch")):
+        m = 1 << log_m
+        sc = rng.integers(0, 1 << 62, size=(m, 4), dtype=np.uint64)
+        sid = ctx.srs_generate(two, m)
+        if window:
+            ctx.srs_precompute(sid, window)
+        buf = ctx.alloc(m)
+        buf.upload(sc)
+        if "dev" in how:
+            ctx.msm_devptr(sid, buf.devptr, m)
+        if "host" in how:
+            ctx.msm(sid, sc)
+        if "batch" in how:
+            ctx.msm_batch_devptr(sid, [buf.devptr] * 3, [m, m, m])
+        buf.free()
+        ctx.srs_free(sid)
+        print(f"PARITY_RUN 2^{log_m} window {window} {how}: done", flush=True)
+    ctx.close()
+
+
+def launches(directory):
+    """{stream (numbered by first appearance): [(kernel, grid, workgroup, lds)] in dispatch order}, and the column that told streams apart"""
+    files = sorted(glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True))
+    if not files:
+        raise SystemExit(f"no *kernel_trace.csv under {directory}")
+    rows = []
+    for f in files:
+        with open(f, newline="") as fh:
+            rows += list(csv.DictReader(fh))
+    key = "Stream_Id" if "Stream_Id" in rows[0] else "Queue_Id"
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
+    streams, order = {}, {}
+    for r in rows:
+        sid = order.setdefault(r[key], len(order))
+        streams.setdefault(sid, []).append((r["Kernel_Name"].split("(")[0],
+                                            tuple(int(r["Grid_Size_" + a]) for a in "XYZ"),
+                                            tuple(int(r["Workgroup_Size_" + a]) for a in "XYZ"),
+                                            int(r["LDS_Block_Size"])))
+    return streams, key, len(rows)
+
+
+def compare(dir_a, dir_b, out=None):
+    a, key_a, na = launches(dir_a)
+    b, key_b, nb = launches(dir_b)
+    lines = [f"A: {na} kernel launches on {len(a)} streams ({key_a}); B: {nb} on {len(b)} ({key_b})"]
+    same = key_a == key_b and sorted(a) == sorted(b)
+    for s in sorted(set(a) | set(b)):
+        la, lb = a.get(s, []), b.get(s, [])
+        if la == lb:
+            lines.append(f"stream {s}: {len(la)} launches, identical")
+            continue
+        same = False
+        lines.append(f"stream {s}: DIFFERENT ({len(la)} against {len(lb)} launches)")
+        for i in range(max(len(la), len(lb))):
+            x, y = (la[i] if i < len(la) else None), (lb[i] if i < len(lb) else None)
+            if x != y:
+                lines.append(f"  launch {i}: A {x}\n  {' ' * len(str(i))}         B {y}")
+    lines.append("VERDICT: the ordered (kernel, grid, workgroup size, LDS bytes) lists are identical per stream" if same
+                 else "VERDICT: the launch lists differ")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 2 and sys.argv[1] == "run":
+        run()
+    elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None))
+    else:
+        sys.exit(__doc__)

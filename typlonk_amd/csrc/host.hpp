@@ -1,7 +1,8 @@
 // Shared state of the host driver of libtyplonk_hip.so (implementation of include/typlonk.h for gfx950).
 //   ctx.hip       context, workspaces, profiling events, device vectors
 //   ntt_host.hip  NTT planning (tables, pass decomposition) + typlonk_ntt_*
-//   msm_host.hip  MSM staging (sort / accumulate / reduce launches, lanes of a batch, host finish) + SRS + typlonk_msm_*
+//   msm_host.hip  MSM staging: plan (msm_plan.hpp: every decision, no device needed), size the workspace, queue the sort /
+//                 accumulate / reduce launches; lanes of a batch, host finish + SRS + typlonk_msm_*
 //   comm.hip      RCCL exchange behind the C ABI
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove; the steps it shares with prove_batch.hip
 //                 (declared below: coset_g, quotient_domain, round3_openings, lin_*); transcripts: proof_script.hpp
@@ -107,8 +108,6 @@ struct SortBufs {
                 &heavy, &tasks, &hpart};
     }
 };
-constexpr int MSM_MAX_CHUNKS = 8;
-constexpr size_t MSM_CHAIN_MIN_TERMS = (size_t)1 << 17;   // typlonk_ctx::msm_chain
 constexpr size_t MSM_FOUR_LANES_BELOW = (size_t)1 << 17;  // typlonk_ctx::msm_inflight
 
 struct MsmWs {
@@ -224,8 +223,6 @@ struct typlonk_ctx {
 
 namespace tyh {
 
-// smallest heavy-bucket threshold (entries one accumulation thread may sum; msm_enqueue)
-constexpr uint32_t MSM_CAP_MIN = 32;
 // full (one-multiplication) twiddle / coset tables are built up to this many entries (512 MB); above, two-level tables
 constexpr uint32_t NTT_FULL_MAX_LOG = 24;
 // default policy (TYPLONK_NTT_FR30 = 1): forward transforms take the 9 x 30-bit kernel up to this size, inverse ones always

@@ -206,7 +206,6 @@ __global__ __launch_bounds__(RC2_THREADS) void msm_rc2_planes_kernel(const uint3
     if (threadIdx.x == 0) st_xyzz(out, blockIdx.x, v);
 }
 
-bool msm_rc2_ok(const RcShape& sh) { return sh.cl >= 6 && sh.ch >= 6; }
 // log2 of the wavefronts in the first launch: one per SIMD (2^11 and 2^12 measured on 2^19 buckets do not beat the
 // four-launch form there, profiles/r06_ab_first_chunk_and_rc2.txt)
 constexpr uint32_t RC2_LOG_WAVES = 10;

@@ -4,6 +4,7 @@
 // See msm_common.hpp for the overall MSM structure.
 #include "launch.hpp"
 #include <algorithm>
+#include <atomic>
 #include "msm_common.hpp"
 
 namespace ty {
@@ -157,44 +158,13 @@ __global__ __launch_bounds__(256) void scan_finish_kernel(const uint32_t* in, ui
 
 // ---- segmented counting sort (no global atomics) ------------------------------------------------------
 // Bucket id = (window j, bucket-in-window b).  Level 1 partitions the W*m entries into
-// nseg = W << hb segments keyed by (j, b >> lb); level 2 sorts every segment by the low lb <= 8 bits
+// nseg segments (2^hb per bucket set) keyed by (j, b >> lb); level 2 sorts every segment by the low lb <= 8 bits
 // inside one workgroup.  Level 1 is the classic radix-sort scheme: every workgroup histograms its
 // chunk of MSM_CHUNK scalars in LDS and publishes the column blk_hist[seg * nblk + blk]; one
 // exclusive scan over that matrix gives each (segment, workgroup) its private output range, so
 // the scatter needs only LDS atomics (for the rank inside the workgroup).
 // Level-1 entry: idx (23 bits) | sign << 23 | (b & (2^lb - 1)) << 24     (m <= 2^23)
-// scalars per workgroup: 2048 (8 per thread) up to 2^20 terms, growing with m beyond that so the
-// workgroup x segment matrix (nblk * nseg counters) stays bounded instead of growing like m^2
-// threads per workgroup of the level-1 passes (512 and 1024 were measured: no gain)
-inline uint32_t msm_seg1_threads() { return 256; }
-// scalars per thread of the level-1 passes: 8 from 2^20 terms on; a short MSM (an index shard) gets fewer, so that its
-// level-1 launches still have 512 workgroups -- at 2^17 terms 8 per thread is 64 workgroups and 34 + 39 us for the
-// histogram and the scatter, 1 per thread 512 workgroups (profiles/r03_shard_timeline.txt)
-inline uint32_t msm_seg1_per_thread(uint64_t m) {
-    // (2^19-term chunks keep 8: their scatter, 4096 segments wide, wants long runs per workgroup and segment)
-    return m <= (1u << 17) ? 1u : (m <= (1u << 18) ? 2u : 8u);
-}
-inline uint32_t msm_chunk_for(uint64_t m) {
-    uint32_t chunk = msm_seg1_per_thread(m) * msm_seg1_threads();
-    while (((uint64_t)chunk << 9) < m) chunk <<= 1;  // at most 512 workgroups
-    return chunk;
-}
-
-struct MsmShape {
-    uint32_t c, W, top_v, hb, lb, nseg, nblk, chunk;
-    // level-1 entry layout: [i : ibits][j : jbits][sign : 1][low bucket bits : lb]
-    uint32_t ibits, jbits;
-    // fixed-base table mode (tlen != 0): base (j, i) lives at gather index j * tlen + i and all windows
-    // share one bucket set (nsets = 1)
-    uint32_t tlen, nsets;
-    // centred scalars: k > (r - 1)/2 is replaced by r - k with every digit's sign flipped, so |k| < 2^254 and
-    // c = 17 needs 15 windows instead of 16, c = 15 17 instead of 18 (launch.hpp, msm_windows)
-    uint32_t centred;
-    // > 0: the kernels of this sort raise their wavefronts' issue priority (s_setprio).  Set for a sort that runs BESIDE an
-    // accumulation (an overlapped chunk, a queued MSM): its few, short wavefronts then get the issue slots they ask for
-    // instead of the ones two accumulation wavefronts per SIMD leave over.
-    uint32_t prio;
-};
+// (MsmShape, the scalars per workgroup and thread of level 1: msm_plan.hpp)
 __device__ __forceinline__ void msm_sort_prio(const MsmShape& sh) {
     if (sh.prio) __builtin_amdgcn_s_setprio(2);
 }
@@ -555,16 +525,8 @@ __global__ __launch_bounds__(512) void msm_seg_scatter_staged_kernel(const Fr* s
 //                         256-bin histogram for itself and claims its run inside each bin from a global cursor).  The claim's
 //                         round trip to the L2 hides under the placement loop.
 // 256, 512 or 1024 threads: all of them walk the segment, the first 256 own the 2^lb <= 256 buckets.
-// Schedule counters of the segmented sort.  Words [0, 516) keep the layout of the atomic sort's hist514 ([512] heavy buckets,
-// [513] tasks -- msm_heavy_kernel reads those); the size histogram and the claim cursors of the SEGMENTED sort are kept in
-// MSM_SCHED_REPLICAS copies behind them, replica r = segment mod R at word 1024 + 512 r (256 bins + 256 cursors, a KiB apart).
-// Why: ~25 size bins are hot, adjacent words of ONE cache line, and every one of the 2048-4096 level-2 workgroups adds
-// to each of them -- 51 K atomics on one line, which the L2 retires one per clock: ~24 us per launch, the whole run time of
-// order_fused_kernel in rounds 1-5 and most of msm_seg_count / msm_seg_place.  Sixteen lines take them sixteen at a time.
+// (the schedule counters hist514 / ohist, MSM_SCHED_WORDS of them: msm_plan.hpp)
 constexpr uint32_t MSM_PLACE_STAGE = 5120;   // entries of a segment msm_seg_place_kernel assembles in the LDS (20 KiB; mean 3328)
-constexpr uint32_t MSM_SCHED_REPLICAS = 16;
-constexpr uint32_t MSM_SCHED_WORDS = 1024 + 512 * MSM_SCHED_REPLICAS;
-uint32_t msm_sched_words() { return MSM_SCHED_WORDS; }
 
 // inclusive scan over the values of threads 0..255 (four wavefronts): shuffles inside a wavefront, one LDS hand-over
 // between them -- two barriers where the Hillis-Steele form over LDS takes sixteen.  Every thread of the workgroup calls it.
@@ -835,8 +797,6 @@ void launch_exclusive_scan(const uint32_t* in, uint64_t n, uint32_t* block_sums,
     hipLaunchKernelGGL(scan_finish_kernel, dim3(nblk), dim3(256), 0, s, in, n, block_sums, out, out2);
 }
 
-uint32_t msm_segsort_blocks(uint64_t m) { return (uint32_t)((m + msm_chunk_for(m) - 1) / msm_chunk_for(m)); }
-
 // LDS of the staged scatter: three arrays of nseg words + the staging area; it is taken when that fits the 160 KiB of a CU
 // (table mode c = 20: 2048 scalars x 13 windows = 104 KiB + 24-48 KiB) and the fused row-prefix form applies
 static size_t msm_staged_lds(const MsmShape& sh) {
@@ -844,85 +804,67 @@ static size_t msm_staged_lds(const MsmShape& sh) {
 }
 template <uint32_t C>
 static bool msm_staged_raise_lds() {
-    static int state[64] = {};   // per device ordinal: 0 = not tried, 1 = raised, -1 = refused
+    static std::atomic<int> state[64];   // per device ordinal: 0 = not tried, 1 = raised, -1 = refused (contexts on other threads ask too)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (state[dev] == 0)
-        state[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(msm_seg_scatter_staged_kernel<C>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 1 : -1;
-    if (state[dev] < 0) (void)hipGetLastError();
-    return state[dev] > 0;
+    int st = state[dev].load(std::memory_order_acquire);
+    if (st == 0) {   // two threads may both ask: the attribute is idempotent and both store the same answer
+        st = hipFuncSetAttribute(reinterpret_cast<const void*>(msm_seg_scatter_staged_kernel<C>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 1 : -1;
+        if (st < 0) (void)hipGetLastError();
+        state[dev].store(st, std::memory_order_release);
+    }
+    return st > 0;
 }
 
 template <uint32_t C>
-static void launch_msm_segsort_c(const Fr* scalars, uint64_t m, const MsmShape& sh, uint32_t* blk_hist, uint32_t* blk_base,
-                                 uint32_t* scan_scratch, uint32_t* blk_cnt, uint32_t* seg_start, uint32_t* entries,
-                                 uint32_t* counts, uint32_t* offsets, uint32_t* sorted, uint32_t cap, uint32_t* hist514,
-                                 uint32_t* heavy, uint32_t* tasks, uint32_t* order, int staged_mode, hipStream_t s) {
+static void launch_msm_segsort_c(const Fr* scalars, uint64_t m, const MsmShape& sh, const MsmSortPtrs& p, uint32_t cap, int staged_mode,
+                                 hipStream_t s) {
     const uint64_t nmat = (uint64_t)sh.nseg * sh.nblk;
     const uint32_t nt1 = msm_seg1_threads();
     // threads of the staged scatter and of the histogram beside it: 256 (one wavefront per SIMD) for a sort beside an
-    // accumulation, else 512 where the chunk divides (msm_enqueue)
+    // accumulation, else 512 where the chunk divides (msm_plan.hpp, sh.prio)
     const uint32_t nts = (!sh.prio && sh.chunk % 512 == 0) ? 512u : 256u;
     // the fused row-prefix form scans the segment totals in LDS next to the scatter's cursors (nseg + nt1 words); wider
     // segment sets take the three-launch scan of the whole workgroup x segment matrix
     const bool fused = sh.nseg <= 8192;
-    uint32_t* seg_tot = fused ? scan_scratch : nullptr;
+    uint32_t* seg_tot = fused ? p.scan_scratch : nullptr;
     const size_t lds_staged = msm_staged_lds(sh);
-    const bool staged = staged_mode != 0 && fused && blk_cnt && lds_staged <= 160 * 1024 &&
+    const bool staged = staged_mode != 0 && fused && p.blk_cnt && lds_staged <= 160 * 1024 &&
                         (lds_staged <= 64 * 1024 || msm_staged_raise_lds<C>());
     hipLaunchKernelGGL(msm_seg_hist_kernel<C>, dim3(sh.nblk), dim3(staged ? nts : nt1), sh.nseg * sizeof(uint32_t), s, scalars, m, sh,
-                       blk_hist, staged ? blk_cnt : (uint32_t*)nullptr);
+                       p.blk_hist, staged ? p.blk_cnt : (uint32_t*)nullptr);
     if (fused)
-        hipLaunchKernelGGL(msm_seg_prefix_kernel, dim3(sh.nseg), dim3(256), 0, s, blk_hist, sh.nblk, blk_base, seg_tot, hist514,
+        hipLaunchKernelGGL(msm_seg_prefix_kernel, dim3(sh.nseg), dim3(256), 0, s, p.blk_hist, sh.nblk, p.blk_base, seg_tot, p.hist514,
                            MSM_SCHED_WORDS, sh.prio);
     else
-        launch_exclusive_scan(blk_hist, nmat, scan_scratch, blk_base, blk_hist /* second copy unused */, hist514, MSM_SCHED_WORDS, s);
+        launch_exclusive_scan(p.blk_hist, nmat, p.scan_scratch, p.blk_base, p.blk_hist /* second copy unused */, p.hist514,
+                              MSM_SCHED_WORDS, s);
     if (staged)
-        hipLaunchKernelGGL(msm_seg_scatter_staged_kernel<C>, dim3(sh.nblk), dim3(nts), lds_staged, s, scalars, m, sh, blk_base, seg_tot,
-                           blk_cnt, seg_start, entries);
+        hipLaunchKernelGGL(msm_seg_scatter_staged_kernel<C>, dim3(sh.nblk), dim3(nts), lds_staged, s, scalars, m, sh, p.blk_base, seg_tot,
+                           p.blk_cnt, p.seg_start, p.entries);
     else
         hipLaunchKernelGGL(msm_seg_scatter_kernel<C>, dim3(sh.nblk), dim3(nt1), (fused ? sh.nseg + nt1 : sh.nseg) * sizeof(uint32_t),
-                           s, scalars, m, sh, blk_base, seg_tot, seg_start, entries);
+                           s, scalars, m, sh, p.blk_base, seg_tot, p.seg_start, p.entries);
     // long segments (short MSMs with few of them) get more threads per segment
     const uint64_t seg_len = (uint64_t)sh.W * m / sh.nseg;
     const uint32_t nt2 = seg_len >= 4096 ? 1024u : (seg_len >= 1536 ? 512u : 256u);
-    hipLaunchKernelGGL(msm_seg_count_kernel, dim3(sh.nseg), dim3(nt2), 0, s, entries, blk_base, seg_tot, sh, (uint32_t)nmat,
-                       counts, offsets, seg_start, cap, hist514, heavy, tasks);
-    hipLaunchKernelGGL(msm_seg_place_kernel, dim3(sh.nseg), dim3(nt2), 0, s, entries, seg_start, sh, counts, offsets, sorted,
-                       hist514, order);
+    hipLaunchKernelGGL(msm_seg_count_kernel, dim3(sh.nseg), dim3(nt2), 0, s, p.entries, p.blk_base, seg_tot, sh, (uint32_t)nmat,
+                       p.counts, p.offsets, p.seg_start, cap, p.hist514, p.heavy, p.tasks);
+    hipLaunchKernelGGL(msm_seg_place_kernel, dim3(sh.nseg), dim3(nt2), 0, s, p.entries, p.seg_start, sh, p.counts, p.offsets, p.sorted,
+                       p.hist514, p.order);
 }
 
-// The whole bucket sort of one chunk of terms, bucket schedule (order[]) included.  staged_mode: 0 = the direct level-1
-// scatter everywhere (TYPLONK_MSM_SCATTER=direct, the A/B reference), else the LDS-staged one where it fits.
-void launch_msm_segsort(const Fr* scalars, uint64_t m, uint32_t c, uint32_t W, uint32_t top_v, uint32_t hb,
-                        uint32_t ibits, uint32_t tlen, uint32_t nsets, uint32_t* blk_hist, uint32_t* blk_base,
-                        uint32_t* scan_scratch, uint32_t* blk_cnt, uint32_t* seg_start, uint32_t* entries, uint32_t* counts,
-                        uint32_t* offsets, uint32_t* sorted, uint32_t cap, uint32_t* hist514, uint32_t* heavy, uint32_t* tasks,
-                        uint32_t* order, bool centred, int staged_mode, bool beside_accum, hipStream_t s) {
-    MsmShape sh;
-    sh.centred = centred ? 1u : 0u;
-    sh.prio = beside_accum ? 1u : 0u;
-    sh.c = c;
-    sh.W = W;
-    sh.top_v = top_v;
-    sh.hb = hb;
-    sh.lb = c - 1 - hb;
-    sh.ibits = ibits;
-    sh.jbits = tlen ? (W > 16 ? 5 : 4) : 0;
-    sh.tlen = tlen;
-    sh.nsets = nsets;
-    sh.nseg = (tlen ? nsets : W) << hb;
-    sh.chunk = msm_chunk_for(m);
-    sh.nblk = (uint32_t)((m + sh.chunk - 1) / sh.chunk);
-#define TY_SEGSORT(C) launch_msm_segsort_c<C>(scalars, m, sh, blk_hist, blk_base, scan_scratch, blk_cnt, seg_start, entries, counts, \
-                                              offsets, sorted, cap, hist514, heavy, tasks, order, staged_mode, s)
+// The whole bucket sort of one chunk of terms, bucket schedule (order[]) included, in the shape the plan gave it.
+// staged_mode: 0 = the direct level-1 scatter everywhere (TYPLONK_MSM_SCATTER=direct, the A/B reference), else the LDS-staged
+// one where it fits.
+void launch_msm_segsort(const Fr* scalars, uint64_t m, const MsmShape& sh, const MsmSortPtrs& p, uint32_t cap, int staged_mode,
+                        hipStream_t s) {
     // the table windows get the constant-width digit extraction; every other width the run-time form
-    if (c == 20) TY_SEGSORT(20);
-    else if (c == 17) TY_SEGSORT(17);
-    else if (c == 15) TY_SEGSORT(15);
-    else TY_SEGSORT(0);
-#undef TY_SEGSORT
+    if (sh.c == 20) launch_msm_segsort_c<20>(scalars, m, sh, p, cap, staged_mode, s);
+    else if (sh.c == 17) launch_msm_segsort_c<17>(scalars, m, sh, p, cap, staged_mode, s);
+    else if (sh.c == 15) launch_msm_segsort_c<15>(scalars, m, sh, p, cap, staged_mode, s);
+    else launch_msm_segsort_c<0>(scalars, m, sh, p, cap, staged_mode, s);
 }
 
 // bucket schedule after the ATOMIC counting sort (the segmented sort builds it itself, msm_seg_place_kernel)
