@@ -170,6 +170,66 @@ def test_both_butterfly_kernels_give_the_c_oracles_words(built, mode, monkeypatc
         c2.close()
 
 
+def test_both_call_orders_meet_one_table_cache(built, monkeypatch):
+    """One context's tables are shared by whoever asks first.  The domain's forward two-level twiddles "tw:f:<log_n>" are looked
+    up by the transforms AND, through domain_twiddles, by the circuit compiler, the grand product and the quotient's domain; a
+    30-bit run looks up the 8 x 32 kernel's small tables beside its own.  Two fresh contexts meet the cache in opposite orders:
+    TYPLONK_NTT_FR30 = 0, a circuit compiled at 2^11 first (the accessor builds the pair), then the four transforms at 2^11
+    (the smallest two-pass size), then at 2^17 (the smallest three-pass size), then a proof; TYPLONK_NTT_FR30 = 2, the
+    transforms first, 2^17 before 2^11, then the compilation, its twin loaded through inverse transforms, and the proofs.
+    Every transform equals the C oracle word for word; the three proofs are equal in every field."""
+    import typlonk_amd
+    import witness_check_ref as W
+    from oracle import coracle as CO
+    from oracle import plonk_oracle as PO
+    from test_gpu_circuit_compile import _compile, _sel_words
+    from test_gpu_prove_batch import same
+    from test_gpu_prove_batch_compact import _free, _upload
+    from test_gpu_witness_check import Loaded, _limbs
+
+    g = np.array(O.fr_to_mont_limbs(7), dtype=np.uint64)
+    forms = ((False, None), (True, None), (False, g), (True, g))
+    xs = {log_n: rand_limbs(4200 + log_n, 1 << log_n) for log_n in (11, 17)}
+    want = {(log_n, i): CO.ntt(xs[log_n], log_n, inverse=inv, coset=cs) for log_n in xs for i, (inv, cs) in enumerate(forms)}
+    n, cols, q, perm = PO.squaring_chain(11)
+    sel, words = _sel_words(q), [W.mont_words(col) for col in cols]
+    proofs = []
+
+    def transforms(c2, sizes):
+        for log_n in sizes:
+            for i, (inv, cs) in enumerate(forms):
+                assert (c2.ntt(xs[log_n], log_n, inverse=inv, coset=cs) == want[log_n, i]).all(), (sizes, log_n, i)
+
+    def prove(c2, cids):
+        sid = c2.srs_generate(_limbs(2), n + 3)
+        bufs, pibs = _upload(c2, n, [(words, [])])
+        try:
+            proofs.extend(c2.prove_native(sid, cid, bufs[0], None, cosets) for cid in cids)
+        finally:
+            _free(bufs, pibs)
+            c2.srs_free(sid)
+
+    cosets = [_limbs(k) for k in PO.COSETS]
+    monkeypatch.setenv("TYPLONK_NTT_FR30", "0")
+    c2 = typlonk_amd.Context(0)
+    try:
+        cid = _compile(c2, 11, sel, perm, cosets)     # domain_twiddles before any transform of the context
+        transforms(c2, (11, 17))
+        prove(c2, [cid])
+    finally:
+        c2.close()
+    monkeypatch.setenv("TYPLONK_NTT_FR30", "2")
+    c2 = typlonk_amd.Context(0)
+    try:
+        transforms(c2, (17, 11))
+        cid = _compile(c2, 11, sel, perm, cosets)     # ... and behind the transforms that made the pair on their way
+        twin = Loaded(c2, 11, sel, perm)
+        prove(c2, [cid, twin.cid])
+    finally:
+        c2.close()
+    assert len(proofs) == 3 and same(proofs[0], proofs[1]) and same(proofs[1], proofs[2])
+
+
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_batched_transforms_equal_single_calls_in_every_kernel_mode(built, mode, monkeypatch):
     """typlonk_ntt_fr_batch_devptr: `count` vectors of one size / direction / coset, every pass ONE launch carrying count x

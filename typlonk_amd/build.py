@@ -9,6 +9,7 @@
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
   tests/cpp/msm_plan_host         host build of msm_plan, every decision of an MSM, a program of its own (tests/test_msm_plan_host.py) -- g++
+  tests/cpp/ntt_plan_host         host build of ntt_plan, every decision of a batch of NTTs, a program of its own (tests/test_ntt_plan_host.py) -- g++
   tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk,wire,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
@@ -197,6 +198,16 @@ def build_msm_plan_host(force: bool = False) -> str:
     return out
 
 
+def build_ntt_plan_host(force: bool = False) -> str:
+    """tests/cpp/ntt_plan_host: ntt_plan (csrc/ntt_plan.hpp) as the host compiles it, printing the plan of each case it reads"""
+    src = os.path.join(ROOT, "tests", "cpp", "ntt_plan_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "ntt_plan_host")
+    deps = [src, os.path.join(CSRC, "ff.hpp"), os.path.join(CSRC, "fr30.hpp"), os.path.join(CSRC, "ntt_args.hpp"), os.path.join(CSRC, "ntt_plan.hpp")]
+    if force or _stale(out, deps):
+        _run(["g++", "-O2", "-std=c++17", src, "-o", out])
+    return out
+
+
 def build_device_pair(force: bool = False) -> str:
     """tests/cpp/libdevice_pair.so: the same functions' device code (the interleaved chains of fq30_pair.hpp) behind an
     element-wise test kernel.  Test-only; the flags are build_hip()'s."""
@@ -248,10 +259,12 @@ def build_all(force: bool = False) -> None:
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
     build_perm_pairs_host(force)
-    # the tests/ of a commit before msm_plan.hpp, run against this library to compare the two, has neither this program's
-    # source nor a test of it
+    # the tests/ of a commit before msm_plan.hpp or ntt_plan.hpp, run against this library to compare the two, has neither
+    # these programs' sources nor tests of them
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "msm_plan_host.cpp")):
         build_msm_plan_host(force)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "ntt_plan_host.cpp")):
+        build_ntt_plan_host(force)
     build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)

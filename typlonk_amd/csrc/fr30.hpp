@@ -32,7 +32,7 @@ struct Fr30 {
 };
 constexpr uint32_t FR30_MASK = 0x3fffffffu;
 // the most butterfly stages one pass may run on this form: the value bounds below (and fr30_reduce_lazy's x_8 < 2^29) are
-// derived for k <= 10; ntt_run (ntt_host.hip) sends a plan with a longer pass to the 8 x 32-bit kernel
+// derived for k <= 10; ntt_plan (ntt_plan.hpp) sends a plan with a longer pass to the 8 x 32-bit kernel
 constexpr uint32_t FR30_MAX_STAGES = 10;
 
 TY_HD constexpr uint32_t fr30_r(int i) {

@@ -1,6 +1,7 @@
 // Shared state of the host driver of libtyplonk_hip.so (implementation of include/typlonk.h for gfx950).
 //   ctx.hip       context, workspaces, profiling events, device vectors
-//   ntt_host.hip  NTT planning (tables, pass decomposition) + typlonk_ntt_*
+//   ntt_host.hip  NTT staging: plan (ntt_plan.hpp: every decision, no device needed), acquire the tables it lists, queue its
+//                 passes; the table cache + typlonk_ntt_*
 //   msm_host.hip  MSM staging: plan (msm_plan.hpp: every decision, no device needed), size the workspace, queue the sort /
 //                 accumulate / reduce launches; lanes of a batch, host finish + SRS + typlonk_msm_*
 //   comm.hip      RCCL exchange behind the C ABI
@@ -17,6 +18,7 @@
 #include "g1.hpp"
 #include "g1_host64.hpp"
 #include "launch.hpp"
+#include "ntt_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -211,7 +213,7 @@ struct typlonk_ctx {
     int ntt_fr30 = 1;              // 0 = the 8 x 32-bit kernel everywhere, 1 = the default policy (9 x 30-bit butterflies, fr30.hpp, for
                                    // every inverse transform and for forward ones up to 2^NTT_FR30_FWD_MAX_LOG), 2 = 30-bit everywhere
     int ntt_big = 1;               // TYPLONK_NTT_BIG: the two-pass 2^20 plan on 4096-element tiles 0 = never, 1 = where it measures
-                                   // faster (ntt_run_batch), 2 = for every 2^20 transform outside a prover round
+                                   // faster (ntt_plan), 2 = for every 2^20 transform outside a prover round
     // profiling
     bool profiling = false;
     bool prof_light = false;       // typlonk_set_profiling(ctx, 2): only the bucket-accumulation launches are bracketed
@@ -222,12 +224,6 @@ struct typlonk_ctx {
 };
 
 namespace tyh {
-
-// full (one-multiplication) twiddle / coset tables are built up to this many entries (512 MB); above, two-level tables
-constexpr uint32_t NTT_FULL_MAX_LOG = 24;
-// default policy (TYPLONK_NTT_FR30 = 1): forward transforms take the 9 x 30-bit kernel up to this size, inverse ones always
-// (their closing factor is free); set from the same-box A/B of the two kernels (ntt_host.hip, ntt_run)
-constexpr uint32_t NTT_FR30_FWD_MAX_LOG = 32;
 
 int fail(typlonk_ctx* c, int code, const std::string& msg);
 
@@ -316,9 +312,9 @@ Fr fr_domain_root(uint32_t log_n);      // generator of the size-2^log_n domain 
 Fr fr_domain_root_inv(uint32_t log_n);
 Fr fr_inv_pow2(uint32_t log_n);         // (2^log_n)^-1 (size_inv)
 Fr fr_from_u64(uint64_t x);
-// two-level power tables of `base` covering exponents < 2^log_len: lo[j] = base^j (j < 2^h), hi[j] = hi_scale * base^(j 2^h)
-int get_pow2l(typlonk_ctx* ctx, const std::string& key, const Fr& base, const Fr& hi_scale, uint32_t log_len, Table* lo,
-              Table* hi, uint32_t* h_out);
+// the forward two-level twiddles of the 2^log_n domain, w its generator: lo[j] = w^j (j < 2^h), hi[j] = w^(j 2^h)
+// (j < 2^(log_n - h)) -- the very tables (one cache entry each) a transform's inter-pass twiddles of that row length are
+int domain_twiddles(typlonk_ctx* ctx, uint32_t log_n, const Fr** lo, const Fr** hi, uint32_t* h);
 // short_in / n_valid: the transform of a ZERO-PADDED vector -- the first pass reads short_in[0, n_valid) and takes every
 // element beyond as zero (no padded copy, no reads of zeros or of their coset factors); the result lands in d_data.
 int ntt_run(typlonk_ctx* ctx, Fr* d_data, uint32_t log_n, int inverse, const uint64_t* coset_shift, bool sync = true,

@@ -1,4 +1,4 @@
-// libtyplonk_hip.so -- NTT planning: twiddle / coset tables, pass decomposition, the typlonk_ntt_* entry points
+// libtyplonk_hip.so -- NTT host side: the table cache, the executor of ntt_plan (ntt_plan.hpp), the typlonk_ntt_* entry points
 // Part of the host driver of include/typlonk.h (see host.hpp for the shared state).  There is deliberately no CPU compute
 // fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #include "host.hpp"
@@ -67,69 +67,26 @@ int upload_table(typlonk_ctx* ctx, const std::string& key, const std::vector<Fr>
     return TYPLONK_OK;
 }
 
-// powers table: out[j] = scale * base^j, j < n
-int get_pow_table(typlonk_ctx* ctx, const std::string& key, const Fr& base, const Fr& scale, size_t n, Table* out) {
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        it->second.last_use = ++ctx->table_tick;
-        *out = it->second;
-        return TYPLONK_OK;
-    }
-    std::vector<Fr> h(n);
-    Fr x = scale;
-    for (size_t j = 0; j < n; ++j) {
-        h[j] = x;
-        x = fe_mul(x, base);
-    }
-    return upload_table(ctx, key, h, out);
-}
-
-// powers table of the 9 x 30-bit kernel: out[j] = scale * base^j re-cut into nine 30-bit limbs on a 12-word (48-byte)
-// stride -- what NttArith30::ldtw (ntt_kernels.hip) reads from global memory
-int get_pow_table30(typlonk_ctx* ctx, const std::string& key, const Fr& base, const Fr& scale, size_t n, Table* out) {
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        it->second.last_use = ++ctx->table_tick;
-        *out = it->second;
-        return TYPLONK_OK;
-    }
-    std::vector<Fr> h((12 * n + 7) / 8, Fr::zero());
-    uint32_t* w = reinterpret_cast<uint32_t*>(h.data());
-    Fr x = scale;
-    for (size_t j = 0; j < n; ++j) {
-        for (int i = 0; i < 9; ++i) {   // fr30_unpack (fr30.hpp) on the host
-            const int bit = 30 * i, wi = bit >> 5, sh = bit & 31;
-            uint32_t t = x.v[wi] >> sh;
-            if (sh > 2 && wi + 1 < 8) t |= x.v[wi + 1] << (32 - sh);
-            w[12 * j + i] = t & 0x3fffffffu;
-        }
-        x = fe_mul(x, base);
-    }
-    return upload_table(ctx, key, h, out);
+std::string fr_hex(const Fr& f) {
+    char buf[80];
+    snprintf(buf, sizeof(buf), "%08x%08x%08x%08x%08x%08x%08x%08x", f.v[7], f.v[6], f.v[5], f.v[4], f.v[3], f.v[2],
+             f.v[1], f.v[0]);
+    return buf;
 }
 
 // Full one-multiplication table built on the device from a two-level pair (launch_ntt_full_table); kept per
-// context like every other table.  Sizes above 2^NTT_FULL_MAX_LOG entries (2^24 = 512 MB) are not
-// built: *out stays empty and the kernel composes the factor from the two-level tables instead.
-int get_full_table(typlonk_ctx* ctx, const std::string& key, const Table& lo, const Table& hi, uint32_t h, uint64_t S,
-                   uint64_t n, Table* out) {
-    *out = Table{};
-    if (n > (1ull << NTT_FULL_MAX_LOG)) return TYPLONK_OK;
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        it->second.last_use = ++ctx->table_tick;
-        *out = it->second;
-        return TYPLONK_OK;
-    }
+// context like every other table.  No room: *out stays empty and the kernel composes the factor from the two-level
+// tables instead (sizes above 2^NTT_FULL_MAX_LOG entries -- 2^24 = 512 MB -- are not even asked for: ntt_plan.hpp).
+int build_full_table(typlonk_ctx* ctx, const std::string& key, const NttTableReq& r, const Table& lo, const Table& hi, Table* out) {
     Table t;
-    t.n = n;
+    t.n = r.n;
     t.last_use = ++ctx->table_tick;
-    hipError_t e = hipMalloc((void**)&t.d, n * sizeof(Fr));
+    hipError_t e = hipMalloc((void**)&t.d, r.n * sizeof(Fr));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return TYPLONK_OK;  // no room: fall back to the two-level tables
+        return TYPLONK_OK;  // fall back to the two-level tables
     }
-    launch_ntt_full_table(lo.d, hi.d, h, S, n, t.d, ctx->stream);
+    launch_ntt_full_table(lo.d, hi.d, r.h, r.S, r.n, t.d, ctx->stream);
     {
         DevGuard g;
         g.add(t.d);
@@ -144,27 +101,95 @@ int get_full_table(typlonk_ctx* ctx, const std::string& key, const Table& lo, co
     return TYPLONK_OK;
 }
 
-std::string fr_hex(const Fr& f) {
-    char buf[80];
-    snprintf(buf, sizeof(buf), "%08x%08x%08x%08x%08x%08x%08x%08x", f.v[7], f.v[6], f.v[5], f.v[4], f.v[3], f.v[2],
-             f.v[1], f.v[0]);
-    return buf;
+// what the named bases and scales of a call's table requests (ntt_plan.hpp) stand for
+struct NttValues {
+    uint32_t log_n = 0;
+    const uint64_t* shift = nullptr;
+    std::string shift_hex;
+    bool have_inv = false;
+    Fr shift_inv;   // computed when the first table that needs it is BUILT: a resident coset group costs no field inversion
+    NttValues(uint32_t lg, const uint64_t* g) : log_n(lg), shift(g) {
+        if (g) shift_hex = fr_hex(shift_fr());
+    }
+    Fr shift_fr() const {
+        Fr g;
+        memcpy(g.v, shift, sizeof(g.v));
+        return g;
+    }
+    Fr base(const NttTableReq& r) {
+        Fr b = Fr::one();
+        if (r.base == NTT_B_ROOT) b = fr_domain_root(r.base_log);
+        if (r.base == NTT_B_ROOT_INV) b = fr_domain_root_inv(r.base_log);
+        if (r.base == NTT_B_SHIFT) b = shift_fr();
+        if (r.base == NTT_B_SHIFT_INV) {
+            if (!have_inv) shift_inv = fe_inv(shift_fr());
+            have_inv = true;
+            b = shift_inv;
+        }
+        for (uint32_t i = 0; i < r.base_sqr; ++i) b = fe_sqr(b);
+        return b;
+    }
+    Fr scale(const NttTableReq& r) const {
+        const Fr c14 = fr_from_u64(1u << 14);
+        if (r.scale == NTT_S_NINV) return fr_inv_pow2(log_n);
+        if (r.scale == NTT_S_C14) return c14;
+        if (r.scale == NTT_S_NINV_C14) return fe_mul(fr_inv_pow2(log_n), c14);
+        return Fr::one();
+    }
+};
+
+// THE table lookup: the cached table of a request, built first if the context does not hold it yet.  got = the tables of
+// the requests before it in the same list (a full table is made from its pair).  An empty *out with TYPLONK_OK: a full
+// table there was no room for.
+int get_table(typlonk_ctx* ctx, const NttTableReq& r, NttValues& val, const Table* got, Table* out) {
+    *out = Table{};
+    const std::string key = ntt_key(r, val.shift_hex);
+    auto it = ctx->tables.find(key);
+    if (it != ctx->tables.end()) {
+        it->second.last_use = ++ctx->table_tick;
+        *out = it->second;
+        return TYPLONK_OK;
+    }
+    if (r.kind == NTT_FULL) return build_full_table(ctx, key, r, got[r.lo], got[r.hi], out);
+    const Fr base = val.base(r);
+    Fr x = val.scale(r);
+    std::vector<Fr> h;
+    if (r.kind != NTT_POW30) {   // out[j] = scale * base^j
+        h.resize(r.n);
+        for (size_t j = 0; j < r.n; ++j) {
+            h[j] = x;
+            x = fe_mul(x, base);
+        }
+    } else {   // the same re-cut into nine 30-bit limbs on a 12-word (48-byte) stride -- what NttArith30::ldtw (ntt_kernels.hip) reads
+        h.assign((12 * r.n + 7) / 8, Fr::zero());
+        uint32_t* w = reinterpret_cast<uint32_t*>(h.data());
+        for (size_t j = 0; j < r.n; ++j) {
+            for (int i = 0; i < 9; ++i) {   // fr30_unpack (fr30.hpp) on the host
+                const int bit = 30 * i, wi = bit >> 5, sh = bit & 31;
+                uint32_t t = x.v[wi] >> sh;
+                if (sh > 2 && wi + 1 < 8) t |= x.v[wi + 1] << (32 - sh);
+                w[12 * j + i] = t & 0x3fffffffu;
+            }
+            x = fe_mul(x, base);
+        }
+    }
+    return upload_table(ctx, key, h, out);
 }
 
-// two-level power tables of `base` covering exponents < 2^log_len:
-//   lo[j] = base^j (j < 2^h),  hi[j] = hi_scale * base^(j * 2^h) (j < 2^(log_len-h))
-int get_pow2l(typlonk_ctx* ctx, const std::string& key, const Fr& base, const Fr& hi_scale, uint32_t log_len,
-              Table* lo, Table* hi, uint32_t* h_out) {
-    const uint32_t h = (log_len + 1) / 2;
-    *h_out = h;
-    int rc = get_pow_table(ctx, key + ":lo", base, Fr::one(), (size_t)1 << h, lo);
-    if (rc) return rc;
-    Fr step = base;
-    for (uint32_t i = 0; i < h; ++i) step = fe_sqr(step);
-    return get_pow_table(ctx, key + ":hi", step, hi_scale, (size_t)1 << (log_len - h), hi);
+int domain_twiddles(typlonk_ctx* ctx, uint32_t log_n, const Fr** lo, const Fr** hi, uint32_t* h) {
+    std::vector<NttTableReq> req;
+    ntt_push_domain_twiddles(req, false, NTT_F32, 0, log_n);
+    NttValues val(log_n, nullptr);
+    Table t[2];
+    for (int i = 0; i < 2; ++i)
+        if (int rc = get_table(ctx, req[i], val, t, &t[i])) return rc;
+    *lo = t[0].d;
+    *hi = t[1].d;
+    *h = req[1].base_sqr;
+    return TYPLONK_OK;
 }
 
-// Coset tables are keyed by the caller's shift ("cs:<dir>:<log_n>:<shift hex>..."): a caller that varies the shift
+// Coset tables are keyed by the caller's shift (ntt_plan.hpp, ntt_coset_group): a caller that varies the shift
 // would otherwise grow HBM without bound.  Before a new group is built, drop least-recently-used groups until the
 // cache is inside its limits (the quotient's generator 7 is looked up on every proof and therefore stays).
 int evict_coset_tables(typlonk_ctx* ctx, const std::string& incoming_group, size_t incoming_bytes) {
@@ -173,9 +198,8 @@ int evict_coset_tables(typlonk_ctx* ctx, const std::string& incoming_group, size
         std::map<std::string, std::pair<uint64_t, size_t>> groups;  // group -> (last use, bytes)
         size_t bytes = 0;
         for (const auto& kv : ctx->tables) {
-            if (kv.first.compare(0, 3, "cs:") != 0) continue;
-            size_t cut = kv.first.find(':', kv.first.find(':', kv.first.find(':', 3) + 1) + 1);  // after the shift hex
-            const std::string grp = kv.first.substr(0, cut);
+            const std::string grp = ntt_coset_group_of(kv.first);
+            if (grp.empty()) continue;
             auto& g = groups[grp];
             g.first = std::max(g.first, kv.second.last_use);
             g.second += kv.second.n * sizeof(Fr);
@@ -197,8 +221,7 @@ int evict_coset_tables(typlonk_ctx* ctx, const std::string& incoming_group, size
         // whole device rather than for the current stream only
         HIPCHK(hipDeviceSynchronize());
         for (auto it = ctx->tables.begin(); it != ctx->tables.end();) {
-            if (it->first.compare(0, victim.size(), victim) == 0 &&
-                (it->first.size() == victim.size() || it->first[victim.size()] == ':')) {
+            if (ntt_coset_group_of(it->first) == victim) {
                 (void)hipFree(it->second.d);
                 it = ctx->tables.erase(it);
             } else {
@@ -208,27 +231,26 @@ int evict_coset_tables(typlonk_ctx* ctx, const std::string& incoming_group, size
     }
 }
 
-// big = 4096-element tiles (1024 threads, 128 KiB of LDS): sub-transforms of 2^10 points with 4 adjacent columns, so a
-// 2^20 transform needs two passes instead of three -- one load/store round and one inter-pass twiddle fewer.  Only 2^20:
-// that is 256 tiles, one per CU; 2^17..2^19 would leave most of the chip idle (measured: 2^19 0.097 -> 0.132 ms) and
-// 2^21.. do not fit (2^11-point sub-transforms x 4 columns = 256 KiB).
-void split_log(uint32_t L, uint32_t ks[4], uint32_t* P, bool big = false) {
-    uint32_t p = L <= 10 ? 1 : (L <= 16 ? 2 : (L <= 24 ? 3 : 4));
-    if (big && L == 20) p = 2;
-    *P = p;
-    for (uint32_t i = 0; i < p; ++i) ks[i] = L / p + (i < L % p ? 1 : 0);
-}
-
-uint32_t ilog2_u64(uint64_t x) {
-    uint32_t r = 0;
-    while ((1ull << (r + 1)) <= x) ++r;
-    return r;
-}
-
 int ntt_run(typlonk_ctx* ctx, Fr* d_data, uint32_t log_n, int inverse, const uint64_t* coset_shift, bool sync, const Fr* short_in,
             uint64_t n_valid) {
     if (!d_data) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null data");
     return ntt_run_batch(ctx, &d_data, 1, log_n, inverse, coset_shift, sync, short_in ? &short_in : nullptr, n_valid);
+}
+
+// the pointer of NttPassArgs a table feeds.  The 30-bit kernel reads full tables only: the halves of its pairs feed nothing.
+static void wire_table(NttPassArgs& a, const NttTableReq& r, const Table& t) {
+    const bool lo = r.kind == NTT_PAIR_LO, hi = r.kind == NTT_PAIR_HI;
+    if (r.form == NTT_F30 && (lo || hi)) return;
+    switch (r.role) {
+        case NTT_SUB:
+            if (r.form == NTT_F30) a.sub_tw30 = reinterpret_cast<const uint32_t*>(t.d);
+            else a.sub_tw = t.d;
+            break;
+        case NTT_TW: (lo ? a.tw_lo : hi ? a.tw_hi : a.tw_full) = t.d; break;
+        case NTT_PRE: (lo ? a.pre_lo : hi ? a.pre_hi : a.pre_full) = t.d; break;
+        case NTT_POST: (lo ? a.post_lo : hi ? a.post_hi : a.post_full) = t.d; break;
+        case NTT_SCALE: a.scale = t.d; break;
+    }
 }
 
 // `count` transforms of the same size, direction and coset in ONE sequence of pass launches: pass p of every vector is
@@ -237,239 +259,63 @@ int ntt_run(typlonk_ctx* ctx, Fr* d_data, uint32_t log_n, int inverse, const uin
 // (:113-115), the three sigmas (:334-338, :412-418), the five selectors (plonk/src/builder.rs:84-88) -- and a 2^20
 // transform alone is one round of tiles on the chip (every CU loads, computes and stores in step); a launch with 3 x
 // the tiles lets rounds overlap.  Bit-identical to `count` single calls (the same kernels on the same tiles).
-// More than NTT_BATCH_MAX vectors (or more than the scratch cap) go through in groups.
+// More vectors than the plan's group go through in groups.  Every decision is ntt_plan's (ntt_plan.hpp).
 int ntt_run_batch(typlonk_ctx* ctx, Fr* const* d_data, size_t count, uint32_t log_n, int inverse, const uint64_t* coset_shift,
                   bool sync, const Fr* const* short_in, uint64_t n_valid) {
-    if (log_n > 32) return fail(ctx, TYPLONK_ERR_DOMAIN, "log_n > 32 (Fr two-adicity)");
+    // (the device is asked for its 144 KiB of LDS only by a transform that could use them)
+    const bool rounds = ctx->prover_rounds_active != 0;
+    const NttFacts facts{ctx->ntt_fr30, ctx->ntt_big, rounds, log_n == 20 && ctx->ntt_big != 0 && !rounds && ntt_big_tiles_available()};
+    const NttPlan pl = ntt_plan(log_n, inverse != 0, coset_shift != nullptr, count, short_in != nullptr, facts);
+    if (pl.status == NTT_PLAN_DOMAIN) return fail(ctx, TYPLONK_ERR_DOMAIN, "log_n > 32 (Fr two-adicity)");
     if (!d_data && count) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null data");
     for (size_t v = 0; v < count; ++v)
         if (!d_data[v]) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null data");
-    if (count == 0) return TYPLONK_OK;
-    // vectors per launch: at most NTT_BATCH_MAX, and a multi-pass transform keeps one scratch vector per batch member
-    // (<= 2^25 elements = 1 GiB of scratch in all: the 2^24-point coset extensions of a 2^22-row proof go two at a time)
-    size_t group = std::min<size_t>(count, NTT_BATCH_MAX);
-    while (group > 1 && (((uint64_t)group) << log_n) > (1ull << 25)) --group;
-    if (count > group) {
-        int rc = TYPLONK_OK;
-        for (size_t g0 = 0; g0 < count && !rc; g0 += group)
-            rc = ntt_run_batch(ctx, d_data + g0, std::min(group, count - g0), log_n, inverse, coset_shift, sync,
-                               short_in ? short_in + g0 : nullptr, n_valid);
-        return rc;
-    }
-    prof_begin(ctx);
-    if (log_n == 0) {
-        prof_collect(ctx);
-        return TYPLONK_OK;  // size-1 transform is the identity (g^0 = 1, n^-1 = 1)
-    }
+    if (pl.status == NTT_PLAN_EMPTY) return TYPLONK_OK;
     const uint64_t N = 1ull << log_n;
-    uint32_t ks[4], P;
-    // (not inside a prover round: there the 144 KiB workgroups crowd out the LDS of the MSM lanes' sort kernels running
-    // beside them -- prove() 38.1 -> 38.3 ms in the same-box A/B)
-    // (forward only: an inverse 2^20 transform is 4 % faster in three passes of the 30-bit kernel, 0.148 against 0.153 ms)
-    // (round 4: the 30-bit kernel reads its sub-transform twiddles from global memory, so 4096 of its 36-byte elements fit
-    // the LDS -- 144 KiB -- and it can take the two-pass form too)
-    const bool big = log_n == 20 && ctx->ntt_big != 0 && ctx->prover_rounds_active == 0 && ntt_big_tiles_available();
-    // log2 of the tile capacity: 4096-element tiles in the first pass of the two-pass 2^20 transform (strided: four columns
-    // make 128-byte runs) and 2048 in the last (rows are contiguous, and two workgroups per CU overlap each other's
-    // load / compute / store phases: 0.0775 -> 0.070 ms, profiles/r03_ntt_2_20_tiles.txt)
-    const uint32_t cap_first = big ? 12u : 10u;
-    const uint32_t cap_last = big ? 11u : 10u;
-    split_log(log_n, ks, &P, big);
-    const std::string dir = inverse ? "i" : "f";
+    if (int rc = ensure(ctx, ctx->ntt_scratch, pl.scratch_bytes)) return rc;
+    Fr* const scratch = pl.scratch_bytes ? (Fr*)ctx->ntt_scratch.p : nullptr;
 
-    Fr* scratch = nullptr;
-    if (P >= 2) {
-        int rc = ensure(ctx, ctx->ntt_scratch, count * N * sizeof(Fr));
-        if (rc) return rc;
-        scratch = (Fr*)ctx->ntt_scratch.p;
+    // the tables, in the plan's order.  The 30-bit kernel's: until one of its full tables comes back empty -- the transform
+    // then runs on the 8 x 32 kernel, which still lacks the full inter-pass tables only it looks up.
+    NttValues val(log_n, coset_shift);
+    if (coset_shift && pl.status == NTT_PLAN_OK)
+        if (int rc = evict_coset_tables(ctx, ntt_coset_group(inverse != 0, log_n, val.shift_hex), (size_t)N * sizeof(Fr))) return rc;
+    std::vector<Table> got(pl.tables.size());
+    bool f30 = pl.f30_eligible, more30 = true;
+    for (size_t i = 0; i < pl.tables.size(); ++i) {
+        const NttTableReq& r = pl.tables[i];
+        if (r.form == NTT_F30 ? !more30 : (r.unless30 && f30)) continue;
+        if (int rc = get_table(ctx, r, val, got.data(), &got[i])) return rc;
+        if (r.form == NTT_F30 && r.kind == NTT_FULL && !got[i].d) f30 = more30 = false;
     }
+    const NttForm form = f30 ? NTT_F30 : NTT_F32;
 
-    // measured (HISTORY.md section 5): the 9 x 30-bit kernel is 9-12 % faster up to 2^19; at 2^20 the two-pass 4096-element
-    // tiles of the 8 x 32 kernel win, and from 2^21 on the 36-B LDS elements cost a workgroup per CU (3 instead of 4)
-    // and a forward transform pays one extra reducing multiplication per element: mode 1 (default) stops at 2^19
-    // Round 3 (radix-4 groups in both kernels, profiles/r03_ntt_fr30_modes.txt): an INVERSE transform is 4-9 % faster on the
-    // 30-bit kernel at every size (its n^-1 / coset factor closes the last pass for free), a forward one from 2^21 on is
-    // not; at 2^20 a forward transform takes the two-pass big tiles when they are allowed, the 30-bit kernel otherwise
-    // Round 4 (profiles/r04_ntt_fr30_global_twiddles.txt): with its twiddles in global memory the 30-bit kernel runs four
-    // 1024-element workgroups per CU and takes the two-pass 2^20 form: 2^20 0.141 -> 0.129 ms in both directions, 2^21
-    // forward 0.268 -> 0.252; mode 1 (default) = the 30-bit kernel for every inverse transform and for forward ones up to
-    // 2^NTT_FR30_FWD_MAX_LOG points (host.hpp)
-    const bool want30 = ctx->ntt_fr30 == 2 || (ctx->ntt_fr30 == 1 && (inverse || log_n <= NTT_FR30_FWD_MAX_LOG));
-
-    // coset / scaling tables (the full tables of the 8 x 32 kernel are not built when the other kernel will run)
-    Table pre_lo{}, pre_hi{}, post_lo{}, post_hi{}, scale{}, pre_full{}, post_full{};
-    uint32_t pre_h = 0, post_h = 0;
-    Fr n_inv = Fr::one();
-    if (inverse) n_inv = fr_inv_pow2(log_n);
-    if (coset_shift) {
-        Fr g;
-        memcpy(g.v, coset_shift, sizeof(g.v));
-        if (!inverse) {
-            const std::string key = "cs:f:" + std::to_string(log_n) + ":" + fr_hex(g);
-            int rc = evict_coset_tables(ctx, key, (size_t)N * sizeof(Fr));
-            if (rc) return rc;
-            rc = get_pow2l(ctx, key, g, Fr::one(), log_n, &pre_lo, &pre_hi, &pre_h);
-            if (rc) return rc;
-            if (!want30 && (rc = get_full_table(ctx, key + ":full", pre_lo, pre_hi, pre_h, 0, N, &pre_full))) return rc;
-        } else {
-            const std::string key = "cs:i:" + std::to_string(log_n) + ":" + fr_hex(g);
-            const bool resident = ctx->tables.count(key + ":lo") && ctx->tables.count(key + ":hi");
-            const Fr gi = resident ? Fr::one() : fe_inv(g);  // only a table build needs the value
-            int rc = evict_coset_tables(ctx, key, (size_t)N * sizeof(Fr));
-            if (rc) return rc;
-            rc = get_pow2l(ctx, key, gi, n_inv, log_n, &post_lo, &post_hi, &post_h);
-            if (rc) return rc;
-            if (!want30 && (rc = get_full_table(ctx, key + ":full", post_lo, post_hi, post_h, 0, N, &post_full))) return rc;
-        }
-    } else if (inverse) {
-        int rc = get_pow_table(ctx, "ninv:" + std::to_string(log_n), Fr::one(), n_inv, 1, &scale);
-        if (rc) return rc;
-    }
-
-    // The 9 x 30-bit kernel (fr30.hpp) multiplies with R' = 2^270: its tables carry an extra factor 2^14 and every one
-    // of them must exist as a full table; if one cannot be built (size, memory) the transform runs on the 8 x 32 kernel.
-    Table sub30[4]{}, tw30[4]{}, pre30{}, post30{}, scale30{};
-    bool f30 = want30;
-    for (uint32_t p = 0; p < P; ++p) f30 = f30 && ks[p] <= FR30_MAX_STAGES;   // the bounds of fr30.hpp hold for k <= 10
-    if (f30) {
-        const Fr c14 = fr_from_u64(1u << 14);
-        int rc = TYPLONK_OK;
-        if (coset_shift) {
-            Fr g;
-            memcpy(g.v, coset_shift, sizeof(g.v));
-            const std::string key = std::string("cs:") + (inverse ? "i:" : "f:") + std::to_string(log_n) + ":" + fr_hex(g) + ":30";
-            Table lo, hi;
-            uint32_t h = 0;
-            if (!inverse) {
-                if ((rc = get_pow2l(ctx, key, g, c14, log_n, &lo, &hi, &h))) return rc;
-                if ((rc = get_full_table(ctx, key + ":full", lo, hi, h, 0, N, &pre30))) return rc;
-                f30 = pre30.d != nullptr;
-            } else {
-                const bool resident = ctx->tables.count(key + ":lo") && ctx->tables.count(key + ":hi");
-                if ((rc = get_pow2l(ctx, key, resident ? Fr::one() : fe_inv(g), fe_mul(n_inv, c14), log_n, &lo, &hi, &h))) return rc;
-                if ((rc = get_full_table(ctx, key + ":full", lo, hi, h, 0, N, &post30))) return rc;
-                f30 = post30.d != nullptr;
+    for (size_t g0 = 0; g0 < count; g0 += pl.group) {
+        const size_t cnt = std::min(pl.group, count - g0);
+        prof_begin(ctx);
+        for (uint32_t p = 0; p < pl.P; ++p) {
+            const NttPassPlan& ps = pl.pass[p];
+            NttPassArgs a = ps.a;   // every scalar
+            if (ps.short_in) a.n_valid = n_valid;
+            for (size_t i = 0; i < pl.tables.size(); ++i)
+                if (pl.tables[i].pass == p && pl.tables[i].form == form) wire_table(a, pl.tables[i], got[i]);
+            for (size_t v = 0; v < cnt; ++v) {
+                Fr* scr = scratch ? scratch + v * N : nullptr;
+                a.in[v] = (p == 0) ? (short_in ? short_in[g0 + v] : d_data[g0 + v]) : scr;
+                a.out[v] = a.last ? d_data[g0 + v] : scr;
             }
-        } else if (inverse) {
-            if ((rc = get_pow_table(ctx, "ninv30:" + std::to_string(log_n), Fr::one(), fe_mul(n_inv, c14), 1, &scale30))) return rc;
-        }
-        uint64_t rl = N;
-        for (uint32_t p = 0; p < P && f30; ++p) {
-            const uint32_t k = ks[p];
-            const uint64_t M = 1ull << k;
-            const Fr w = inverse ? fr_domain_root_inv(k) : fr_domain_root(k);
-            if ((rc = get_pow_table30(ctx, "sub30:" + dir + ":" + std::to_string(k), w, c14, (size_t)std::max<uint64_t>(M / 2, 1), &sub30[p])))
-                return rc;
-            if (p + 1 < P) {
-                const uint32_t lrow = ilog2_u64(rl);
-                const Fr wr = inverse ? fr_domain_root_inv(lrow) : fr_domain_root(lrow);
-                Table lo, hi;
-                uint32_t h = 0;
-                if ((rc = get_pow2l(ctx, "tw30:" + dir + ":" + std::to_string(lrow), wr, c14, lrow, &lo, &hi, &h))) return rc;
-                if ((rc = get_full_table(ctx, "tw30:" + dir + ":" + std::to_string(lrow) + ":full:" + std::to_string(k), lo, hi, h,
-                                         rl / M, rl, &tw30[p])))
-                    return rc;
-                f30 = tw30[p].d != nullptr;
+            const unsigned blocks = (unsigned)(a.blocks_per_vec * cnt);
+            {
+                static const char* names[4] = {"ntt_pass1", "ntt_pass2", "ntt_pass3", "ntt_pass4"};
+                StageTimer st(ctx, names[p]);
+                if (f30) launch_ntt_pass30(a, blocks, ps.threads, ps.lds[form], ctx->stream);
+                else launch_ntt_pass(a, blocks, ps.threads, ps.lds[form], ctx->stream);
             }
-            rl /= M;
+            HIPCHK(hipGetLastError());
         }
+        if (pl.P && (sync || (ctx->profiling && !ctx->prof_light))) HIPCHK(hipStreamSynchronize(ctx->stream));
+        prof_collect(ctx);
     }
-
-    uint64_t row_len = N;  // length of the rows the current pass works inside
-    uint64_t rows = 1;
-    for (uint32_t p = 0; p < P; ++p) {
-        const uint32_t k = ks[p];
-        const uint64_t M = 1ull << k;
-        const bool last = (p + 1 == P);
-        NttPassArgs a{};
-        a.k = k;
-        a.last = last ? 1 : 0;
-        a.S = row_len / M;
-        a.row_len = row_len;
-        // sub-transform twiddles w_M^e
-        {
-            const Fr w = inverse ? fr_domain_root_inv(k) : fr_domain_root(k);
-            Table t;
-            int rc = get_pow_table(ctx, "sub:" + dir + ":" + std::to_string(k), w, Fr::one(), (size_t)std::max<uint64_t>(M / 2, 1), &t);
-            if (rc) return rc;
-            a.sub_tw = t.d;
-        }
-        uint32_t logT;
-        if (!last) {
-            const uint32_t lrow = ilog2_u64(row_len);
-            const Fr w = inverse ? fr_domain_root_inv(lrow) : fr_domain_root(lrow);
-            Table lo, hi;
-            int rc = get_pow2l(ctx, "tw:" + dir + ":" + std::to_string(lrow), w, Fr::one(), lrow, &lo, &hi, &a.tw_h);
-            if (rc) return rc;
-            a.tw_lo = lo.d;
-            a.tw_hi = hi.d;
-            Table full;
-            if (!f30) {
-                rc = get_full_table(ctx, "tw:" + dir + ":" + std::to_string(lrow) + ":full:" + std::to_string(k), lo, hi, a.tw_h,
-                                    a.S, row_len, &full);
-                if (rc) return rc;
-            }
-            a.tw_full = full.d;
-            logT = std::min<uint32_t>(cap_first - k, ilog2_u64(a.S));
-        } else {
-            const uint64_t N1 = 1ull << ks[0];
-            a.N1 = (P == 1) ? 1 : N1;
-            a.Q = (P <= 2) ? 1 : rows / N1;
-            a.N2 = (P >= 3) ? (1ull << ks[1]) : 1;
-            a.N3 = (P == 4) ? (1ull << ks[2]) : 1;
-            a.out_stride = N / M;
-            logT = (P == 1) ? 0 : std::min<uint32_t>(cap_last - k, ks[0]);
-            a.post_lo = post_lo.d;
-            a.post_hi = post_hi.d;
-            a.post_h = post_h;
-            a.post_full = post_full.d;
-            a.scale = scale.d;
-        }
-        a.logT = logT;
-        if (p == 0) {
-            a.pre_lo = pre_lo.d;
-            a.pre_hi = pre_hi.d;
-            a.pre_h = pre_h;
-            a.pre_full = pre_full.d;
-        }
-        a.n_valid = ~0ull;
-        if (p == 0 && short_in) {
-            a.n_valid = n_valid;
-        }
-        for (size_t v = 0; v < count; ++v) {
-            const Fr* src = short_in ? short_in[v] : d_data[v];
-            Fr* scr = scratch ? scratch + v * N : nullptr;
-            a.in[v] = (p == 0) ? src : scr;
-            a.out[v] = last ? d_data[v] : scr;
-        }
-        const uint64_t E = M << logT;
-        a.blocks_per_vec = (uint32_t)(N / E);
-        const uint64_t blocks = (N / E) * count;
-        if (f30) {
-            a.sub_tw = nullptr;
-            a.sub_tw30 = reinterpret_cast<const uint32_t*>(sub30[p].d);
-            a.tw_full = tw30[p].d;
-            a.tw_lo = a.tw_hi = nullptr;
-            a.pre_lo = a.pre_hi = a.post_lo = a.post_hi = nullptr;
-            a.pre_full = p == 0 ? pre30.d : nullptr;
-            a.post_full = last ? post30.d : nullptr;
-            a.scale = last ? scale30.d : nullptr;
-        }
-        // LDS: the tile, and (8 x 32 kernel) the sub-transform's twiddles behind it
-        const size_t lds = f30 ? (size_t)E * 36 : (size_t)(E + std::max<uint64_t>(M / 2, 1)) * sizeof(Fr);
-        const unsigned threads = big ? (unsigned)std::max<uint64_t>(E / 4, 64) : 256u;
-        {
-            static const char* names[4] = {"ntt_pass1", "ntt_pass2", "ntt_pass3", "ntt_pass4"};
-            StageTimer st(ctx, names[p]);
-            if (f30) launch_ntt_pass30(a, (unsigned)blocks, threads, lds, ctx->stream);
-            else launch_ntt_pass(a, (unsigned)blocks, threads, lds, ctx->stream);
-        }
-        HIPCHK(hipGetLastError());
-        rows *= M;
-        row_len /= M;
-    }
-    if (sync || (ctx->profiling && !ctx->prof_light)) HIPCHK(hipStreamSynchronize(ctx->stream));
-    prof_collect(ctx);
     return TYPLONK_OK;
 }
 

@@ -365,11 +365,7 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
         a.n = n;
         a.stride = stride;
         a.nblk = (uint32_t)((n + PSCAN_PER_BLOCK - 1) / PSCAN_PER_BLOCK);
-        Table lo, hi;
-        const uint32_t lg = std::max<uint32_t>(log_n, 1);
-        if ((rc = get_pow2l(ctx, "tw:f:" + std::to_string(lg), fr_domain_root(lg), Fr::one(), lg, &lo, &hi, &a.w_h))) return rc;
-        a.w_lo = lo.d;
-        a.w_hi = hi.d;
+        if ((rc = domain_twiddles(ctx, std::max<uint32_t>(log_n, 1), &a.w_lo, &a.w_hi, &a.w_h))) return rc;
         const unsigned gx = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(pb_gp_terms_kernel, dim3(gx, G), dim3(256), 0, s, a);
         hipLaunchKernelGGL(pb_pscan_block_kernel, dim3(a.nblk, 2 * G), dim3(256), 0, s, a);

@@ -19,12 +19,9 @@ const uint64_t* coset_g(Fr* g_out) {
 }
 int quotient_domain(typlonk_ctx* ctx, uint32_t log_n, QuotientDomain* d) {
     const uint32_t log4 = log_n + 2;
-    Table lo, hi;
     const Fr w4 = fr_domain_root(log4);
-    const int rc = get_pow2l(ctx, "tw:f:" + std::to_string(log4), w4, Fr::one(), log4, &lo, &hi, &d->w_h);
+    const int rc = domain_twiddles(ctx, log4, &d->w_lo, &d->w_hi, &d->w_h);
     if (rc) return rc;
-    d->w_lo = lo.d;
-    d->w_hi = hi.d;
     d->n_hi = 1ull << (log4 - d->w_h);
     d->g_limbs = coset_g(&d->g);
     Fr gn = d->g, iota = w4;   // g^n; iota = w_{4n}^n, a primitive 4th root of unity
@@ -257,14 +254,8 @@ int typlonk_grand_product_dev(typlonk_ctx* ctx, const typlonk_buf* const wires[3
         memcpy(k.v, cosets[i], 32);
         a.kbeta[i] = fe_mul(k, a.beta);
     }
-    {
-        Table lo, hi;
-        const uint32_t lg = std::max<uint32_t>(log_n, 1);  // a two-level table needs at least one bit
-        rc = get_pow2l(ctx, "tw:f:" + std::to_string(lg), fr_domain_root(lg), Fr::one(), lg, &lo, &hi, &a.w_h);
-        if (rc) return rc;
-        a.w_lo = lo.d;
-        a.w_hi = hi.d;
-    }
+    rc = domain_twiddles(ctx, std::max<uint32_t>(log_n, 1), &a.w_lo, &a.w_hi, &a.w_h);  // a two-level table needs at least one bit
+    if (rc) return rc;
     launch_gp_terms(a, s);
     launch_product_scan(num, n, 0, blk, npre, s);
     launch_product_scan(den, n, 1, blk, dsuf, s);

@@ -502,11 +502,8 @@ int circuit_compile_impl(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ProfilingOff prof_off(ctx);
-    Table lo, hi;
-    rc = get_pow2l(ctx, "tw:f:" + std::to_string(log_n), fr_domain_root(log_n), Fr::one(), log_n, &lo, &hi, &t.h);
+    rc = domain_twiddles(ctx, log_n, &t.lo, &t.hi, &t.h);
     if (rc) return rc;
-    t.lo = lo.d;
-    t.hi = hi.d;
     t.log_n = log_n;
 
     CircuitEntry e;
