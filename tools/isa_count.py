@@ -2,9 +2,11 @@
 issue costs of the round-4 pricing micro-benchmark (tools/ubench4.hip, profiles/r04_ubench4_pricing.txt) -- an
 instruction-count ceiling that does not come from timing the same loop.
 
-usage: python tools/isa_count.py <file.s> <kernel-substring> <units-per-iteration> [block labels of the hot path ...]
+usage: python tools/isa_count.py [--bb] <file.s> <kernel-substring> <units-per-iteration> [block labels of the hot path ...]
 Without block labels it lists the kernel's basic blocks (size, multiplier instructions) so that the steady-state
-path can be picked by reading the listing."""
+path can be picked by reading the listing.  A block runs from one `.LBBn_m:` label to the next, so it takes in the
+fall-through blocks behind it, rare paths included; --bb also cuts at the compiler's `; %bb.N:` marks (named "%bb.N"),
+for a steady-state path that has to leave such a tail out."""
 import json, re, sys
 from collections import Counter
 
@@ -31,14 +33,18 @@ DEFAULT_NS = DEFAULT_CYCLES / CLOCK_HZ * 1e9
 
 
 def main():
-    path, kern, units = sys.argv[1], sys.argv[2], float(sys.argv[3])
-    hot = set(sys.argv[4:])
+    args = sys.argv[1:]
+    fine = bool(args) and args[0] == "--bb"
+    if fine:
+        args = args[1:]
+    path, kern, units = args[0], args[1], float(args[2])
+    hot = set(args[3:])
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + re.escape(kern) + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
     blocks, cur = [], ["entry", Counter()]
     for l in lines[start + 1:end]:
-        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        m = re.match(r"^(\.LBB\d+_\d+):", l) or (fine and re.match(r"^; (%bb\.\d+):", l))
         if m:
             blocks.append(cur)
             cur = [m.group(1), Counter()]

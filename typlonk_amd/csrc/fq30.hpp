@@ -399,6 +399,21 @@ TY_HD Fq30 fq30_sub_lazy(const Fq30& a, const Fq30& b) {
     }
     return r;
 }
+// add ? a + b : a - b + K p, normalised: the sign of b is a per-lane choice made inside the one carry pass (a limb takes
+// b_i or Kp_i - b_i).  Requires b <= K p and a + b, a + K p < 2^390.
+template <int K>
+TY_HD Fq30 fq30_addsub_lazy(const Fq30& a, const Fq30& b, bool add) {
+    Fq30 r;
+    int32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 13; ++i) {
+        const int32_t t = add ? (int32_t)b.v[i] : (int32_t)fq30_kp(K, i) - (int32_t)b.v[i];
+        const int32_t s = (int32_t)a.v[i] + t + c;
+        r.v[i] = (uint32_t)s & FQ30_MASK;
+        c = s >> 30;
+    }
+    return r;
+}
 // a - b - c + K p, normalised.  Requires b + c <= K p.
 template <int K>
 TY_HD Fq30 fq30_sub2_lazy(const Fq30& a, const Fq30& b, const Fq30& cc) {

@@ -136,6 +136,107 @@ TY_HD void g1_madd(G1Xyzz& acc, const G1Affine& q, bool neg) {
     g1_madd_xy(acc, q.x, qy);
 }
 
+// ---- the mixed addition of the accumulation loops (msm_accum.hip) --------------------------------------------------
+// g1_madd_xy spends four carry passes and three 26-word zero tests per addition on things the sum does not need.  An
+// accumulator that is only ever fed by mixed additions can drop them by carrying two bits beside the point:
+//   inf   the sum is the identity (the words of p are then meaningless): replaces ZZ == 0 mod p, tested every addition;
+//   flip  the sum is -p, not p.  madd-2008-s ends in Y3 = R (Q - X3) - Y1 PPP, and the subtraction costs a 4p - Y1 pass
+//         before the two-product reduction.  With R' = -R = Y1 - S2 instead, R' (Q - X3) + Y1 PPP = -Y3 has two positive
+//         terms, and R'^2 = R^2, so X3, ZZ3 and ZZZ3 are those of the sum: the formulas yield -(p + q), which is
+//         recorded by toggling flip, and the next point is added with the sign neg ^ flip.
+// The sign of the incoming point is applied to S2 inside the R' pass (fq30_addsub_lazy) rather than to qy in a pass of
+// its own, and the equal-x test runs in full only when some lane's lowest limb says it may hold.
+// g1_acc_finish turns the pair back into a stored XYZZ point (invariants at the top of this file).
+struct G1Acc {
+    G1Xyzz p;
+    uint32_t flags;
+};
+constexpr uint32_t G1_ACC_INF = 1u, G1_ACC_FLIP = 2u;
+
+// `c` on any active lane of the wavefront (host: this one value)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define G1_ANY_LANE(c) (__any((int)(c)) != 0)
+#else
+#define G1_ANY_LANE(c) (c)
+#endif
+
+TY_HD G1Acc g1_acc_empty() {
+    G1Acc a;
+    a.p = G1Xyzz::inf();
+    a.flags = G1_ACC_INF;
+    return a;
+}
+// continue from a stored point (flip = 0)
+TY_HD G1Acc g1_acc_from(const G1Xyzz& p) {
+    G1Acc a;
+    a.p = p;
+    a.flags = p.is_inf() ? G1_ACC_INF : 0u;
+    return a;
+}
+
+// acc += (neg ? -q : q);  q canonical (x, y < p) or the identity (0, 0).  With s = neg ^ flip, p takes +-q:
+TY_HD void g1_madd_acc(G1Acc& a, const G1Affine& q, bool neg) {
+    if (G1_ANY_LANE(q.x.v[0] == 0u)) {                                 // (0, 0) in full only where a lowest limb allows it
+        if (q.is_inf()) return;
+    }
+    if (a.flags & G1_ACC_INF) {                                        // the sum is +-q itself: p = q, flip = neg
+        a.p.x = q.x;
+        a.p.y = q.y;                                                   // < 1 (so is every Y held with flip set, see below)
+        a.p.zz = fq30_one();
+        a.p.zzz = fq30_one();
+        a.flags = neg ? G1_ACC_FLIP : 0u;
+        return;
+    }
+    const bool s = neg != ((a.flags & G1_ACC_FLIP) != 0);
+    Fq30 u2, s2, pp, rr, ppp, qq;
+    fq30_mul_pair(q.x, a.p.zz, q.y, a.p.zzz, u2, s2);                  // < 1.01 each
+    const Fq30 p = fq30_sub_lazy<6>(u2, a.p.x);                        // 1.01 + 6 < 7.1   (X1 < 5.1 <= 6)
+    // R' = Y1 - (s ? -S2 : S2):  s: Y1 + S2 < 3.2 + 1.01;  else Y1 - S2 + 2p < 3.2 + 2   (S2 < 1.01 <= 2)
+    const Fq30 r = fq30_addsub_lazy<2>(a.p.y, s2, s);                  // < 5.2
+    fq30_sqr_pair(p, r, pp, rr);                                       // pp: m(7.1,7.1) < 1.09, rr: m(5.2,5.2) < 1.05
+    fq30_mul_pair(p, pp, a.p.x, pp, ppp, qq);                          // ppp: m(7.1,1.09) < 1.02, q: m(5.1,1.09) < 1.01
+    const Fq30 x3 = fq30_sub2_lazy<4>(rr, ppp, fq30_mulk_lazy<2>(qq)); // 1.05 + 4 < 5.1  (ppp + 2q < 3.1 <= 4)
+    const Fq30 t = fq30_sub_lazy<6>(qq, x3);                           // 1.01 + 6 < 7.1
+    a.p.y = fq30_mul2_add(r, t, a.p.y, ppp);                           // -Y3 < 1 + (5.2*7.1 + 3.2*1.02)/630 < 1.07
+    a.p.x = x3;
+    fq30_mul_pair(a.p.zz, pp, a.p.zzz, ppp, a.p.zz, a.p.zzz);          // < 1.01 each
+    a.flags ^= G1_ACC_FLIP;
+    // Same x (P = 0 mod p): the formulas do not apply; they ran on bounded values, harmlessly, and the case shows in
+    // their results, so nothing stays alive for it.  ZZ1 != 0, hence P = 0 <=> ZZ3 = ZZ1 P^2 = 0; and then PPP = Q = 0,
+    // X3 = R'^2, -Y3 = -R'^3, which is 0 exactly when R' = 0: the same point (double) and not the opposite one (cancel).
+    // Both tests are exact (values < 2p) and run only when some lane's lowest limb of ZZ3 says it may be 0 or p.
+    if (G1_ANY_LANE(a.p.zz.v[0] == 0u || a.p.zz.v[0] == fq30_kp(1, 0))) {
+        if (fq30_is_zero_mod(a.p.zz)) {
+            if (fq30_is_zero_mod(a.p.y)) {                             // p was +-q as added: the sum is 2 (neg ? -q : q)
+                const Fq30 ny = fq30_neg_lazy<1>(q.y);                 // p - y <= p
+                Fq30 y;
+#pragma unroll
+                for (int i = 0; i < 13; ++i) y.v[i] = neg ? ny.v[i] : q.y.v[i];
+                a.p = g1_dbl_affine(q.x, y);                           // Y < 3.1, held with flip = 0
+                a.flags = 0u;                                          // (never the identity: #E(Fq) is odd, no point has y = 0)
+            } else {
+                a.flags = G1_ACC_INF;
+            }
+        }
+    }
+}
+
+// The sum as a stored XYZZ point: X < 5.1, Y < 3.2, ZZ, ZZZ < 1.1.  flip is set only by the two paths above that leave
+// Y < 1.07 (a stored point and a doubling are held with flip = 0), so 2p - Y < 2 restores the sign within the bound.
+TY_HD G1Xyzz g1_acc_finish(const G1Acc& a) {
+    const bool inf = (a.flags & G1_ACC_INF) != 0, flip = (a.flags & G1_ACC_FLIP) != 0;
+    const Fq30 ny = fq30_neg_lazy<2>(a.p.y);                           // (of meaningless words when inf: not used)
+    G1Xyzz r;                                                          // word by word: G1Xyzz::inf() or (X, +-Y, ZZ, ZZZ)
+#pragma unroll
+    for (int i = 0; i < 13; ++i) {
+        r.x.v[i] = inf ? fq30_one_limb(i) : a.p.x.v[i];
+        r.y.v[i] = inf ? fq30_one_limb(i) : flip ? ny.v[i] : a.p.y.v[i];
+        r.zz.v[i] = inf ? 0u : a.p.zz.v[i];
+        r.zzz.v[i] = inf ? 0u : a.p.zzz.v[i];
+    }
+    return r;
+}
+
 // a + b, both XYZZ  (add-2008-s)
 TY_HD G1Xyzz g1_add(const G1Xyzz& a, const G1Xyzz& b) {
     if (a.is_inf()) return b;

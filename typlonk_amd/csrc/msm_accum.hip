@@ -45,7 +45,8 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint32_t end = offsets[g + 1] - start > cap ? start : offsets[g + 1];  // a heavy bucket is msm_heavy_kernel's
     // init != 0: a later chunk of the same MSM (msm_host.hip, msm_enqueue) continues from the stored bucket
     if (init && start >= end) return;
-    G1Xyzz acc = init ? ld_xyzz(buckets, g) : G1Xyzz::inf();
+    // the accumulator carries its identity and sign bits beside the point (G1Acc, g1.hpp)
+    G1Acc acc = init ? g1_acc_from(ld_xyzz(buckets, g)) : g1_acc_empty();
     uint32_t pl_next = 0;
     PackedPoint pk_next;
     if (start < end) {
@@ -59,9 +60,9 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) __attribute__((amdgpu_waves_per_eu
             pl_next = sorted[pos + 1];
             pk_next = ld_packed(points, pl_next & 0x7fffffffu);
         }
-        g1_madd(acc, unpack_point(pk), (pl >> 31) != 0);
+        g1_madd_acc(acc, unpack_point(pk), (pl >> 31) != 0);
     }
-    st_xyzz(buckets, g, acc);
+    st_xyzz(buckets, g, g1_acc_finish(acc));
 }
 
 // The same with L = 2, 4, 8 or 16 lanes per bucket (KzgScheme::evaluate_in_s of a SHORT vector -- an 8-way shard of
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accum_ml_kernel(const uin
         end = offsets[g + 1] - start > cap ? start : offsets[g + 1];   // a heavy bucket is msm_heavy_kernel's
     }
     const bool skip = slot >= nbuckets || (init && start >= end);   // nothing to add: the stored bucket stays
-    G1Xyzz acc = (init && !skip && lane == 0) ? ld_xyzz(buckets, g) : G1Xyzz::inf();
+    G1Acc part = (init && !skip && lane == 0) ? g1_acc_from(ld_xyzz(buckets, g)) : g1_acc_empty();
     uint32_t pl_next = 0;
     PackedPoint pk_next;
     uint32_t pos = start + lane;
@@ -107,8 +108,9 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accum_ml_kernel(const uin
             pl_next = sorted[pos + lanes];
             pk_next = ld_packed(points, pl_next & 0x7fffffffu);
         }
-        g1_madd(acc, unpack_point(pk), (pl >> 31) != 0);
+        g1_madd_acc(part, unpack_point(pk), (pl >> 31) != 0);
     }
+    G1Xyzz acc = g1_acc_finish(part);
 #pragma unroll 1
     for (int mask = 1; mask < (int)lanes; mask <<= 1) acc = butterfly_add(acc, mask);
     if (!skip && lane == 0) st_xyzz(buckets, g, acc);
@@ -135,12 +137,13 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_heavy_kernel(const uint32
     constexpr uint32_t WPG = MSM_ACC_THREADS / 64;   // wavefronts per workgroup
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t t = blockIdx.x * WPG + wave; t < ntasks; t += gridDim.x * WPG) {   // t is uniform in the wavefront
-        G1Xyzz acc = G1Xyzz::inf();
+        G1Acc part = g1_acc_empty();
         const uint32_t end = tasks[3 * t + 1], h = tasks[3 * t + 2];
         for (uint32_t pos = tasks[3 * t] + lane; pos < end; pos += 64) {
             const uint32_t pl = sorted[pos];
-            g1_madd(acc, unpack_point(ld_packed(points, pl & 0x7fffffffu)), (pl >> 31) != 0);
+            g1_madd_acc(part, unpack_point(ld_packed(points, pl & 0x7fffffffu)), (pl >> 31) != 0);
         }
+        G1Xyzz acc = g1_acc_finish(part);
 #pragma unroll 1
         for (int mask = 1; mask < 64; mask <<= 1) acc = butterfly_add(acc, mask);
         const uint32_t k = heavy[4 * h + 2];
