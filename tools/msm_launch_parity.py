@@ -1,15 +1,18 @@
-"""Launch parity of two builds of the library (profiles/r21_msm_plan_launch_parity.txt, profiles/r22_ntt_plan_launch_parity.txt):
+"""Launch parity of two builds of the library (profiles/r21_msm_plan_launch_parity.txt, profiles/r22_ntt_plan_launch_parity.txt,
+profiles/r24_prove_plan_launch_parity.txt):
 the same work under `rocprofv3 --kernel-trace` with each build, then the ordered kernel name, grid, workgroup size and LDS
 bytes compared per stream.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR_A -- python3 tools/msm_launch_parity.py run [ntt]   (TYPLONK_LIB_PATH: build A)
-    rocprofv3 --kernel-trace --output-format csv -d DIR_B -- python3 tools/msm_launch_parity.py run [ntt]
+    rocprofv3 --kernel-trace --output-format csv -d DIR_A -- python3 tools/msm_launch_parity.py run [ntt | prove]   (TYPLONK_LIB_PATH: build A)
+    rocprofv3 --kernel-trace --output-format csv -d DIR_B -- python3 tools/msm_launch_parity.py run [ntt | prove]
     python tools/msm_launch_parity.py compare DIR_A DIR_B [OUT]
 
 run: one MSM at 2^14 terms over a plain SRS, 2^17 with c = 17 tables, 2^20 with c = 20 tables from device and from host
 scalars, and 2^21 with c = 20 tables queued in a batch of three.
 run ntt: single transforms at 2^10, 2^16, 2^20 and 2^22 in both directions, transforms on the coset 7 at 2^20 and 2^22, a
-group of three at 2^20, and one proof of the squaring chain at 2^16."""
+group of three at 2^20, and one proof of the squaring chain at 2^16.
+run prove: on one context, the squaring chain at 2^12 through typlonk_prove, typlonk_prove_compact, typlonk_prove_batch and
+typlonk_prove_batch_compact of three, and the round-by-round session with batched openings; then typlonk_prove at 2^3."""
 import csv
 import glob
 import os
@@ -76,6 +79,26 @@ def run_ntt():
     ctx.close()
 
 
+def run_prove():
+    import typlonk_amd
+    from bench import fr_mont_limbs
+    from typlonk_amd.circuits import SquaringChain
+
+    ctx = typlonk_amd.Context(0)
+    for log_n in (12, 3):
+        sid = ctx.srs_generate(fr_mont_limbs(2), (1 << log_n) + 3)
+        chain = SquaringChain(ctx, log_n)
+        w, cosets = chain.wire_evals, chain.cosets
+        ctx.prove_native(sid, chain.circuit, w, None, cosets)
+        if log_n == 12:
+            ctx.prove_compact(sid, chain.circuit, w, None, 0, cosets)
+            ctx.prove_batch(sid, chain.circuit, [w] * 3, None, cosets)
+            ctx.prove_batch_compact(sid, chain.circuit, [w] * 3, None, None, cosets)
+            ctx.prove(sid, chain.circuit, w, None, cosets, challenge_v=lambda evals: fr_mont_limbs(5))
+        print(f"PARITY_RUN prove 2^{log_n}: done", flush=True)
+    ctx.close()
+
+
 def launches(directory):
     """{stream (numbered by first appearance): [(kernel, grid, workgroup, lds)] in dispatch order}, and the column that told streams apart"""
     files = sorted(glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True))
@@ -138,7 +161,7 @@ def compare(dir_a, dir_b, out=None):
 
 if __name__ == "__main__":
     if len(sys.argv) >= 2 and sys.argv[1] == "run":
-        run_ntt() if sys.argv[2:3] == ["ntt"] else run()
+        {"ntt": run_ntt, "prove": run_prove}.get((sys.argv[2:3] or [""])[0], run)()
     elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None))
     else:

@@ -10,6 +10,8 @@
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
   tests/cpp/msm_plan_host         host build of msm_plan, every decision of an MSM, a program of its own (tests/test_msm_plan_host.py) -- g++
   tests/cpp/ntt_plan_host         host build of ntt_plan, every decision of a batch of NTTs, a program of its own (tests/test_ntt_plan_host.py) -- g++
+  tests/cpp/prove_plan_host[_san] host build of prove_plan, where a proof's data lives and what each workspace of a prover call holds, a program of its
+                                  own, once plain and once under the address and undefined-behaviour sanitizers (tests/test_prove_plan_host.py) -- g++
   tests/cpp/madd_acc_host[_san]   host build of g1_madd_acc / g1_acc_finish, the accumulation loops' mixed addition, a program of its own, once plain
                                   and once under the address and undefined-behaviour sanitizers (tests/test_madd_acc_host.py) -- g++
   tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
@@ -210,6 +212,18 @@ def build_ntt_plan_host(force: bool = False) -> str:
     return out
 
 
+def build_prove_plan_host(force: bool = False, sanitize: bool = False) -> str:
+    """tests/cpp/prove_plan_host: prove_plan (csrc/prove_plan.hpp) as the host compiles it, printing the plan of each case it reads;
+    sanitize: the same program as tests/cpp/prove_plan_host_san, compiled with -fsanitize=address,undefined"""
+    src = os.path.join(ROOT, "tests", "cpp", "prove_plan_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "prove_plan_host_san" if sanitize else "prove_plan_host")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("ff.hpp", "fr30.hpp", "ntt_args.hpp", "ntt_plan.hpp", "prove_plan.hpp")]
+    if force or _stale(out, deps):
+        extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+        _run(["g++", *extra, "-std=c++17", src, "-o", out])
+    return out
+
+
 def build_madd_acc_host(force: bool = False, sanitize: bool = False) -> str:
     """tests/cpp/madd_acc_host: g1_madd_acc / g1_acc_finish (csrc/g1.hpp) as the host compiles them, run over the cases it reads;
     sanitize: the same program as tests/cpp/madd_acc_host_san, compiled with -fsanitize=address,undefined"""
@@ -273,12 +287,15 @@ def build_all(force: bool = False) -> None:
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
     build_perm_pairs_host(force)
-    # the tests/ of a commit before msm_plan.hpp, ntt_plan.hpp or g1_madd_acc, run against this library to compare the two, has
+    # the tests/ of a commit before msm_plan.hpp, ntt_plan.hpp, prove_plan.hpp or g1_madd_acc, run against this library to compare the two, has
     # neither these programs' sources nor tests of them
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "msm_plan_host.cpp")):
         build_msm_plan_host(force)
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "ntt_plan_host.cpp")):
         build_ntt_plan_host(force)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "prove_plan_host.cpp")):
+        build_prove_plan_host(force)
+        build_prove_plan_host(force, sanitize=True)
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "madd_acc_host.cpp")):
         build_madd_acc_host(force)
         build_madd_acc_host(force, sanitize=True)

@@ -6,8 +6,12 @@
 //                 accumulate / reduce launches; lanes of a batch, host finish + SRS + typlonk_msm_*
 //   comm.hip      RCCL exchange behind the C ABI
 //   prover.hip    quotient, grand product, openings, the prover rounds, typlonk_prove; the steps it shares with prove_batch.hip
-//                 (declared below: coset_g, quotient_domain, round3_openings, lin_*); transcripts: proof_script.hpp
+//                 (declared below: prover_workspaces, coset_g, quotient_domain, round3_openings, lin_*); transcripts:
+//                 proof_script.hpp
 //   prove_batch.hip  typlonk_prove_batch: many witnesses of one circuit in waves, every stage batched across the wave
+//   prove_plan.hpp   where a proof's data lives (no device needed): the arena's regions, the roles of q, the result slots, the
+//                 scratch layouts, and the size of every workspace of a prover call.  ensure() on ops_tmp, prover_mem, quot_ext,
+//                 quot_tab and batch_tab is called by prover_workspaces and the three stand-alone entry points of prover.hip only
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip); which scalars and
 //                 points they and the wire format admit: host_checks.hpp; the linearisation commitment: lin_commit.hpp
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
@@ -19,6 +23,7 @@
 #include "g1_host64.hpp"
 #include "launch.hpp"
 #include "ntt_plan.hpp"
+#include "prove_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -189,8 +194,8 @@ struct typlonk_ctx {
     // 0.419 -> 0.464 ms per MSM -- so the switch sits below the shard size; from 2^19 on the chain is never worse and
     // 2^20 needs it.  -1 = by term count (MSM_CHAIN_MIN_TERMS), 0 / 1 = TYPLONK_MSM_CHAIN.
     int msm_chain = -1;
-    tyh::Fr* eval_slots_host = nullptr;  // pinned, device-visible result slots: 16 (prover_ops_tmp), 16 per proof of a wave
-    size_t eval_slots_cap = 0;           // (typlonk_prove_batch grows them)
+    tyh::Fr* eval_slots_host = nullptr;  // pinned, device-visible result slots: PROVE_SLOTS per proof in flight
+    size_t eval_slots_cap = 0;           // (prover_workspaces grows them)
     int msm_chunks = 0;            // chunks of a stand-alone MSM (0 = choose by length)
     int msm_lanes = 0;             // lanes per bucket of the accumulation (0 = choose by bucket load)
     bool msm_scatter_staged = true;  // TYPLONK_MSM_SCATTER=direct: level 1 of the bucket sort writes every entry straight to global
@@ -201,7 +206,7 @@ struct typlonk_ctx {
     tyh::DevBuf wc_ws, wc_stage;   // typlonk_witness_check: masks, counts and lists of a launch; the host form's staged columns
     tyh::DevBuf eval_ws;           // typlonk_poly_eval_dev: points, results and chunk partials (poly_eval.hip)
     tyh::DevBuf batch_tab;         // typlonk_prove_batch: per-proof scalars and item tables of a wave (device copy of batch_host)
-    void* batch_host = nullptr;    // pinned staging of batch_tab (PROVE_BATCH_TAB_BYTES)
+    void* batch_host = nullptr;    // pinned staging of batch_tab (PbTables, prove_plan.hpp)
     bool prover_busy = false;  // one proof in flight per context (the arena above is shared)
     int prover_rounds_active = 0;  // > 0 while a typlonk_prover_round* call is running (ProverRound)
     std::map<std::string, tyh::Table> tables;
@@ -366,7 +371,6 @@ struct WaitAll {
 void lin_zeta_terms(const Fr& zeta, uint32_t log_n, Fr* zn, Fr* zh, Fr* l0z);
 // r = sum_k scalar[k] * poly_k + constant, the ten polynomials in this order: q_l q_r q_o q_m q_c, Z, sigma_2, t_lo, t_mid,
 // t_hi.  ev[0..4] = a, b, c, Z at zeta (Z(zeta) unused) and Z at zeta w; s0, s1 = sigma_0, sigma_1 at zeta; pi_z = PI(zeta).
-constexpr int LIN_TERMS = 10;
 void lin_scalars(const Fr* ev, const Fr& s0, const Fr& s1, const Fr& pi_z, const Fr& beta, const Fr& gamma, const Fr (&k)[3],
                  const Fr& alpha, const Fr& zeta, const Fr& zn, const Fr& zh, const Fr& l0z, Fr* scalar /* LIN_TERMS */, Fr* constant);
 
@@ -383,6 +387,9 @@ TY_HD void lin_polys(const Fr* coef, const Fr* z, const Fr* t, uint64_t n, const
 // The quotient's coset generator: Fr's multiplicative generator 7 (7^(4n) != 1, so X^n - 1 never vanishes on g H_4n), as
 // the limbs the transforms take; g_out: the same as an Fr.
 const uint64_t* coset_g(Fr* g_out = nullptr);
+// THE sizing site of a prover call: every workspace the plan names grown to its size (grow-only: the call drains the device and
+// discards contents when it must re-allocate, so it comes before anything is queued), the pinned slots and a wave's staging
+int prover_workspaces(typlonk_ctx* ctx, const ProvePlan& plan);
 // The quotient's domain g H_4n for n = 2^log_n: x_i = g w_{4n}^i = g * w_lo[i & (2^w_h - 1)] * w_hi[i >> w_h] (n_hi entries of
 // w_hi; a caller folds g and what else it has per call into a scaled copy), and X^n - 1 there, which takes only the four
 // values g^n iota^k - 1 (iota = w_{4n}^n, k = i mod 4): their inverses.
@@ -397,23 +404,13 @@ struct QuotientDomain {
 };
 int quotient_domain(typlonk_ctx* ctx, uint32_t log_n, QuotientDomain* d);
 
-// Round 3's openings and evaluations of one proof.  Where each result lands (a pinned slot per proof) depends on the proof
-// shape: the compact shape keeps its seven evaluations in the proof's order.  (sig0, sig1: CircuitEntry::coef's sigma_0 and
-// sigma_1, which the compact shape's documents count from 1.)  r(zeta) and F come after these and are not part of the list.
-struct Round3Slots {
-    int wire;   // a, b, c at zeta: wire + i
-    int z, sig0, sig1;
-    int pi;     // PI(zeta), for the linearisation only
-    int zw;     // Z at zeta w
-    int count;  // slots to fetch
-};
-constexpr Round3Slots REF_SLOTS{0, 3, 4, 5, 6, 8, 9};
-constexpr Round3Slots COMPACT_SLOTS{0, 3, 5, 6, 7, 4, 8};
+// Round 3's openings and evaluations of one proof; where each result lands (a pinned slot per proof) depends on the proof
+// shape: Round3Slots, prove_plan.hpp.  r(zeta) and F come after these and are not part of the list.
 struct Round3Polys {
-    const Fr* co[3];
+    const Fr* co;     // a, b, c: n apart (PR_CO)
     const Fr* z;
     const Fr* pi;     // null: the zero polynomial
-    Fr* const* q;     // the proof's witness polynomials q[0..4]
+    Fr* q;            // the proof's witness polynomials, n apart (PR_Q; roles: ProveQ)
     const Fr* coef;   // CircuitEntry::coef
     uint64_t n;
 };
@@ -421,12 +418,12 @@ struct Round3Polys {
 // opened at zeta one by one (the reference shape's six openings); Z at zeta w always has its quotient.
 template <class Emit>
 void round3_openings(const Round3Slots& s, bool with_quotients, const Round3Polys& p, Emit emit) {
-    for (int i = 0; i < 3; ++i) emit(p.co[i], with_quotients ? p.q[i] : nullptr, s.wire + i, 0);
-    emit(p.z, with_quotients ? p.q[3] : nullptr, s.z, 0);
+    for (int i = 0; i < 3; ++i) emit(p.co + i * p.n, with_quotients ? p.q + (Q_WIT_A + i) * p.n : nullptr, s.wire + i, 0);
+    emit(p.z, with_quotients ? p.q + Q_WIT_Z * p.n : nullptr, s.z, 0);
     emit(p.coef + 5 * p.n, nullptr, s.sig0, 0);
     emit(p.coef + 6 * p.n, nullptr, s.sig1, 0);
     if (p.pi) emit(p.pi, nullptr, s.pi, 0);
-    emit(p.z, p.q[4], s.zw, 1);
+    emit(p.z, p.q + Q_WIT_ZW * p.n, s.zw, 1);
 }
 
 // ---- prover.hip: the tail typlonk_circuit_load and typlonk_circuit_compile share ------------------------------------------

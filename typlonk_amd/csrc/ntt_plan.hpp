@@ -107,8 +107,10 @@ inline std::string ntt_key(const NttTableReq& r, const std::string& shift_hex) {
 }
 
 // the two halves of a two-level pair over exponents < 2^log_len (r: everything but kind, n, base_sqr and the lo half's scale)
+// (the split: the lo half holds 2^h entries, the hi half 2^(log_len - h))
+constexpr uint32_t ntt_pair_lo_log(uint32_t log_len) { return (log_len + 1) / 2; }
 inline void ntt_push_pair(std::vector<NttTableReq>& t, NttTableReq r, uint32_t log_len) {
-    const uint32_t h = (log_len + 1) / 2;
+    const uint32_t h = ntt_pair_lo_log(log_len);
     NttTableReq lo = r, hi = r;
     lo.kind = NTT_PAIR_LO;
     lo.n = 1ull << h;

@@ -24,48 +24,10 @@ using namespace tyh;
 
 namespace {
 
-constexpr uint32_t PB_MAX = 64;              // proofs per wave (the cap of typlonk.h)
-constexpr uint64_t PB_ROWS = 1ull << 22;     // and at most this many rows of all proofs of a wave together
-constexpr uint32_t PB_ITEMS = 8;             // round 3's openings / evaluations per proof
+// (the wave size, the item count per proof and every table of a wave: prove_plan.hpp)
 constexpr uint32_t PB_QGROUP = 4;            // proofs one thread of the quotient kernel evaluates per point
 constexpr uint32_t PB_FGROUP = 4;            // proofs one thread of the compact shape's fold kernel combines per coefficient
-constexpr uint32_t PB_SLOTS = 16;            // pinned result slots per proof: round 3's (Round3Slots, host.hpp), then
-constexpr uint32_t PB_SLOT_F = 8, PB_SLOT_R = 9;   // F(zeta) of the compact shape (not read) and r(zeta)
-// per-proof arena of a wave, in units of n Fr: ev[3] co[3] pi z t(4) q[6] r | ext a b c Z PI (5 x 4)
-constexpr uint64_t PB_EV = 0, PB_CO = 3, PB_PI = 6, PB_Z = 7, PB_T = 8, PB_Q = 12, PB_R = 18, PB_EXT = 19, PB_STRIDE = 39;
-
-struct PbGp {          // round 2
-    Fr beta, gamma, kbeta[3];
-};
-struct PbQuot {        // round 3, quotient
-    Fr alpha, alpha2, beta, gamma;
-    uint32_t has_pi, pad[7];
-};
-struct PbLin {         // round 3, linearisation
-    Fr scalar[LIN_TERMS];
-    Fr constant;
-};
-struct PbFold {        // round 3 of the compact shape: r's terms, then F = a + v b + ... with vpow[j] = v^(j + 1)
-    PbLin lin;
-    Fr vpow[6];
-};
-struct PbItem {        // one opening (q != null) or evaluation at zpow[zi]
-    const Fr* c;
-    Fr* q;
-    Fr* y;
-    uint64_t zi;
-};
-// every table of a wave, staged in pinned memory (ctx->batch_host) and copied to ctx->batch_tab; each part is written once per
-// wave and copied once, so no host write can overtake a copy still in flight
-struct PbTables {
-    PbGp gp[PB_MAX];
-    PbQuot quot[PB_MAX];
-    PbLin lin[PB_MAX];
-    PbItem item[PB_MAX * PB_ITEMS];
-    PbItem ritem[2 * PB_MAX];   // r's opening; the compact shape: F's opening and r's evaluation
-    PbFold fold[PB_MAX];
-    Fr zpow[2 * PB_MAX][32];   // zeta_p^(2^k) at 2p, (zeta_p w)^(2^k) at 2p + 1
-};
+static_assert(PSCAN_PER_BLOCK == PROVE_SCAN_BLOCK, "the plan sizes the scans' carries");
 
 // ---- round 2: the grand product of every proof of the wave (plonk_ops.hip's kernels with a proof index) ---------------------
 struct PbGpArgs {
@@ -275,14 +237,16 @@ struct Wave {
     const CircuitEntry* ce;
     uint32_t log_n;
     uint64_t n;
-    Fr* mem;          // proof p's arena: mem + p * PB_STRIDE * n
+    ProveArena mem;   // proof p's arena: regions, stride and the roles of q in prove_plan.hpp
     PbTables* host;   // pinned staging
     PbTables* dev;
-    Fr* slots;        // PB_SLOTS per proof
+    Fr* slots;        // PROVE_SLOTS per proof
+    Fr* carries;      // of the openings: nblk per item of a launch (ops_tmp, sized for PB_ITEMS items per proof)
     Fr k[3];
     bool has_pi[PB_MAX];   // of the running wave (wave_rounds12)
     const typlonk_vk* vk = nullptr;   // the compact shape's statement (without [s]G2)
-    Fr* at(uint32_t p, uint64_t off) const { return mem + ((uint64_t)p * PB_STRIDE + off) * n; }
+    Fr* at(uint32_t p, ProveRegion r, uint64_t i = 0) const { return mem.at(p, r, i); }
+    Fr* slot(uint32_t p, int i = 0) const { return slots + (uint64_t)p * PROVE_SLOTS + i; }
 };
 
 // copy one part of the staged tables to the device, stream-ordered
@@ -298,9 +262,9 @@ template <class Script>
 int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typename Script::Proof* out, std::vector<Script>& tr) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
-    const uint64_t n = w.n, n4 = 4 * n;
+    const uint64_t n = w.n;
     const uint32_t log_n = w.log_n, log4 = log_n + 2;
-    const uint64_t stride = PB_STRIDE * n;
+    const uint64_t stride = w.mem.stride_elems();
     const uint64_t* g_limbs = coset_g();
     int rc = TYPLONK_OK;
     bool* has_pi = w.has_pi;
@@ -312,13 +276,13 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
     std::vector<const Fr*> ext_src;
     for (uint32_t p = 0; p < G && !rc; ++p) {
         for (int i = 0; i < 3 && !rc; ++i) {
-            rc = hip_rc(ctx, column_to_device(w.at(p, PB_EV + i), in.column(first + p, i, n), n, s));
-            if (!rc) rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PB_CO + i), w.at(p, PB_EV + i), n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
-            co.push_back(w.at(p, PB_CO + i));
+            rc = hip_rc(ctx, column_to_device(w.at(p, PR_EV, i), in.column(first + p, i, n), n, s));
+            if (!rc) rc = hip_rc(ctx, hipMemcpyAsync(w.at(p, PR_CO, i), w.at(p, PR_EV, i), n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+            co.push_back(w.at(p, PR_CO, i));
         }
         if (!rc && has_pi[p]) {   // (the compact shape reads pi_len rows; the rest are zero)
-            rc = hip_rc(ctx, column_to_device(w.at(p, PB_PI), in.pi(first + p, n), n, s));
-            co.push_back(w.at(p, PB_PI));
+            rc = hip_rc(ctx, column_to_device(w.at(p, PR_PI), in.pi(first + p, n), n, s));
+            co.push_back(w.at(p, PR_PI));
         }
     }
     if (!rc) rc = ntt_run_batch(ctx, co.data(), co.size(), log_n, 1, nullptr, /*sync=*/false);   // proof.rs:50, 105-106
@@ -329,8 +293,8 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
     for (uint32_t p = 0; p < G; ++p)
         for (int k = 0; k < 5; ++k) {
             if (k == 3 || (k == 4 && !has_pi[p])) continue;   // (Z is extended in round 2)
-            ext.push_back(w.at(p, PB_EXT) + k * n4);
-            ext_src.push_back(k < 3 ? w.at(p, PB_CO + k) : w.at(p, PB_PI));
+            ext.push_back(w.at(p, PR_EXT, 4 * k));
+            ext_src.push_back(k < 3 ? w.at(p, PR_CO, k) : w.at(p, PR_PI));
         }
     rc = ntt_run_batch(ctx, ext.data(), ext.size(), log4, 0, g_limbs, /*sync=*/false, ext_src.data(), n);
     {
@@ -338,7 +302,7 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
         q.fence = ctx->batch_fence;
         for (uint32_t p = 0; p < G && !rc; ++p)
             for (int i = 0; i < 3 && !rc; ++i)
-                rc = q.submit(w.at(p, PB_CO + i), n, out[first + p].commit_xy[i], out[first + p].commit_inf + i);   // :107-110
+                rc = q.submit(w.at(p, PR_CO, i), n, out[first + p].commit_xy[i], out[first + p].commit_inf + i);   // :107-110
         const int r = q.wait_all();
         if (!rc) rc = r;
     }
@@ -356,15 +320,18 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
     if ((rc = upload(w, w.host->gp, G * sizeof(PbGp)))) return rc;
     {
         PbGpArgs a{};
-        a.ev = w.at(0, PB_EV);
+        a.ev = w.at(0, PR_EV);
         a.sigma = w.ce->sig_ev;
-        a.tmp = w.at(0, PB_T);
-        a.blk = w.at(0, PB_Q);
-        a.z = w.at(0, PB_Z);
+        // the scratch is laid over t and the head of q, not written before round 3 (gp_scratch_wave; the kernels index the
+        // four vectors from a.tmp and the two carry runs and the inverse from a.blk)
+        const GpScratch L = gp_scratch_wave(n);
+        a.tmp = w.mem.mem + L.num;
+        a.blk = w.mem.mem + L.carries;
+        a.z = w.at(0, PR_Z);
         a.gp = w.dev->gp;
         a.n = n;
         a.stride = stride;
-        a.nblk = (uint32_t)((n + PSCAN_PER_BLOCK - 1) / PSCAN_PER_BLOCK);
+        a.nblk = (uint32_t)prove_nblk(n);
         if ((rc = domain_twiddles(ctx, std::max<uint32_t>(log_n, 1), &a.w_lo, &a.w_hi, &a.w_h))) return rc;
         const unsigned gx = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(pb_gp_terms_kernel, dim3(gx, G), dim3(256), 0, s, a);
@@ -379,16 +346,16 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
         std::vector<Fr*> zs(G), zext(G);
         std::vector<const Fr*> zsrc(G);
         for (uint32_t p = 0; p < G; ++p) {
-            zs[p] = w.at(p, PB_Z);
+            zs[p] = w.at(p, PR_Z);
             zsrc[p] = zs[p];
-            zext[p] = w.at(p, PB_EXT) + 3 * n4;
+            zext[p] = w.at(p, PR_EXT, 4 * 3);
         }
         if ((rc = ntt_run_batch(ctx, zs.data(), G, log_n, 1, nullptr, /*sync=*/false))) return rc;
         HIPCHK(hipEventRecord(ctx->batch_fence, s));
         rc = ntt_run_batch(ctx, zext.data(), G, log4, 0, g_limbs, /*sync=*/false, zsrc.data(), n);   // beside the commitments
         MsmQueue q(ctx, w.srs, /*first_lane=*/1);
         q.fence = ctx->batch_fence;
-        for (uint32_t p = 0; p < G && !rc; ++p) rc = q.submit(w.at(p, PB_Z), n, out[first + p].z_xy, &out[first + p].z_inf);
+        for (uint32_t p = 0; p < G && !rc; ++p) rc = q.submit(w.at(p, PR_Z), n, out[first + p].z_xy, &out[first + p].z_inf);
         const int r = q.wait_all();
         if (!rc) rc = r;
     }
@@ -409,14 +376,10 @@ int wave_rounds12(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typena
 // round 3's openings and evaluations of every proof of the wave (round3_openings) into the staged item table; returns how many
 uint32_t stage_round3_items(Wave& w, uint32_t G, const Round3Slots& slots, bool with_quotients) {
     uint32_t nitems = 0;
-    Fr* q[5];
     for (uint32_t p = 0; p < G; ++p) {
-        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
-        for (int i = 0; i < 5; ++i) q[i] = w.at(p, PB_Q + i);
-        const Round3Polys polys{{w.at(p, PB_CO), w.at(p, PB_CO + 1), w.at(p, PB_CO + 2)}, w.at(p, PB_Z),
-                                w.has_pi[p] ? w.at(p, PB_PI) : nullptr, q, w.ce->coef, w.n};
+        const Round3Polys polys{w.at(p, PR_CO), w.at(p, PR_Z), w.has_pi[p] ? w.at(p, PR_PI) : nullptr, w.at(p, PR_Q), w.ce->coef, w.n};
         round3_openings(slots, with_quotients, polys, [&](const Fr* c, Fr* quot, int slot, uint32_t point) {
-            w.host->item[nitems++] = PbItem{c, quot, y + slot, 2ull * p + point};
+            w.host->item[nitems++] = PbItem{c, quot, w.slot(p, slot), 2ull * p + point};
         });
     }
     return nitems;
@@ -435,7 +398,7 @@ void stage_zpow(Wave& w, uint32_t p, const Fr& zeta) {
 }
 
 // The quotient of every proof of the wave (proof.rs:139-145): the staged table w.host->quot to the device, the pointwise kernel
-// and one batched inverse 4n transform; t_lo, t_mid, t_hi of proof p are then the first 3n coefficients at PB_T.
+// and one batched inverse 4n transform; t_lo, t_mid, t_hi of proof p are then the first 3n coefficients of its t.
 int wave_quotient(Wave& w, uint32_t G) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
@@ -447,16 +410,16 @@ int wave_quotient(Wave& w, uint32_t G) {
     QuotientDomain d;
     if ((rc = quotient_domain(ctx, log_n, &d))) return rc;
     const uint64_t* g_limbs = d.g_limbs;
-    a.ext = w.at(0, PB_EXT);
+    a.ext = w.at(0, PR_EXT);
     a.cext = w.ce->ext;
-    a.t = w.at(0, PB_T);
+    a.t = w.at(0, PR_T);
     a.pq = w.dev->quot;
     a.n4 = n4;
-    a.stride = PB_STRIDE * n;
+    a.stride = w.mem.stride_elems();
     a.count = G;
     a.w_lo = d.w_lo;
     a.w_h = d.w_h;
-    if ((rc = ensure(ctx, ctx->quot_tab, d.n_hi * sizeof(Fr)))) return rc;
+    if (d.n_hi * sizeof(Fr) > ctx->quot_tab.cap) return fail(ctx, TYPLONK_ERR_INTERNAL, "quot_tab is smaller than the 4n domain's upper level");
     launch_fr_scale(d.w_hi, d.n_hi, d.g, (Fr*)ctx->quot_tab.p, s);   // (beta is per proof: the kernel multiplies)
     a.gx_hi = (const Fr*)ctx->quot_tab.p;
     for (int k = 0; k < 4; ++k) a.zh_inv[k] = d.zh_inv[k];
@@ -465,14 +428,14 @@ int wave_quotient(Wave& w, uint32_t G) {
     hipLaunchKernelGGL(pb_quotient_kernel, dim3((unsigned)((n4 + 255) / 256), (G + PB_QGROUP - 1) / PB_QGROUP), dim3(256), 0, s, a);
     if ((rc = hip_rc(ctx, hipGetLastError()))) return rc;
     std::vector<Fr*> ts(G);
-    for (uint32_t p = 0; p < G; ++p) ts[p] = w.at(p, PB_T);
+    for (uint32_t p = 0; p < G; ++p) ts[p] = w.at(p, PR_T);
     return ntt_run_batch(ctx, ts.data(), G, log4, 1, g_limbs, /*sync=*/false);
 }
 
 int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_proof* out, int* status) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
-    const uint64_t n = w.n, stride = PB_STRIDE * n;
+    const uint64_t n = w.n, stride = w.mem.stride_elems();
     const uint32_t log_n = w.log_n;
     const bool* has_pi = w.has_pi;
     auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
@@ -487,7 +450,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     }
 
     // ---- round 3: openings (:147-163), quotient (:139-145), linearisation (:165-175), nine commitments per proof (:181) ----
-    Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
+    Fr* blocks = w.carries;
     const uint32_t nitems = stage_round3_items(w, G, REF_SLOTS, /*with_quotients=*/true);
     if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
     if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
@@ -499,7 +462,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     for (uint32_t p = 0; p < G; ++p) lin_zeta_terms(zeta[p], log_n, &zn[p], &zh[p], &l0z[p]);
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p) {
-        const Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        const Fr* y = w.slot(p);
         constexpr Round3Slots S = REF_SLOTS;
         const Fr ev[5] = {y[S.wire], y[S.wire + 1], y[S.wire + 2], y[S.z], y[S.zw]};
         const Fr pi_z = has_pi[p] ? y[S.pi] : Fr::zero();
@@ -508,12 +471,12 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
                     l0z[p], l.scalar, &l.constant);
         typlonk_proof_tail& t = out[first + p].tail;
         for (int i = 0; i < 5; ++i) memcpy(t.evals[i], ev[i].v, 32);
-        w.host->ritem[p] = PbItem{w.at(p, PB_R), w.at(p, PB_Q + 5), w.slots + (uint64_t)p * PB_SLOTS + PB_SLOT_R, 2ull * p};
+        w.host->ritem[p] = PbItem{w.at(p, PR_R), w.at(p, PR_Q, Q_WIT_R), w.slot(p, S.r), 2ull * p};
     }
     if ((rc = upload(w, w.host->lin, G * sizeof(PbLin)))) return rc;
     if ((rc = upload(w, w.host->ritem, G * sizeof(PbItem)))) return rc;
     {
-        PbLinArgs a{w.ce->coef, w.at(0, PB_Z), w.at(0, PB_T), w.at(0, PB_R), w.dev->lin, n, stride};
+        PbLinArgs a{w.ce->coef, w.at(0, PR_Z), w.at(0, PR_T), w.at(0, PR_R), w.dev->lin, n, stride};
         hipLaunchKernelGGL(pb_lincomb_kernel, dim3((unsigned)((n + 255) / 256), G), dim3(256), 0, s, a);
         if ((rc = lasterr())) return rc;
     }
@@ -526,8 +489,9 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
         const size_t m[9] = {n - 1, n - 1, n - 1, n - 1, n - 1, n - 1, n, n, n > 3 ? n - 3 : 0};
         for (uint32_t p = 0; p < G && !rc; ++p) {
             typlonk_proof_tail& t = out[first + p].tail;
-            const Fr* polys[9] = {w.at(p, PB_Q), w.at(p, PB_Q + 1), w.at(p, PB_Q + 2), w.at(p, PB_Q + 3), w.at(p, PB_Q + 4),
-                                  w.at(p, PB_Q + 5), w.at(p, PB_T), w.at(p, PB_T + 1), w.at(p, PB_T + 2)};
+            // (the six witnesses in q's order, Q_WIT_A .. Q_WIT_R, as the proof lists them)
+            const Fr* polys[9] = {w.at(p, PR_Q, 0), w.at(p, PR_Q, 1), w.at(p, PR_Q, 2), w.at(p, PR_Q, 3), w.at(p, PR_Q, 4),
+                                  w.at(p, PR_Q, 5), w.at(p, PR_T), w.at(p, PR_T, 1), w.at(p, PR_T, 2)};
             for (int k = 0; k < 9 && !rc; ++k)
                 rc = k < 6 ? q.submit(polys[k], m[k], t.w_xy[k], t.w_inf + k) : q.submit(polys[k], m[k], t.t_xy[k - 6], t.t_inf + k - 6);
         }
@@ -537,7 +501,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p) {
-        const Fr rz = w.slots[(uint64_t)p * PB_SLOTS + PB_SLOT_R];
+        const Fr rz = *w.slot(p, REF_SLOTS.r);
         memcpy(out[first + p].tail.evals[5], rz.v, 32);
         // r(zeta) != 0: the witness does not satisfy the circuit (proof.rs:234-235), as typlonk_prove reports it
         status[first + p] = rz.is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
@@ -550,7 +514,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
 int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_proof_compact* out, int* status) {
     typlonk_ctx* ctx = w.ctx;
     hipStream_t s = ctx->stream;
-    const uint64_t n = w.n, stride = PB_STRIDE * n;
+    const uint64_t n = w.n, stride = w.mem.stride_elems();
     const uint32_t log_n = w.log_n;
     const bool* has_pi = w.has_pi;
     auto lasterr = [&]() { return hip_rc(ctx, hipGetLastError()); };
@@ -589,7 +553,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
         const size_t m[3] = {n, n, n > 3 ? n - 3 : 0};
         for (uint32_t p = 0; p < G && !rc; ++p)
             for (int k = 0; k < 3 && !rc; ++k)
-                rc = q.submit(w.at(p, PB_T + k), m[k], out[first + p].t_xy[k], out[first + p].t_inf + k);
+                rc = q.submit(w.at(p, PR_T, k), m[k], out[first + p].t_xy[k], out[first + p].t_inf + k);
         const int r = q.wait_all();
         if (!rc) rc = r;
     }
@@ -601,7 +565,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     }
     // ---- a, b, c, Z, sigma_1, sigma_2 (and PI) at zeta_p, Z at zeta_p w with its quotient (COMPACT_SLOTS: the first seven slots
     // are the proof's evaluations in order); one wait for the whole wave ----
-    Fr* blocks = (Fr*)ctx->ops_tmp.p;   // (sized by prove_batch_impl for PB_ITEMS items per proof)
+    Fr* blocks = w.carries;
     const uint32_t nitems = stage_round3_items(w, G, COMPACT_SLOTS, /*with_quotients=*/false);
     if ((rc = upload(w, w.host->item, nitems * sizeof(PbItem)))) return rc;
     if ((rc = upload(w, w.host->zpow, 2 * G * sizeof(w.host->zpow[0])))) return rc;
@@ -611,7 +575,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     for (uint32_t p = 0; p < G; ++p) lin_zeta_terms(zeta[p], log_n, &zn[p], &zh[p], &l0z[p]);   // while the kernels run
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p) {
-        Fr* y = w.slots + (uint64_t)p * PB_SLOTS;
+        Fr* y = w.slot(p);
         typlonk_proof_compact& o = out[first + p];
         constexpr Round3Slots S = COMPACT_SLOTS;
         for (int i = 0; i < 7; ++i) memcpy(o.evals[i], y[i].v, 32);
@@ -625,14 +589,14 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
                     l0z[p], f.lin.scalar, &f.lin.constant);
         f.vpow[0] = v;
         for (int j = 1; j < 6; ++j) f.vpow[j] = fe_mul(f.vpow[j - 1], v);
-        // F (in q[1]) opened at zeta with its witness into q[0]; r evaluated there for the status (q[0..3] are free in this shape)
-        w.host->ritem[2 * p] = PbItem{w.at(p, PB_Q + 1), w.at(p, PB_Q), y + PB_SLOT_F, 2ull * p};
-        w.host->ritem[2 * p + 1] = PbItem{w.at(p, PB_R), nullptr, y + PB_SLOT_R, 2ull * p};
+        // F opened at zeta with its witness (their places in q: ProveQ); r evaluated there for the status
+        w.host->ritem[2 * p] = PbItem{w.at(p, PR_Q, Q_COMPACT_F), w.at(p, PR_Q, Q_COMPACT_WIT), y + S.f, 2ull * p};
+        w.host->ritem[2 * p + 1] = PbItem{w.at(p, PR_R), nullptr, y + S.r, 2ull * p};
     }
     if ((rc = upload(w, w.host->fold, G * sizeof(PbFold)))) return rc;
     if ((rc = upload(w, w.host->ritem, 2 * G * sizeof(PbItem)))) return rc;
     {
-        PbFoldArgs a{w.ce->coef, w.at(0, PB_CO), w.at(0, PB_Z), w.at(0, PB_T), w.at(0, PB_R), w.at(0, PB_Q + 1), w.dev->fold,
+        PbFoldArgs a{w.ce->coef, w.at(0, PR_CO), w.at(0, PR_Z), w.at(0, PR_T), w.at(0, PR_R), w.at(0, PR_Q, Q_COMPACT_F), w.dev->fold,
                      n, stride, G};
         hipLaunchKernelGGL(pb_fold_kernel, dim3((unsigned)((n + 255) / 256), (G + PB_FGROUP - 1) / PB_FGROUP), dim3(256), 0, s, a);
         if ((rc = lasterr())) return rc;
@@ -646,8 +610,8 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
         q.fence = ctx->batch_fence;
         for (uint32_t p = 0; p < G && !rc; ++p) {
             typlonk_proof_compact& o = out[first + p];
-            rc = q.submit(w.at(p, PB_Q), n - 1, o.w_xy[0], o.w_inf + 0);
-            if (!rc) rc = q.submit(w.at(p, PB_Q + 4), n - 1, o.w_xy[1], o.w_inf + 1);
+            rc = q.submit(w.at(p, PR_Q, Q_COMPACT_WIT), n - 1, o.w_xy[0], o.w_inf + 0);
+            if (!rc) rc = q.submit(w.at(p, PR_Q, Q_WIT_ZW), n - 1, o.w_xy[1], o.w_inf + 1);
         }
         const int r = q.wait_all();
         if (!rc) rc = r;
@@ -655,7 +619,7 @@ int run_wave(Wave& w, const ColumnsOf& in, size_t first, uint32_t G, typlonk_pro
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     for (uint32_t p = 0; p < G; ++p)   // r(zeta) != 0: the witness does not satisfy the circuit, as typlonk_prove_compact reports it
-        status[first + p] = w.slots[(uint64_t)p * PB_SLOTS + PB_SLOT_R].is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
+        status[first + p] = w.slot(p, COMPACT_SLOTS.r)->is_zero() ? TYPLONK_OK : TYPLONK_ERR_UNSATISFIED;
     return TYPLONK_OK;
 }
 
@@ -701,21 +665,11 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
         const int vrc = circuit_vk_fill(ctx, srs_id, circuit_id, cosets, &vk);
         if (vrc) return vrc;
     }
-    const uint32_t G = (uint32_t)std::min<uint64_t>({(uint64_t)count, PB_MAX, std::max<uint64_t>(1, PB_ROWS >> log_n)});
-    // the wave's workspaces: the per-proof arenas, the openings' carries, the result slots, the tables
-    int rc = ensure(ctx, ctx->prover_mem, (size_t)G * PB_STRIDE * n * sizeof(Fr));
-    if (!rc) rc = ensure(ctx, ctx->ops_tmp, (size_t)G * PB_ITEMS * ((n + 2047) / 2048) * sizeof(Fr));
-    if (!rc) rc = ensure(ctx, ctx->batch_tab, sizeof(PbTables));
+    // the wave's workspaces: the per-proof arenas, the openings' carries, the quotient's table, the result slots, the tables
+    const ProvePlan plan = prove_plan(log_n, count, PROVE_WAVE, /*cached=*/true);
+    const uint32_t G = plan.G;
+    int rc = prover_workspaces(ctx, plan);
     if (rc) return rc;
-    if (ctx->eval_slots_cap < (size_t)G * PB_SLOTS) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->eval_slots_host) HIPCHK(hipHostFree(ctx->eval_slots_host));
-        ctx->eval_slots_host = nullptr;
-        ctx->eval_slots_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, (size_t)G * PB_SLOTS * sizeof(Fr)));
-        ctx->eval_slots_cap = (size_t)G * PB_SLOTS;
-    }
-    if (!ctx->batch_host) HIPCHK(hipHostMalloc(&ctx->batch_host, sizeof(PbTables)));
     ctx->prover_busy = true;
     BusyGuard busy{ctx};
     ProfilingOff prof_off(ctx);
@@ -726,7 +680,8 @@ int prove_batch_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, con
     w.ce = &ci->second;
     w.log_n = log_n;
     w.n = n;
-    w.mem = (Fr*)ctx->prover_mem.p;
+    w.mem = ProveArena{(Fr*)ctx->prover_mem.p, n, plan.stride};
+    w.carries = (Fr*)ctx->ops_tmp.p;
     w.host = (PbTables*)ctx->batch_host;
     w.dev = (PbTables*)ctx->batch_tab.p;
     w.slots = ctx->eval_slots_host;

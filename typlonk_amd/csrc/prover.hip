@@ -17,6 +17,23 @@ const uint64_t* coset_g(Fr* g_out) {
     if (g_out) *g_out = g;
     return limbs;
 }
+int prover_workspaces(typlonk_ctx* ctx, const ProvePlan& plan) {
+    const std::pair<DevBuf*, size_t> bufs[] = {{&ctx->prover_mem, plan.prover_mem}, {&ctx->ops_tmp, plan.ops_tmp},
+                                               {&ctx->quot_ext, plan.quot_ext}, {&ctx->quot_tab, plan.quot_tab},
+                                               {&ctx->batch_tab, plan.batch_tab}};
+    for (const auto& b : bufs)
+        if (const int rc = ensure(ctx, *b.first, b.second)) return rc;
+    if (ctx->eval_slots_cap < plan.slots) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->eval_slots_host) HIPCHK(hipHostFree(ctx->eval_slots_host));
+        ctx->eval_slots_host = nullptr;
+        ctx->eval_slots_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, plan.slots * sizeof(Fr)));
+        ctx->eval_slots_cap = plan.slots;
+    }
+    if (plan.batch_tab && !ctx->batch_host) HIPCHK(hipHostMalloc(&ctx->batch_host, plan.batch_tab));
+    return TYPLONK_OK;
+}
 int quotient_domain(typlonk_ctx* ctx, uint32_t log_n, QuotientDomain* d) {
     const uint32_t log4 = log_n + 2;
     const Fr w4 = fr_domain_root(log4);
@@ -127,44 +144,64 @@ int typlonk_circuit_free(typlonk_ctx* ctx, uint32_t circuit_id) {
 }
 
 namespace {
-// typlonk_quotient_dev with bit k of `extended` set when ext[k] (k = 0..4: a, b, c, Z, PI) already holds that
-// polynomial's coset evaluations -- the prover session extends them in rounds 1 and 2, beside the commitments
-int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out, uint32_t extended);
+// per-proof inputs first, then (without a cached circuit) the per-circuit ones
+struct QuotientInputs {
+    const typlonk_buf* in[13];
+    const Fr* cached = nullptr;   // the circuit's coset evaluations from the circuit cache
+    bool has_pi = false;          // NULL = zero polynomial (public inputs [0])
+};
+// what the quotient refuses, in this order, before it sizes or queues anything
+int quotient_check(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, const typlonk_buf* t_out, QuotientInputs* qi) {
+    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint64_t n = 1ull << log_n;
+    const typlonk_buf* in[13] = {args->wires[0], args->wires[1], args->wires[2], args->z, args->public_inputs,
+                                 args->selectors[0], args->selectors[1], args->selectors[2], args->selectors[3],
+                                 args->selectors[4], args->sigma[0], args->sigma[1], args->sigma[2]};
+    std::copy(in, in + 13, qi->in);
+    if (args->circuit) {
+        auto it = ctx->circuits.find(args->circuit);
+        if (it == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
+        if (it->second.log_n != log_n) return fail(ctx, TYPLONK_ERR_DOMAIN, "circuit was loaded for another domain size");
+        qi->cached = it->second.ext;
+    }
+    qi->has_pi = args->public_inputs != nullptr;
+    for (int k = 0; k < (qi->cached ? 5 : 13); ++k) {
+        if (k == 4 && !qi->has_pi) continue;
+        if (!in[k] || in[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "quotient input shorter than n");
+    }
+    if (t_out->n < 4 * n) return fail(ctx, TYPLONK_ERR_RANGE, "t_out must hold 4n elements");
+    return TYPLONK_OK;
+}
+// The quotient of checked inputs over ctx->quot_ext and ctx->quot_tab AS SIZED by the caller (prove_plan: quot_ext, quot_tab),
+// stream-ordered.  Bit k of `extended`: ext[k] (k = 0..4: a, b, c, Z, PI) already holds that polynomial's coset evaluations
+// -- the prover session extends them in rounds 1 and 2, beside the commitments
+int quotient_queue(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out, const QuotientInputs& qi,
+                   uint32_t extended);
 }  // namespace
 
 int typlonk_quotient_dev(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out) {
     if (!ctx || !args || !t_out) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
     // a prover session keeps coset evaluations in the context's quotient workspace between its rounds
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is in flight on this context");
-    return quotient_run(ctx, args, log_n, t_out, 0);
+    QuotientInputs qi;
+    int rc = quotient_check(ctx, args, log_n, t_out, &qi);
+    if (rc) return rc;
+    const ProvePlan plan = prove_plan(log_n, 1, PROVE_SESSION, qi.cached != nullptr);
+    if ((rc = ensure(ctx, ctx->quot_ext, plan.quot_ext))) return rc;
+    if ((rc = ensure(ctx, ctx->quot_tab, plan.quot_tab))) return rc;
+    return quotient_queue(ctx, args, log_n, t_out, qi, 0);
 }
 
 namespace {
-int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out, uint32_t extended) {
-    if (log_n < 1 || log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_DOMAIN, "quotient needs 1 <= log_n <= 24");
-    HIPCHK(hipSetDevice(ctx->device));
+int quotient_queue(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t log_n, typlonk_buf* t_out, const QuotientInputs& qi,
+                   uint32_t extended) {
     const uint64_t n = 1ull << log_n, n4 = 4 * n;
     const uint32_t log4 = log_n + 2;
-    // per-proof inputs first, then (without a cached circuit) the per-circuit ones
-    const typlonk_buf* in[13] = {args->wires[0], args->wires[1], args->wires[2], args->z, args->public_inputs,
-                                 args->selectors[0], args->selectors[1], args->selectors[2], args->selectors[3],
-                                 args->selectors[4], args->sigma[0], args->sigma[1], args->sigma[2]};
-    const Fr* cached = nullptr;
-    if (args->circuit) {
-        auto it = ctx->circuits.find(args->circuit);
-        if (it == ctx->circuits.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown circuit id");
-        if (it->second.log_n != log_n) return fail(ctx, TYPLONK_ERR_DOMAIN, "circuit was loaded for another domain size");
-        cached = it->second.ext;
-    }
-    const int n_in = cached ? 5 : 13;
-    const bool has_pi = args->public_inputs != nullptr;  // NULL = zero polynomial (public inputs [0])
-    for (int k = 0; k < n_in; ++k) {
-        if (k == 4 && !has_pi) continue;
-        if (!in[k] || in[k]->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "quotient input shorter than n");
-    }
-    if (t_out->n < n4) return fail(ctx, TYPLONK_ERR_RANGE, "t_out must hold 4n elements");
-    int rc = ensure(ctx, ctx->quot_ext, (size_t)(cached ? 5 : 14) * n4 * sizeof(Fr));
-    if (rc) return rc;
+    const Fr* cached = qi.cached;
+    const bool has_pi = qi.has_pi;
+    const typlonk_buf* const* in = qi.in;
+    int rc = TYPLONK_OK;
     Fr* ext = (Fr*)ctx->quot_ext.p;
     hipStream_t s = ctx->stream;
     ProfilingOff prof_off(ctx);  // stage events are per call
@@ -201,8 +238,8 @@ int quotient_run(typlonk_ctx* ctx, const typlonk_quotient_args* args, uint32_t l
     if ((rc = quotient_domain(ctx, log_n, &d))) return rc;
     qa.w_lo = d.w_lo;
     qa.w_h = d.w_h;
-    if ((rc = ensure(ctx, ctx->quot_tab, d.n_hi * sizeof(Fr)))) return rc;
     memcpy(qa.beta.v, args->beta, 32);
+    if (d.n_hi * sizeof(Fr) > ctx->quot_tab.cap) return fail(ctx, TYPLONK_ERR_INTERNAL, "quot_tab is smaller than the 4n domain's upper level");
     launch_fr_scale(d.w_hi, d.n_hi, fe_mul(qa.beta, d.g), (Fr*)ctx->quot_tab.p, s);   // beta * g folded into the upper level
     qa.bx_hi = (const Fr*)ctx->quot_tab.p;
     for (int k = 0; k < 4; ++k) qa.zh_inv[k] = d.zh_inv[k];
@@ -230,14 +267,11 @@ int typlonk_grand_product_dev(typlonk_ctx* ctx, const typlonk_buf* const wires[3
         if (!wires[i] || !sigma[i] || wires[i]->n < n || sigma[i]->n < n)
             return fail(ctx, TYPLONK_ERR_RANGE, "grand product input shorter than n");
     if (z_evals_out->n < n) return fail(ctx, TYPLONK_ERR_RANGE, "z_evals_out shorter than n");
-    const uint64_t nblk = (n + 2047) / 2048;
-    int rc = ensure(ctx, ctx->ops_tmp, (4 * n + nblk + 8) * sizeof(Fr));
+    const GpScratch L = gp_scratch(n);
+    int rc = ensure(ctx, ctx->ops_tmp, L.end * sizeof(Fr));   // (inside a session: sized in round 1, nothing to grow)
     if (rc) return rc;
-    Fr* num = (Fr*)ctx->ops_tmp.p;
-    Fr* den = num + n;
-    Fr* npre = den + n;
-    Fr* dsuf = npre + n;
-    Fr* blk = dsuf + n;
+    Fr* const base = (Fr*)ctx->ops_tmp.p;
+    Fr *num = base + L.num, *den = base + L.den, *npre = base + L.npre, *dsuf = base + L.dsuf, *blk = base + L.carries;
     hipStream_t s = ctx->stream;
     GrandProductArgs a{};
     for (int i = 0; i < 3; ++i) {
@@ -262,7 +296,7 @@ int typlonk_grand_product_dev(typlonk_ctx* ctx, const typlonk_buf* const wires[3
     HIPCHK(hipGetLastError());
     // S_0 = dsuf[0] = the product of all denominators: inverted ON THE DEVICE (fr_inv.hpp) into the slot behind the carries
     // -- no copy, no wait, no host inversion between the scans and the finish (rounds 1-5 drained the stream here)
-    Fr* inv_total = blk + nblk;
+    Fr* inv_total = base + L.inv;
     launch_fr_inv(dsuf, inv_total, s);
     launch_gp_finish(npre, dsuf, inv_total, n, z_evals_out->d, s);
     HIPCHK(hipGetLastError());
@@ -278,12 +312,11 @@ int typlonk_open_dev(typlonk_ctx* ctx, const typlonk_buf* poly, size_t offset, s
     if (q_out && q_out->n < m - 1) return fail(ctx, TYPLONK_ERR_RANGE, "q_out shorter than m - 1");
     if (q_out && q_out->d == poly->d) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "q_out must not alias poly");
     HIPCHK(hipSetDevice(ctx->device));
-    // one carry per 2048-coefficient workgroup (at least 2048 slots: the layout of m <= 2^22), then the result
-    const size_t nblk = std::max<size_t>((m + 2047) / 2048, 2048);
-    int rc = ensure(ctx, ctx->ops_tmp, (nblk + 8) * sizeof(Fr));
+    const OpenDevScratch L = open_dev_scratch(m);   // one carry per 2048-coefficient workgroup, then the result
+    int rc = ensure(ctx, ctx->ops_tmp, L.end * sizeof(Fr));
     if (rc) return rc;
-    Fr* blocks = (Fr*)ctx->ops_tmp.p;
-    Fr* y_dev = blocks + nblk;
+    Fr* blocks = (Fr*)ctx->ops_tmp.p + L.carries;
+    Fr* y_dev = (Fr*)ctx->ops_tmp.p + L.y;
     Fr zz;
     memcpy(zz.v, z, 32);
     launch_open(poly->d + offset, m, zz, q_out ? q_out->d : nullptr, blocks, y_dev, ctx->stream);
@@ -324,8 +357,8 @@ struct typlonk_prover {
     typlonk_ctx* ctx = nullptr;
     uint32_t srs_id = 0, circuit = 0, log_n = 0;
     uint64_t n = 0;
-    Fr* mem = nullptr;  // one allocation, carved below
-    Fr *ev[3], *co[3], *pi, *z, *t, *q[6], *r;
+    ProveArena mem;     // the proof's arena in ctx->prover_mem (regions and the roles of q: prove_plan.hpp)
+    Fr* at(ProveRegion r, uint64_t i = 0) const { return mem.at(0, r, i); }
     Fr beta, gamma, k[3];
     bool has_pi = true;
     int round = 0;
@@ -346,86 +379,56 @@ int prover_commit_batch(typlonk_prover* p, const Fr* const* polys, const size_t*
 // latency-bound stretches of the MSMs (sort, bucket reduction) instead of sitting on round 3's critical path.
 int prover_extend(typlonk_prover* p, int k, const Fr* coeffs) {
     typlonk_ctx* ctx = p->ctx;
-    const uint64_t n4 = 4 * p->n;
-    int rc = ensure(ctx, ctx->quot_ext, (size_t)5 * n4 * sizeof(Fr));
-    if (rc) return rc;
     const Fr ninv = Fr::one();  // unused: src is never null here
-    rc = quotient_extend(ctx, (Fr*)ctx->quot_ext.p + (uint64_t)k * n4, coeffs, &ninv, p->n, p->log_n + 2);
+    const int rc = quotient_extend(ctx, (Fr*)ctx->quot_ext.p + (uint64_t)k * 4 * p->n, coeffs, &ninv, p->n, p->log_n + 2);
     if (!rc) p->extended |= 1u << k;
     return rc;
 }
-// Scratch of the prover's openings: 8 * max(2048, n / 2048) per-workgroup carries in ops_tmp, and 16 result slots.
+// Scratch of the prover's openings: the carries in ops_tmp (session_open_carries) and the result slots, both sized in round 1.
 // The slots are only ever WRITTEN by kernels (p(z) of an opening) and read by the host, so they live in pinned host memory the
 // kernels store into directly: a fetch is one stream synchronisation, no copy.  (Device slots + hipMemcpyAsync into a stack
 // array -- pageable, so staged by the runtime -- left the GPU idle for ~170 us before the linearisation and ~120 us before
 // round 3's commitments, profiles/r06_prove_timeline.txt 15.50-15.67 and 15.89-16.02 ms.)
-constexpr size_t PROVER_EVAL_BLOCKS = 8 * 2048;   // n <= 2^22
-int prover_ops_tmp(typlonk_prover* p, Fr** blocks, Fr** slots) {
-    typlonk_ctx* ctx = p->ctx;
-    int rc = ensure(ctx, ctx->ops_tmp, std::max<size_t>(PROVER_EVAL_BLOCKS, 8 * ((p->n + 2047) / 2048)) * sizeof(Fr));
-    if (rc) return rc;
-    if (!ctx->eval_slots_host) {
-        HIPCHK(hipHostMalloc((void**)&ctx->eval_slots_host, 16 * sizeof(Fr)));
-        ctx->eval_slots_cap = 16;
-    }
-    *blocks = (Fr*)ctx->ops_tmp.p;
-    *slots = ctx->eval_slots_host;
-    return TYPLONK_OK;
-}
 // open() without waiting: p(z) lands in result slot `slot`, the quotient (if q) in q; stream-ordered
 int prover_open_async(typlonk_prover* p, const Fr* poly, uint64_t m, const Fr& z, Fr* q, int slot) {
-    Fr *blocks, *slots;
-    int rc = prover_ops_tmp(p, &blocks, &slots);
-    if (rc) return rc;
     typlonk_ctx* ctx = p->ctx;
-    launch_open(poly, m, z, q, blocks, slots + slot, ctx->stream);
+    launch_open(poly, m, z, q, (Fr*)ctx->ops_tmp.p, ctx->eval_slots_host + slot, ctx->stream);
     HIPCHK(hipGetLastError());
     return TYPLONK_OK;
 }
-// one synchronisation for `count` result slots
-int prover_fetch(typlonk_prover* p, Fr* out, int count) {
+// one synchronisation for the `count` result slots from `first` on
+int prover_fetch(typlonk_prover* p, Fr* out, int first, int count) {
     typlonk_ctx* ctx = p->ctx;
-    Fr *blocks, *slots;
-    int rc = prover_ops_tmp(p, &blocks, &slots);
-    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    memcpy((void*)out, (const void*)slots, (size_t)count * sizeof(Fr));
+    memcpy((void*)out, (const void*)(ctx->eval_slots_host + first), (size_t)count * sizeof(Fr));
     return TYPLONK_OK;
-}
-int prover_open(typlonk_prover* p, const Fr* poly, uint64_t m, const Fr& z, Fr* q, Fr* y) {
-    int rc = prover_open_async(p, poly, m, z, q, 0);
-    if (rc) return rc;
-    return prover_fetch(p, y, 1);
 }
 // round 3's openings and evaluations (round3_openings) at ze and zw = ze * w in three launches, the results into `slots`' places
 int prover_open_round3(typlonk_prover* p, const CircuitEntry& ce, const Round3Slots& slots, bool with_quotients, const Fr& ze,
                        const Fr& zw) {
-    Fr *blocks = nullptr, *res = nullptr;
-    const int rc = prover_ops_tmp(p, &blocks, &res);
-    if (rc) return rc;
-    const Fr* polys[8];
-    Fr* quots[8];
-    Fr* ys[8];
-    uint8_t zsel[8];
+    const Fr* polys[PB_ITEMS];
+    Fr* quots[PB_ITEMS];
+    Fr* ys[PB_ITEMS];
+    uint8_t zsel[PB_ITEMS];
     uint32_t cnt = 0;
-    const Round3Polys in{{p->co[0], p->co[1], p->co[2]}, p->z, p->has_pi ? p->pi : nullptr, p->q, ce.coef, p->n};
+    const Round3Polys in{p->at(PR_CO), p->at(PR_Z), p->has_pi ? p->at(PR_PI) : nullptr, p->at(PR_Q), ce.coef, p->n};
     round3_openings(slots, with_quotients, in, [&](const Fr* poly, Fr* quot, int slot, uint8_t point) {
         polys[cnt] = poly;
         quots[cnt] = quot;
-        ys[cnt] = res + slot;
+        ys[cnt] = p->ctx->eval_slots_host + slot;
         zsel[cnt++] = point;
     });
-    launch_open_multi(polys, quots, ys, zsel, cnt, p->n, ze, zw, blocks, p->ctx->stream);
+    launch_open_multi(polys, quots, ys, zsel, cnt, p->n, ze, zw, (Fr*)p->ctx->ops_tmp.p, p->ctx->stream);
     return hip_rc(p->ctx, hipGetLastError());
 }
-// r = sum_k scalar[k] * lin_polys[k] + constant into p->r, stream-ordered
+// r = sum_k scalar[k] * lin_polys[k] + constant into the arena's r, stream-ordered
 int prover_linearise(typlonk_prover* p, const CircuitEntry& ce, const Fr* scalar /* LIN_TERMS */, const Fr& constant) {
     LincombArgs la{};
-    lin_polys(ce.coef, p->z, p->t, p->n, la.poly);
+    lin_polys(ce.coef, p->at(PR_Z), p->at(PR_T), p->n, la.poly);
     for (int k = 0; k < LIN_TERMS; ++k) la.scalar[k] = scalar[k];
     la.constant = constant;
     la.terms = LIN_TERMS;
-    la.out = p->r;
+    la.out = p->at(PR_R);
     la.n = p->n;
     launch_lincomb(la, p->ctx->stream);
     return hip_rc(p->ctx, hipGetLastError());
@@ -456,23 +459,16 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     if (rc) return rc;
     if (log_n > TYPLONK_MAX_PROVER_LOG_N) return fail(ctx, TYPLONK_ERR_LENGTH, "prover supports up to 2^24 rows");
     if (ctx->prover_busy) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "a proof is already in flight on this context");
-    rc = ensure(ctx, ctx->prover_mem, (uint64_t)19 * n * sizeof(Fr));  // 3+3+1+1+4+6+1 vectors, kept across proofs
-    if (rc) return rc;
+    // everything the three (four) rounds touch, sized before anything is queued; kept across proofs
+    const ProvePlan plan = prove_plan(log_n, 1, PROVE_SESSION, /*cached=*/true);
+    if ((rc = prover_workspaces(ctx, plan))) return rc;
     typlonk_prover* p = new typlonk_prover();
     p->ctx = ctx;
     p->srs_id = srs_id;
     p->circuit = circuit_id;
     p->log_n = log_n;
     p->n = n;
-    p->mem = (Fr*)ctx->prover_mem.p;
-    Fr* c = p->mem;
-    for (int i = 0; i < 3; ++i) { p->ev[i] = c; c += n; }
-    for (int i = 0; i < 3; ++i) { p->co[i] = c; c += n; }
-    p->pi = c; c += n;
-    p->z = c; c += n;
-    p->t = c; c += 4 * n;
-    for (int i = 0; i < 6; ++i) { p->q[i] = c; c += n; }
-    p->r = c;
+    p->mem = ProveArena{(Fr*)ctx->prover_mem.p, n, plan.stride};
     hipStream_t s = ctx->stream;
     ProfilingOff prof_off(ctx);  // stage events are per call
     ProverRound in_round(ctx);
@@ -488,19 +484,19 @@ int prover_round1_impl(typlonk_ctx* ctx, uint32_t srs_id, uint32_t circuit_id, c
     MsmQueue q(ctx, srs, /*first_lane=*/1);
     p->has_pi = pi_src.present();  // absent: public inputs [0] -> the zero polynomial
     for (int i = 0; i < 3 && !rc; ++i) {
-        if ((rc = hip_rc(ctx, column_to_device(p->ev[i], wires[i], n, s)))) break;
-        if ((rc = hip_rc(ctx, hipMemcpyAsync(p->co[i], p->ev[i], n * sizeof(Fr), hipMemcpyDeviceToDevice, s)))) break;
-        if ((rc = ntt_run(ctx, p->co[i], log_n, 1, nullptr, false))) break;
-        rc = q.submit(p->co[i], n, commit_xy[i], commit_inf + i);
+        if ((rc = hip_rc(ctx, column_to_device(p->at(PR_EV, i), wires[i], n, s)))) break;
+        if ((rc = hip_rc(ctx, hipMemcpyAsync(p->at(PR_CO, i), p->at(PR_EV, i), n * sizeof(Fr), hipMemcpyDeviceToDevice, s)))) break;
+        if ((rc = ntt_run(ctx, p->at(PR_CO, i), log_n, 1, nullptr, false))) break;
+        rc = q.submit(p->at(PR_CO, i), n, commit_xy[i], commit_inf + i);
     }
     if (!rc && p->has_pi) {
-        rc = hip_rc(ctx, column_to_device(p->pi, pi_src, n, s));
-        if (!rc) rc = ntt_run(ctx, p->pi, log_n, 1, nullptr, false);  // proof.rs:105-106
+        rc = hip_rc(ctx, column_to_device(p->at(PR_PI), pi_src, n, s));
+        if (!rc) rc = ntt_run(ctx, p->at(PR_PI), log_n, 1, nullptr, false);  // proof.rs:105-106
     }
     // the coset transforms of the quotient's per-proof inputs run beside the commitments (measured: -1 % per proof;
     // submitting round 3's first opening MSMs before the quotient loses 1 %: profiles/r02_ab_prover_overlap.txt)
-    for (int i = 0; i < 3 && !rc; ++i) rc = prover_extend(p, i, p->co[i]);
-    if (!rc && p->has_pi) rc = prover_extend(p, 4, p->pi);
+    for (int i = 0; i < 3 && !rc; ++i) rc = prover_extend(p, i, p->at(PR_CO, i));
+    if (!rc && p->has_pi) rc = prover_extend(p, 4, p->at(PR_PI));
     {
         const int r = q.wait_all();
         if (!rc) rc = r;
@@ -550,22 +546,22 @@ int typlonk_prover_round2(typlonk_prover* p, const uint64_t beta[4], const uint6
     memcpy(p->beta.v, beta, 32);
     memcpy(p->gamma.v, gamma, 32);
     for (int i = 0; i < 3; ++i) memcpy(p->k[i].v, cosets[i], 32);
-    typlonk_buf wb[3] = {{p->ev[0], n}, {p->ev[1], n}, {p->ev[2], n}};
+    typlonk_buf wb[3] = {{p->at(PR_EV, 0), n}, {p->at(PR_EV, 1), n}, {p->at(PR_EV, 2), n}};
     typlonk_buf sb[3] = {{ce.sig_ev, n}, {ce.sig_ev + n, n}, {ce.sig_ev + 2 * n, n}};
     const typlonk_buf* wp[3] = {&wb[0], &wb[1], &wb[2]};
     const typlonk_buf* sp[3] = {&sb[0], &sb[1], &sb[2]};
-    typlonk_buf zb{p->z, n};
+    typlonk_buf zb{p->at(PR_Z), n};
     ProfilingOff prof_off(ctx);  // stage events are per call
     ProverRound in_round(ctx);
     int rc = typlonk_grand_product_dev(ctx, wp, sp, beta, gamma, cosets, p->log_n, &zb);  // proof.rs:119-120
-    if (!rc) rc = ntt_run(ctx, p->z, p->log_n, 1, nullptr, false);                          // :127-128
+    if (!rc) rc = ntt_run(ctx, p->at(PR_Z), p->log_n, 1, nullptr, false);                          // :127-128
     if (!rc) {
         const SrsEntry* srs = nullptr;
         rc = msm_validate(ctx, p->srs_id, n, &srs);
         if (!rc) {
             MsmQueue q(ctx, srs, /*first_lane=*/1);
-            rc = q.submit(p->z, n, z_xy, z_inf, /*standalone=*/true);                       // :129
-            if (!rc) rc = prover_extend(p, 3, p->z);  // Z's coset transform runs beside its commitment
+            rc = q.submit(p->at(PR_Z), n, z_xy, z_inf, /*standalone=*/true);                       // :129
+            if (!rc) rc = prover_extend(p, 3, p->at(PR_Z));  // Z's coset transform runs beside its commitment
             const int r = q.wait_all();
             if (!rc) rc = r;
         }
@@ -575,12 +571,12 @@ int typlonk_prover_round2(typlonk_prover* p, const uint64_t beta[4], const uint6
 }
 
 namespace {
-// The quotient t (proof.rs:139-145) into p->t, stream-ordered.  a, b, c, Z (and PI) were transformed to the coset domain in
+// The quotient t (proof.rs:139-145) into the arena's t, stream-ordered.  a, b, c, Z (and PI) were transformed to the coset domain in
 // rounds 1 and 2 (p->extended), so what is left is the pointwise kernel and one inverse transform.
 int prover_quotient(typlonk_prover* p, const Fr& alpha) {
     const uint64_t n = p->n;
-    typlonk_buf b[5] = {{p->co[0], n}, {p->co[1], n}, {p->co[2], n}, {p->z, n}, {p->pi, n}};
-    typlonk_buf tb{p->t, 4 * n};
+    typlonk_buf b[5] = {{p->at(PR_CO, 0), n}, {p->at(PR_CO, 1), n}, {p->at(PR_CO, 2), n}, {p->at(PR_Z), n}, {p->at(PR_PI), n}};
+    typlonk_buf tb{p->at(PR_T), 4 * n};
     typlonk_quotient_args qa{};
     for (int i = 0; i < 3; ++i) qa.wires[i] = &b[i];
     qa.z = &b[3];
@@ -590,7 +586,11 @@ int prover_quotient(typlonk_prover* p, const Fr& alpha) {
     memcpy(qa.gamma, p->gamma.v, 32);
     for (int i = 0; i < 3; ++i) memcpy(qa.cosets[i], p->k[i].v, 32);
     qa.circuit = p->circuit;
-    return quotient_run(p->ctx, &qa, p->log_n, &tb, p->extended);
+    // The session built every buffer itself, so the check is not here because these inputs can fail: it resolves the circuit's
+    // cached evaluations, and it is kept whole so that this step refuses what it always refused, in the same order.
+    QuotientInputs qi;
+    if (const int rc = quotient_check(p->ctx, &qa, p->log_n, &tb, &qi)) return rc;
+    return quotient_queue(p->ctx, &qa, p->log_n, &tb, qi, p->extended);   // (quot_ext, quot_tab: sized in round 1)
 }
 
 // Round 3 in both shapes.  tail != NULL: the reference's six separate openings (proof.rs:147-175).
@@ -628,18 +628,18 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     Fr s0, s1, pi_z = Fr::zero();
     const Fr one = Fr::one();
     Fr zn = ze, zh = one, l0z = one;   // zeta^n, Z_H(zeta), L0(zeta): filled under the kernels, before the wait
+    constexpr Round3Slots S = REF_SLOTS;
     {
         // ONE synchronisation for everything evaluated here (REF_SLOTS): a, b, c, Z at zeta (with their quotients unless
         // batched), sigma_0, sigma_1 and the public-input polynomial at zeta (for the linearisation, proof.rs:376-439, :138),
         // Z at zeta*w (always with its quotient) -- all of them in three launches (launch_open_multi)
-        constexpr Round3Slots S = REF_SLOTS;
         Fr host[S.count];
         rc = prover_open_round3(p, ce, S, /*with_quotients=*/!batched, ze, zw);
         // ---- quotient (proof.rs:139-145): queued behind the opening scans ----
         if (!rc) rc = prover_quotient(p, al);
         // what the linearisation needs of zeta alone (one host inversion among it): while the kernels above run
         lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);
-        if (!rc) rc = prover_fetch(p, host, S.count);
+        if (!rc) rc = prover_fetch(p, host, 0, S.count);
         for (int i = 0; i < 3; ++i) ev[i] = host[S.wire + i];
         ev[3] = host[S.z];
         ev[4] = host[S.zw];
@@ -655,7 +655,8 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     // r(zeta) and its witness polynomial (proof.rs:175).  The reference shape does not wait for the value here: it is an
     // OUTPUT (and the r(zeta) != 0 check), nothing of this round's commitments depends on it -- it is read from its pinned slot
     // once the commitments have been waited for, and the first sort starts without a drain of the context's stream in between.
-    if (!rc) rc = batched ? prover_open(p, p->r, n, ze, nullptr, &ev[5]) : prover_open_async(p, p->r, n, ze, p->q[5], 0);
+    if (!rc) rc = prover_open_async(p, p->at(PR_R), n, ze, batched ? nullptr : p->at(PR_Q, Q_WIT_R), S.r);
+    if (!rc && batched) rc = prover_fetch(p, &ev[5], S.r, 1);
     if (!rc && batched) {
         // evaluations only: every commitment of this shape is issued by round4_batched in ONE five-MSM batch
         for (int i = 0; i < 6; ++i) memcpy(evals_out->evals[i], ev[i].v, 32);
@@ -664,7 +665,9 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
     }
     // ---- the nine remaining commitments in one batch: 6 opening witnesses + 3 quotient slices (:181) ----
     if (!rc && !batched) {
-        const Fr* polys[9] = {p->q[0], p->q[1], p->q[2], p->q[3], p->q[4], p->q[5], p->t, p->t + n, p->t + 2 * n};
+        // (the six witnesses in q's order, Q_WIT_A .. Q_WIT_R, as the proof lists them: prove_plan.hpp asserts the order)
+        const Fr* polys[9] = {p->at(PR_Q, 0), p->at(PR_Q, 1), p->at(PR_Q, 2), p->at(PR_Q, 3), p->at(PR_Q, 4), p->at(PR_Q, 5),
+                              p->at(PR_T), p->at(PR_T, 1), p->at(PR_T, 2)};
         const size_t m[9] = {n - 1, n - 1, n - 1, n - 1, n - 1, n - 1, n, n, n > 3 ? n - 3 : 0};
         q.set_first_lane(0);  // the context's stream has nothing left to do but commit
         // All nine polynomials exist once what is queued on the context's stream NOW has run: the lanes wait for this
@@ -680,7 +683,7 @@ int prover_round3_core(typlonk_prover* p, const uint64_t alpha[4], const uint64_
             const int r = q.wait_all();
             if (!rc) rc = r;
         }
-        if (!rc) rc = prover_fetch(p, &ev[5], 1);   // (every lane has been waited for: this returns at once)
+        if (!rc) rc = prover_fetch(p, &ev[5], S.r, 1);   // (every lane has been waited for: this returns at once)
         if (!rc) {
             memcpy(out->w_xy, xy, 6 * 96);
             memcpy(out->w_inf, inf, 6);
@@ -760,7 +763,7 @@ int typlonk_prover_round4_batched(typlonk_prover* p, const uint64_t v[4], typlon
     // F = a + v b + v^2 c + v^3 Z + v^4 r; division by (X - zeta) is linear, so its witness is
     // sum_i v^i W_i of the six-opening proof
     LincombArgs la{};
-    const Fr* polys[5] = {p->co[0], p->co[1], p->co[2], p->z, p->r};
+    const Fr* polys[5] = {p->at(PR_CO, 0), p->at(PR_CO, 1), p->at(PR_CO, 2), p->at(PR_Z), p->at(PR_R)};
     Fr vv, pw = Fr::one();
     memcpy(vv.v, v, 32);
     for (int i = 0; i < 5; ++i) {
@@ -770,14 +773,15 @@ int typlonk_prover_round4_batched(typlonk_prover* p, const uint64_t v[4], typlon
     }
     la.terms = 5;
     la.constant = Fr::zero();
-    la.out = p->q[5];
+    la.out = p->at(PR_Q, Q_BATCHED_F);
     la.n = n;
     launch_lincomb(la, ctx->stream);
     int rc = hip_rc(ctx, hipGetLastError());
-    if (!rc) rc = prover_open_async(p, p->q[5], n, p->zeta, p->q[0], 0);  // F(zeta) itself is not needed: stream-ordered
+    // (F(zeta) itself is not needed: stream-ordered)
+    if (!rc) rc = prover_open_async(p, p->at(PR_Q, Q_BATCHED_F), n, p->zeta, p->at(PR_Q, Q_BATCHED_WIT), REF_SLOTS.f);
     if (!rc) {
         // one batch: [t_lo], [t_mid], [t_hi] (proof.rs:181), the witness of Z at zeta*w, the batched witness at zeta
-        const Fr* ms[5] = {p->t, p->t + n, p->t + 2 * n, p->q[4], p->q[0]};
+        const Fr* ms[5] = {p->at(PR_T), p->at(PR_T, 1), p->at(PR_T, 2), p->at(PR_Q, Q_WIT_ZW), p->at(PR_Q, Q_BATCHED_WIT)};
         const size_t m[5] = {n, n, n > 3 ? n - 3 : 0, n - 1, n - 1};
         uint64_t xy[5][12];
         uint8_t inf[5];
@@ -903,7 +907,7 @@ int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proo
     rc = prover_quotient(p, al);
     if (!rc) rc = record_fence();
     if (!rc) {
-        const Fr* polys[3] = {p->t, p->t + n, p->t + 2 * n};
+        const Fr* polys[3] = {p->at(PR_T), p->at(PR_T, 1), p->at(PR_T, 2)};
         const size_t m[3] = {n, n, n > 3 ? n - 3 : 0};
         for (int k = 0; k < 3 && !rc; ++k) rc = q.submit(polys[k], m[k], out->t_xy[k], out->t_inf + k);
     }
@@ -924,12 +928,12 @@ int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proo
     rc = prover_open_round3(p, ce, S, /*with_quotients=*/false, ze, zw);
     if (rc) return leave_w(rc);
     lin_zeta_terms(ze, log_n, &zn, &zh, &l0z);   // while the kernels run
-    rc = prover_fetch(p, host, S.count);
+    rc = prover_fetch(p, host, 0, S.count);
     if (rc) return leave_w(rc);
     const Fr pi_z = p->has_pi ? host[S.pi] : Fr::zero();
     for (int i = 0; i < 7; ++i) memcpy(out->evals[i], host[i].v, 32);
     const Fr v = script.after_evals(*out);
-    // ---- r (proof.rs:376-439, with +PI(zeta) as typlonk_prove); r(zeta) lands in slot 0 and is read after the commitments ----
+    // ---- r (proof.rs:376-439, with +PI(zeta) as typlonk_prove); r(zeta) lands in its slot and is read after the commitments ----
     {
         static_assert(S.wire == 0 && S.z == 3 && S.zw == 4, "lin_scalars reads a, b, c, Z, Z(zeta w) as ev[0..4]");
         Fr scalar[LIN_TERMS], constant;
@@ -937,11 +941,11 @@ int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proo
         rc = prover_linearise(p, ce, scalar, constant);
         if (rc) return leave_w(rc);
     }
-    rc = prover_open_async(p, p->r, n, ze, nullptr, 0);
-    // ---- F as one 7-term combination in q[1], its witness polynomial in q[0] (q[0..3] are free in this shape) ----
+    rc = prover_open_async(p, p->at(PR_R), n, ze, nullptr, S.r);
+    // ---- F as one 7-term combination and its witness polynomial, in the places of q this shape gives them (ProveQ) ----
     if (!rc) {
         LincombArgs fa{};
-        const Fr* polys[7] = {p->co[0], p->co[1], p->co[2], p->z, p->r, ce.coef + 5 * n, ce.coef + 6 * n};
+        const Fr* polys[7] = {p->at(PR_CO, 0), p->at(PR_CO, 1), p->at(PR_CO, 2), p->at(PR_Z), p->at(PR_R), ce.coef + 5 * n, ce.coef + 6 * n};
         Fr pw = Fr::one();
         for (int i = 0; i < 7; ++i) {
             fa.poly[i] = polys[i];
@@ -950,22 +954,22 @@ int prover_round3_compact(typlonk_prover* p, CompactScript& script, typlonk_proo
         }
         fa.terms = 7;
         fa.constant = Fr::zero();
-        fa.out = p->q[1];
+        fa.out = p->at(PR_Q, Q_COMPACT_F);
         fa.n = n;
         launch_lincomb(fa, ctx->stream);
         rc = hip_rc(ctx, hipGetLastError());
     }
-    if (!rc) rc = prover_open_async(p, p->q[1], n, ze, p->q[0], 1);   // F(zeta) itself is not needed
+    if (!rc) rc = prover_open_async(p, p->at(PR_Q, Q_COMPACT_F), n, ze, p->at(PR_Q, Q_COMPACT_WIT), S.f);   // F(zeta) itself is not needed
     // ---- W_zeta and W_zeta_w in one queue ----
     if (!rc) rc = record_fence();
-    if (!rc) rc = q.submit(p->q[0], n - 1, out->w_xy[0], out->w_inf + 0);
-    if (!rc) rc = q.submit(p->q[4], n - 1, out->w_xy[1], out->w_inf + 1);
+    if (!rc) rc = q.submit(p->at(PR_Q, Q_COMPACT_WIT), n - 1, out->w_xy[0], out->w_inf + 0);
+    if (!rc) rc = q.submit(p->at(PR_Q, Q_WIT_ZW), n - 1, out->w_xy[1], out->w_inf + 1);
     {
         const int r = q.wait_all();
         if (!rc) rc = r;
     }
     Fr rz;
-    if (!rc) rc = prover_fetch(p, &rz, 1);   // (every lane has been waited for: this returns at once)
+    if (!rc) rc = prover_fetch(p, &rz, S.r, 1);   // (every lane has been waited for: this returns at once)
     // collective 4 of a sharded proof.  r(zeta) comes from replicated data: an unsatisfied witness is unsatisfied on every
     // rank, the points are folded all the same and `out` is filled as on one GPU
     rc = leave_w(rc);
