@@ -246,6 +246,10 @@ int typlonk_ntt_fr_batch_devptr(typlonk_ctx* ctx, void* const* d_data, size_t co
  *                                                                           (160 MiB + 12 MiB at 2^20); not in the total.
  *                                                                           A circuit made by typlonk_circuit_compile holds the
  *                                                                           12 n-byte permutation from the start
+ *   solve cache (about 52 n B)             0.2 GiB    0.4 GiB    0.8 GiB   per circuit, only once typlonk_witness_solve* has run
+ *                                                                           on it, on top of the check cache: src 12 n, order
+ *                                                                           <= 4 n, level offsets <= 4 n, inverses 32 n bytes;
+ *                                                                           not in the total
  * typlonk_prove_batch keeps one wave's arena in prover_mem instead (39 n Fr per proof in flight, one proof per wave here):
  *   prover_mem (39 n Fr)                   4.9 GiB    9.8 GiB   19.5 GiB   (quot_ext is not used by a batch)
  *   ops_tmp (8 n / 2048 Fr) + slots        4 MiB      8 MiB     16 MiB
@@ -692,6 +696,63 @@ int typlonk_witness_check_host(typlonk_ctx* ctx, uint32_t circuit_id, const uint
                                const uint64_t* const* pi, const size_t* pi_len, size_t count,
                                const uint64_t cosets[3][4], uint32_t cap,
                                typlonk_witness_report* reports, uint32_t* gate_rows, uint32_t* copy_cells);
+
+/* ---- witness solve: the wire columns from the circuit's inputs ---------------------------------------------------------------
+ * The reference's interface is circuit.prove([3, 4, 5], vec![0]) (plonk/src/proof.rs:26-57): it takes the circuit's INPUTS, and
+ * C::run (builder.rs:381-396) fills the three advice columns gate by gate.  The call below is that step on the device: from a
+ * loaded circuit, a handful of assigned cells and the public values it writes the full wire columns into device buffers, ready
+ * for typlonk_witness_check and every prover -- the columns never leave HBM.  Deterministic: the library draws no randomness.
+ * Cells are flat indices x = col * n + row.  A CLASS is a cycle of the circuit's permutation (the copy kept by
+ * typlonk_circuit_compile*, or the one recovered as for typlonk_witness_check, under `cosets`); a circuit with defects != 0 is
+ * refused exactly as the check refuses it.
+ *   driven      row j is driven iff q_o[j] != 0 mod r.  A class is driven iff it contains the c cell 2n + j of a driven row; its
+ *               driver is the lowest such row.  Every other class is free.
+ *   values      a free class takes the value assigned to one of its cells through cells / values, or 0 if none is assigned
+ *               (the reference's resize(rows - 3, Fr::zero())).  The three blinding rows are ordinary free cells that the
+ *               caller assigns.  A driven class with driver d takes c_d = (q_l a + q_r b + q_m a b + q_c + PI_d) / q_o at row
+ *               d, a and b being the values of the classes of cells d and n + d, and PI_d = 0 for d >= pi_len.
+ *               Every cell gets its class's value, with one exception: the c cell of a driven row that is NOT its class's
+ *               driver gets its OWN row's computed value -- two computed values tied by assert_eq.  If the two differ,
+ *               typlonk_witness_check then names the copy constraint; solve never papers over it.
+ *               Rows with q_o = 0 (constant rows, boolean rows) are not enforced by solve: they are the check's business.
+ *               Outputs are canonical Montgomery residues: they compare word for word.
+ *   order       row j depends on the drivers of the classes of its a and b cells; rows may be in any order in the table.  If
+ *               the dependencies have a cycle the circuit cannot be solved by propagation: TYPLONK_ERR_INVALID_ARG, and
+ *               typlonk_last_error names the lowest row that could not be scheduled.
+ *   cells       HOST, n_cells flat indices shared by all witnesses; values: HOST, count * n_cells * 4 limbs, witness-major.
+ *               Both may be NULL when n_cells = 0.
+ *   pi, pi_len  as typlonk_witness_check.  wire_out: count * 3 buffers, proof-major, >= n elements each, all distinct.
+ *   refusals    TYPLONK_ERR_INVALID_ARG: a null argument, an unknown circuit, a null output column, pi_len[k] != 0 with pi or
+ *               pi[k] NULL, a cell >= 3n, a cell in a driven class, two cells of one class, a value >= r (as
+ *               typlonk_poly_eval_dev refuses a point), an unsolvable or malformed circuit.  TYPLONK_ERR_RANGE: an output or pi
+ *               buffer too short.  TYPLONK_ERR_LENGTH: pi_len[k] > n.  For the cell and value refusals typlonk_last_error names
+ *               the index into cells.  A refused call leaves every output as it was; count = 0 is a no-op.
+ * Like the check: blocks, runs on the context's stream, never a collective, no SRS, works on a sharded context.
+ * The plan (host, O(n), once per (circuit, cosets), cached with the circuit, freed by typlonk_circuit_free / typlonk_destroy):
+ * the level of a driven row is 1 + the larger level of its two sources, a free source being level 0.  A level wider than 256
+ * rows is one launch over rows x witnesses; a maximal run of consecutive levels of <= 256 rows each is ONE launch of one
+ * 256-thread workgroup per witness that steps through them (cut every 65,536 levels); one fill launch writes the undriven
+ * rows.  No kernel waits on another workgroup.  Per driven row: two 32-byte gathers, seven fr30 products (five of the equation,
+ * two radix fixes), three 32-byte stores.  Every cell is written exactly once per call.
+ * Kept per circuit once solved (beside the check cache): src 12 n + order 4 n + level offsets <= 4 n + inverses 32 n bytes on the
+ * device, about 52 n (52 MiB at 2^20), and src again on the host.  Per call: 4 bytes per free class and 32 * count * n_cells
+ * bytes go up.
+ * What a caller reads to decide (typlonk_solve_info): a solve costs `launches` kernel launches plus, inside run launches, one
+ * dependent global-memory round trip and a barrier per level -- `depth` of them end to end.  A wide, shallow circuit (depth of
+ * tens) is launch- and bandwidth-bound: 2^20 rows in 33 levels take 1.0 ms, 1/70 of the CPU fill and upload they replace.  A
+ * deep, narrow one (the squaring chain: depth = n - 3, one row per level) is latency-bound at about 4.5 us per level and
+ * LOSES to the CPU: 291 ms against 5 ms on one CPU thread at 2^16 rows for one witness, on par from 64 witnesses per call
+ * (MI355X; DESIGN.md 8i has the measured table).  When depth is within a small factor of driven_rows, fill on the CPU. */
+typedef struct typlonk_solve_info {
+    uint64_t driven_rows, free_classes;
+    uint32_t depth;    /* number of levels                                                                                  */
+    uint32_t launches; /* kernel launches one solve queues, whatever count is (per group of 1024 witnesses)                 */
+} typlonk_solve_info;
+/* builds the plan on first use per (circuit, cosets), caches it with the circuit, reports it */
+int typlonk_witness_solve_plan(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t cosets[3][4], typlonk_solve_info* info);
+int typlonk_witness_solve(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t cosets[3][4],
+                          const uint32_t* cells, size_t n_cells, const uint64_t* values,
+                          const typlonk_buf* const* pi, const size_t* pi_len, size_t count, typlonk_buf* const* wire_out);
 
 /* ---- wire format: compact proofs, verifying keys and SRS points as bytes, with compressed points ------------------------
  * Everything above works on in-memory arkworks limbs that the caller is trusted to have formed.  The byte forms below are

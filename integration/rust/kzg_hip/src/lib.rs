@@ -563,6 +563,45 @@ impl Backend {
         }).collect()
     }
 
+    /// `typlonk_witness_solve_plan`: what a solve of this circuit costs -- driven rows, free classes, levels (`depth`) and
+    /// kernel launches per solve.  Built on first use per (circuit, cosets) and cached with the circuit.  A deep, narrow
+    /// circuit (depth close to n) is latency-bound on the device: a caller with a single witness of one reads `depth` here
+    /// and may fill it on the CPU instead.
+    pub fn solve_info(&self, circuit: CircuitHandle, cosets: [Fr; 3]) -> ffi::TyplonkSolveInfo {
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        let mut info: ffi::TyplonkSolveInfo = unsafe { std::mem::zeroed() };
+        self.check(unsafe { ffi::typlonk_witness_solve_plan(self.ctx, circuit.id, k.as_ptr(), &mut info) });
+        info
+    }
+
+    /// `typlonk_witness_solve`: the three wire columns of `values.len()` witnesses from the circuit's inputs, computed on
+    /// the device (`C::run(ComputeVar..)` of the reference, builder.rs:381-396).  `cells`: the flat indices col * n + row of
+    /// the assigned cells -- the inputs and, if wanted, the three blinding rows -- shared by all witnesses; `values[k]`: their
+    /// values for witness k; `public_inputs`: empty, or one list of public values per witness.  Every other free class reads
+    /// 0; every driven row's c cell is computed.  The columns stay on the device: `[a, b, c]` per witness, ready for the
+    /// check and the provers.  Panics for a cell in a driven class, two cells of one class, or an unsolvable circuit.
+    pub fn solve_witnesses(&self, circuit: CircuitHandle, cells: &[u32], values: &[&[Fr]], public_inputs: &[&[Fr]],
+                           cosets: [Fr; 3]) -> Vec<[DeviceVec<'_>; 3]> {
+        let count = values.len();
+        assert!(values.iter().all(|v| v.len() == cells.len()), "one value per assigned cell and witness");
+        assert!(public_inputs.is_empty() || public_inputs.len() == count, "one public-input list per witness");
+        let n = 1usize << circuit.log_n;
+        let vals: Vec<u64> = values.iter().flat_map(|v| v.iter().flat_map(|e| fr_limbs(e))).collect();
+        let pis: Vec<DeviceVec<'_>> = public_inputs.iter().map(|p| self.upload(p, p.len().max(1))).collect();
+        let pp: Vec<*const ffi::TyplonkBuf> = pis.iter().map(|d| d.buf as *const ffi::TyplonkBuf).collect();
+        let lens: Vec<usize> = public_inputs.iter().map(|p| p.len()).collect();
+        let out: Vec<[DeviceVec<'_>; 3]> = (0..count).map(|_| [self.upload(&[], n), self.upload(&[], n), self.upload(&[], n)]).collect();
+        let wp: Vec<*mut ffi::TyplonkBuf> = out.iter().flat_map(|cols| cols.iter().map(|d| d.buf)).collect();
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        self.check(unsafe {
+            ffi::typlonk_witness_solve(self.ctx, circuit.id, k.as_ptr(), if cells.is_empty() { ptr::null() } else { cells.as_ptr() },
+                                       cells.len(), if vals.is_empty() { ptr::null() } else { vals.as_ptr() },
+                                       if pp.is_empty() { ptr::null() } else { pp.as_ptr() },
+                                       if lens.is_empty() { ptr::null() } else { lens.as_ptr() }, count, wp.as_ptr())
+        });
+        out
+    }
+
     /// `typlonk_verify_compact`: a batch of compact proofs against a verifying key; needs no SRS and no circuit on this
     /// backend.  `public_inputs`: empty, or one list of public values per proof.
     pub fn verify_compact(&self, vk: &ffi::TyplonkVk, proofs: &[ffi::TyplonkProofCompact], public_inputs: &[Vec<Fr>]) -> Vec<bool> {

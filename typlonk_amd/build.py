@@ -10,6 +10,8 @@
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
   tests/cpp/msm_plan_host         host build of msm_plan, every decision of an MSM, a program of its own (tests/test_msm_plan_host.py) -- g++
   tests/cpp/ntt_plan_host         host build of ntt_plan, every decision of a batch of NTTs, a program of its own (tests/test_ntt_plan_host.py) -- g++
+  tests/cpp/solve_plan_host[_san] host build of solve_plan, every decision of a witness solve, a program of its own, once plain and once under the
+                                  address and undefined-behaviour sanitizers (tests/test_solve_plan_host.py) -- g++
   tests/cpp/prove_plan_host[_san] host build of prove_plan, where a proof's data lives and what each workspace of a prover call holds, a program of its
                                   own, once plain and once under the address and undefined-behaviour sanitizers (tests/test_prove_plan_host.py) -- g++
   tests/cpp/madd_acc_host[_san]   host build of g1_madd_acc / g1_acc_finish, the accumulation loops' mixed addition, a program of its own, once plain
@@ -49,7 +51,7 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -224,6 +226,18 @@ def build_prove_plan_host(force: bool = False, sanitize: bool = False) -> str:
     return out
 
 
+def build_solve_plan_host(force: bool = False, sanitize: bool = False) -> str:
+    """tests/cpp/solve_plan_host: solve_plan (csrc/solve_plan.hpp) as the host compiles it, printing the plan of each circuit it reads;
+    sanitize: the same program as tests/cpp/solve_plan_host_san, compiled with -fsanitize=address,undefined"""
+    src = os.path.join(ROOT, "tests", "cpp", "solve_plan_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "solve_plan_host_san" if sanitize else "solve_plan_host")
+    deps = [src, os.path.join(CSRC, "solve_plan.hpp")]
+    if force or _stale(out, deps):
+        extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+        _run(["g++", *extra, "-std=c++17", src, "-o", out])
+    return out
+
+
 def build_madd_acc_host(force: bool = False, sanitize: bool = False) -> str:
     """tests/cpp/madd_acc_host: g1_madd_acc / g1_acc_finish (csrc/g1.hpp) as the host compiles them, run over the cases it reads;
     sanitize: the same program as tests/cpp/madd_acc_host_san, compiled with -fsanitize=address,undefined"""
@@ -258,7 +272,7 @@ def build_host_tests(force: bool = False) -> list[str]:
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
                  "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
-                 "test_circuit_pairs_host"):
+                 "test_circuit_pairs_host", "test_witness_solve_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
         if force or _stale(out, [src] + hdr):
@@ -299,6 +313,9 @@ def build_all(force: bool = False) -> None:
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "madd_acc_host.cpp")):
         build_madd_acc_host(force)
         build_madd_acc_host(force, sanitize=True)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "solve_plan_host.cpp")):
+        build_solve_plan_host(force)
+        build_solve_plan_host(force, sanitize=True)
     build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)

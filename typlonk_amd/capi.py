@@ -39,6 +39,7 @@ SYMBOLS = [
     "typlonk_circuit_permutation", "typlonk_witness_check", "typlonk_witness_check_host",
     "typlonk_circuit_compile", "typlonk_circuit_compile_host",
     "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
+    "typlonk_witness_solve_plan", "typlonk_witness_solve",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -101,6 +102,11 @@ class WitnessReport(C.Structure):
 
 
 CELL_NONE = 0xFFFFFFFF   # TYPLONK_CELL_NONE
+
+
+class SolveInfo(C.Structure):
+    """typlonk_solve_info"""
+    _fields_ = [("driven_rows", C.c_uint64), ("free_classes", C.c_uint64), ("depth", C.c_uint32), ("launches", C.c_uint32)]
 
 
 class ProofCompact(C.Structure):
@@ -360,6 +366,11 @@ def load_library() -> C.CDLL:
                                                       C.c_uint32, u32p, C.POINTER(C.c_uint64)]
         lib.typlonk_circuit_compile_pairs_host.argtypes = [vp, C.POINTER(u64p), C.c_size_t, u32p, C.c_size_t,
                                                            C.POINTER((C.c_uint64 * 4) * 3), C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "typlonk_witness_solve") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_witness_solve_plan.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(SolveInfo)]
+        lib.typlonk_witness_solve.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), u32p, C.c_size_t, u64p, C.POINTER(vp),
+                                              C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -1223,6 +1234,35 @@ class Context:
                                                       C.byref(_cosets_arg(cosets)), cap, reports, gate if cap else None,
                                                       copy if cap else None))
         return self._witness_reports(k, cap, reports, gate, copy)
+
+    # ---- witness solve --------------------------------------------------------------------
+    def witness_solve_plan(self, circuit: int, cosets) -> dict:
+        """typlonk_witness_solve_plan: the plan of a solve of this circuit under these cosets (built on first use, cached with the
+        circuit) as a dict: driven_rows, free_classes, depth (levels) and launches (kernel launches per solve)"""
+        info = SolveInfo()
+        self._chk(self.lib.typlonk_witness_solve_plan(self.h, circuit, C.byref(_cosets_arg(cosets)), C.byref(info)))
+        return {"driven_rows": int(info.driven_rows), "free_classes": int(info.free_classes), "depth": int(info.depth),
+                "launches": int(info.launches)}
+
+    def witness_solve(self, circuit: int, cosets, cells, values, wire_out, pi=None, pi_len=None) -> None:
+        """typlonk_witness_solve: cells = the flat indices of the assigned cells (shared by all witnesses); values = a
+        (count, len(cells), 4) u64 array of canonical Montgomery limbs, witness-major; wire_out = one [a, b, c] list of buffers
+        (>= n elements each) per witness, written in place; pi / pi_len as witness_check."""
+        k = len(wire_out)
+        cl = np.ascontiguousarray(cells, dtype=np.uint32)
+        vals = np.ascontiguousarray(values, dtype=np.uint64)
+        if vals.size != k * cl.size * 4:
+            raise ValueError("witness_solve needs count * len(cells) * 4 value limbs")
+        w = (C.c_void_p * max(3 * k, 1))(*[b.handle.value for cols in wire_out for b in cols])
+        pip = None
+        if pi is not None:
+            pip = (C.c_void_p * max(k, 1))(*[b.handle.value if b is not None else None for b in pi])
+        if pi_len is None and pi is not None:
+            pi_len = [b.n if b is not None else 0 for b in pi]
+        lens = (C.c_size_t * max(k, 1))(*[int(x) for x in pi_len]) if pi_len is not None else None
+        self._chk(self.lib.typlonk_witness_solve(self.h, circuit, C.byref(_cosets_arg(cosets)),
+                                                 cl.ctypes.data_as(C.POINTER(C.c_uint32)) if cl.size else None, cl.size,
+                                                 _u64p(vals) if vals.size else None, pip, lens, k, w))
 
     def circuit_load(self, log_n: int, selectors, sigma) -> int:
         sel = (C.c_void_p * 5)(*[b.handle.value for b in selectors])

@@ -14,6 +14,8 @@
 //                 quot_tab and batch_tab is called by prover_workspaces and the three stand-alone entry points of prover.hip only
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip); which scalars and
 //                 points they and the wire format admit: host_checks.hpp; the linearisation commitment: lin_commit.hpp
+//   witness_solve.hip  typlonk_witness_solve: the wire columns of a witness from the circuit's inputs, level by level
+//                 (solve_plan.hpp: every decision, no device needed)
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
 //                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
@@ -24,6 +26,7 @@
 #include "launch.hpp"
 #include "ntt_plan.hpp"
 #include "prove_plan.hpp"
+#include "solve_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -92,6 +95,17 @@ struct CircuitEntry {
     uint64_t perm_defects = 0;      //      cells without an image + cells that are the image of != 1 cells
     uint32_t perm_first_bad = 0;    //      the lowest such cell
     Fr* sel_ev = nullptr;           // 5n : selector evaluations over the domain
+    // typlonk_witness_solve (witness_solve.hip), built on first use per (circuit, cosets): the plan (solve_plan.hpp; of its
+    // tables the host keeps src, for the admission of a call's cells, and the schedule) and its tables on the device
+    struct Solve {
+        bool ready = false;
+        uint64_t cosets[3][4] = {};
+        SolvePlan plan;                 // order and level are dropped once the tables are uploaded
+        uint32_t* d_src = nullptr;      // 3n
+        uint32_t* d_order = nullptr;    // driven rows
+        uint32_t* d_level_off = nullptr;  // depth + 1
+        Fr* d_qo_inv = nullptr;         // n : 2^28 / q_o of a driven row, zero elsewhere
+    } solve;
 };
 
 struct ProfStage {
@@ -564,8 +578,13 @@ inline int admit_rows(typlonk_ctx* ctx, const ColumnsOf& in, uint64_t n) {
 }
 
 // ---- witness_check.hip ----------------------------------------------------------------------------------------------
-// frees a circuit's recovered permutation and selector evaluations (typlonk_circuit_free, typlonk_destroy)
+// frees a circuit's recovered permutation, selector evaluations and solve tables (typlonk_circuit_free, typlonk_destroy)
 void circuit_check_release(CircuitEntry& e);
+// e.perm for these cosets and e.sel_ev, made on first use; a circuit whose sigma is no permutation of the cells is refused
+// (TYPLONK_ERR_INVALID_ARG, the lowest defective cell named).  Blocks.  typlonk_witness_check and typlonk_witness_solve.
+int circuit_check_prepare(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]);
+// ---- witness_solve.hip ----------------------------------------------------------------------------------------------
+void circuit_solve_release(CircuitEntry& e);
 // where the permutation a compile keeps comes from: 3n successors in HOST memory, or a producer that writes them into the
 // kept copy on the device (perm_pairs.hip), or neither: the identity
 struct PermSource {

@@ -425,13 +425,7 @@ int witness_check_impl(typlonk_ctx* ctx, uint32_t circuit_id, const ColumnsOf& i
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ProfilingOff prof_off(ctx);
-    rc = ensure_perm(ctx, e, cosets);
-    if (rc) return rc;
-    if (e.perm_defects)
-        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
-                    "malformed circuit: sigma is not a permutation of the cells (" + std::to_string(e.perm_defects) +
-                        " defects, the lowest at cell " + std::to_string(e.perm_first_bad) + "; see typlonk_circuit_permutation)");
-    rc = ensure_selectors(ctx, e);
+    rc = circuit_check_prepare(ctx, e, cosets);
     if (rc) return rc;
     // witnesses per launch: bounded by the workspace (masks, counts, lists) and, for the host form, by the staged columns
     const uint32_t cap_copy = (uint32_t)std::min<uint64_t>(o.cap, 3 * n);
@@ -561,7 +555,19 @@ int circuit_compile_impl(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource
 }  // namespace
 
 namespace tyh {
-void circuit_check_release(CircuitEntry& e) { free_check_cache(e); }
+void circuit_check_release(CircuitEntry& e) {
+    free_check_cache(e);
+    circuit_solve_release(e);
+}
+int circuit_check_prepare(typlonk_ctx* ctx, CircuitEntry& e, const uint64_t cosets[3][4]) {
+    const int rc = ensure_perm(ctx, e, cosets);
+    if (rc) return rc;
+    if (e.perm_defects)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG,
+                    "malformed circuit: sigma is not a permutation of the cells (" + std::to_string(e.perm_defects) +
+                        " defects, the lowest at cell " + std::to_string(e.perm_first_bad) + "; see typlonk_circuit_permutation)");
+    return ensure_selectors(ctx, e);
+}
 int circuit_compile_from(typlonk_ctx* ctx, const ColumnsOf& in, const PermSource& from, const uint64_t cosets[3][4], uint32_t log_n,
                          uint32_t* circuit_id, uint64_t* defects) {
     return circuit_compile_impl(ctx, in, from, cosets, log_n, circuit_id, defects);

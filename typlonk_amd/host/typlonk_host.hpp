@@ -919,6 +919,52 @@ class CompiledCircuit {
         for (uint32_t k = 0; k < rep.copy_listed; ++k) out.copy_cells.push_back({copy[2 * k], copy[2 * k + 1]});
         return out;
     }
+    // The three wire columns of a witness from the circuit's inputs, computed on the device (typlonk_witness_solve; the
+    // reference's C::run filling the advice columns, builder.rs:381-396): `cells` are the flat indices (col * n + row) of the
+    // assigned cells -- the inputs and, if wanted, the three blinding rows -- and `values` their values; every other free class
+    // reads 0 and every driven row's c cell is computed.  The columns come back to the host here, for check_witness / prove();
+    // a caller that keeps them on the device calls the C ABI directly.  Throws for a cell in a driven class, two cells of one
+    // class, or a circuit whose rows depend on each other in a cycle.
+    void solve_witness(const std::vector<uint32_t>& cells, const std::vector<Fr>& values, std::vector<Fr> (&advice)[3],
+                       const std::vector<Fr>& public_inputs = {}) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        if (cells.size() != values.size()) throw std::runtime_error("one value per assigned cell");
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        typlonk_buf* out[3] = {nullptr, nullptr, nullptr};
+        typlonk_buf* pib = nullptr;
+        auto release = [&] {
+            for (typlonk_buf* b : out)
+                if (b) typlonk_buf_free(c, b);
+            if (pib) typlonk_buf_free(c, pib);
+        };
+        int rc = 0;
+        for (int i = 0; i < 3 && rc >= 0; ++i) rc = typlonk_buf_alloc(c, n_, &out[i]);
+        if (rc >= 0 && !public_inputs.empty()) {
+            rc = typlonk_buf_alloc(c, public_inputs.size(), &pib);
+            if (rc >= 0) rc = typlonk_buf_upload(c, pib, 0, public_inputs[0].limbs(), public_inputs.size());
+        }
+        const typlonk_buf* pis[1] = {pib};
+        const size_t lens[1] = {public_inputs.size()};
+        if (rc >= 0)
+            rc = typlonk_witness_solve(c, circuit_, ks, cells.empty() ? nullptr : cells.data(), cells.size(),
+                                       values.empty() ? nullptr : values[0].limbs(), pis, lens, 1, out);
+        for (int i = 0; i < 3 && rc >= 0; ++i) {
+            advice[i].assign(n_, Fr());
+            rc = typlonk_buf_download(c, out[i], 0, advice[i][0].limbs(), n_);
+        }
+        release();
+        check(rc, c);
+    }
+    // what a solve of this circuit costs: driven rows, free classes, levels and kernel launches (typlonk_witness_solve_plan)
+    typlonk_solve_info solve_info() const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        typlonk_solve_info info{};
+        check(typlonk_witness_solve_plan(c, circuit_, ks, &info), c);
+        return info;
+    }
 
    private:
     void g2s_limbs(uint64_t g2s[24]) const {
