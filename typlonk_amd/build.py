@@ -16,6 +16,9 @@
                                   own, once plain and once under the address and undefined-behaviour sanitizers (tests/test_prove_plan_host.py) -- g++
   tests/cpp/madd_acc_host[_san]   host build of g1_madd_acc / g1_acc_finish, the accumulation loops' mixed addition, a program of its own, once plain
                                   and once under the address and undefined-behaviour sanitizers (tests/test_madd_acc_host.py) -- g++
+  tests/cpp/fq30_rows_host[_san]  host build of csrc/fq30_rows.hpp, Fq with one limb per lane and g1_add_rows over an array-of-64 wave, a program of its
+                                  own, once plain and once under the address and undefined-behaviour sanitizers (tests/test_fq30_rows_host.py) -- g++
+  tests/cpp/libdevice_reduce_rows.so  device harness over g1_add_rows and the row-form bit planes of msm_reduce.hip (tests/test_gpu_reduce_rows.py) -- hipcc
   tests/cpp/libdevice_pair.so     device build of the same (tests/test_gpu_fq30_pair.py) -- hipcc
   tests/cpp/test_{poly,kzg,plonk,wire,...}_host  tests of the C++ host mirror (typlonk_amd/host) -- g++
 
@@ -65,6 +68,10 @@ def build_hip(force: bool = False) -> str:
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     hdrs.append(os.path.join(ROOT, "include", "typlonk.h"))
     objdir = os.path.join(CSRC, "_obj")
+    # a tree that came with its library but without the objects (they are intermediate files): nothing to do while the
+    # library is newer than every source
+    if not force and not _stale(LIB, [os.path.join(CSRC, u) for u in HIP_UNITS] + hdrs):
+        return LIB
     os.makedirs(objdir, exist_ok=True)
     hipcc = hipcc_path()
     jobs, objs = [], []
@@ -122,6 +129,11 @@ def build_hip_test_hooks(force: bool = False) -> str:
     obj = os.path.join(out_dir, "comm.o")
     base_obj = os.path.join(CSRC, "_obj")
     objs = [obj if u == "comm.hip" else os.path.join(base_obj, u.replace(".hip", ".o")) for u in HIP_UNITS]
+    # (as build_hip: a hooks library newer than its sources and the base library stands without the objects)
+    if not force and not _stale(lib, [src] + hdrs + [LIB]):
+        return lib
+    if not all(os.path.exists(o) for o in objs if o != obj):
+        build_hip(force=True)
     # comm.o is linked with the base objects, so it must be compiled from the same headers (typlonk_ctx's layout): one older
     # than the base library may come from other sources with newer mtimes, and is rebuilt
     if force or _stale(obj, [src] + hdrs + [LIB]):
@@ -250,6 +262,30 @@ def build_madd_acc_host(force: bool = False, sanitize: bool = False) -> str:
     return out
 
 
+def build_fq30_rows_host(force: bool = False, sanitize: bool = False) -> str:
+    """tests/cpp/fq30_rows_host: csrc/fq30_rows.hpp as the host compiles it (the wave an array of 64), run over the commands it reads;
+    sanitize: the same program as tests/cpp/fq30_rows_host_san, compiled with -fsanitize=address,undefined"""
+    src = os.path.join(ROOT, "tests", "cpp", "fq30_rows_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "fq30_rows_host_san" if sanitize else "fq30_rows_host")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("ff.hpp", "fq30.hpp", "g1.hpp", "fq30_rows.hpp")]
+    if force or _stale(out, deps):
+        extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+        _run(["g++", *extra, "-std=c++17", src, "-o", out])
+    return out
+
+
+def build_device_reduce_rows(force: bool = False) -> str:
+    """tests/cpp/libdevice_reduce_rows.so: csrc/harness/device_reduce_rows.hip, msm_reduce.hip compiled as a unit behind entry points that
+    run g1_add_rows on caller-made pairs and the four-launch reduction with its planes summed either way (tests/test_gpu_reduce_rows.py).
+    Test-only and not linked into the shipped library; the flags are build_hip()'s."""
+    src = os.path.join(CSRC, "harness", "device_reduce_rows.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_reduce_rows.so")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "msm_reduce.hip")]
+    if force or _stale(out, [src] + deps):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
 def build_device_pair(force: bool = False) -> str:
     """tests/cpp/libdevice_pair.so: the same functions' device code (the interleaved chains of fq30_pair.hpp) behind an
     element-wise test kernel.  Test-only; the flags are build_hip()'s."""
@@ -316,6 +352,10 @@ def build_all(force: bool = False) -> None:
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "solve_plan_host.cpp")):
         build_solve_plan_host(force)
         build_solve_plan_host(force, sanitize=True)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "fq30_rows_host.cpp")):
+        build_fq30_rows_host(force)
+        build_fq30_rows_host(force, sanitize=True)
+    build_device_reduce_rows(force)
     build_device_pair(force)
     build_host_tests(force)
     build_fake_rccl(force)

@@ -112,6 +112,10 @@ void launch_msm_accum(const uint32_t* points, const uint32_t* offsets, const uin
 // Row/column bucket reduction (msm_reduce.hip; RcShape and the bit planes it returns: msm_plan.hpp)
 void launch_msm_rc_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* pb, uint32_t* pa, uint32_t* sums,
                           uint32_t* bitsum, uint32_t* out, hipStream_t s);
+// launch_msm_rc_reduce with the form of its bit planes named (cl, ch >= 6): rows = one addition per wavefront (fq30_rows.hpp;
+// what launch_msm_rc_reduce runs wherever the shape allows it), else one thread per point (msm_rc2_planes_kernel)
+void launch_msm_rc_reduce_form(const uint32_t* buckets, const RcShape& sh, uint32_t* pb, uint32_t* pa, uint32_t* sums,
+                               uint32_t* bitsum, uint32_t* out, bool rows, hipStream_t s);
 // the same bit planes in two launches (msm_reduce.hip); needs msm_rc2_ok(sh); prow, pcol: nsets << (c1 - 6) points each
 void launch_msm_rc2_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* prow, uint32_t* pcol, uint32_t* out,
                            hipStream_t s);

@@ -1,4 +1,5 @@
 // MSM bucket reduction: per bucket set sum_k w(k)*B_k by the row/column split (launch.hpp) + wavefront butterflies.
+#include "fq30_rows.hpp"
 #include "launch.hpp"
 #include "msm_common.hpp"
 
@@ -13,6 +14,7 @@ namespace ty {
 // 3. msm_rc_bits_kernel     one wavefront per (set, kind, weight bit, 64-item chunk): butterfly sum of the
 //    items whose weight has that bit set.
 // 4. msm_rc_final_kernel    one wavefront per (set, kind, bit): sum over the chunks.
+// For cl, ch >= 6 steps 3 and 4 are msm_rows_planes_kernel<0> and <1> below, one addition per wavefront (fq30_rows.hpp).
 __global__ __launch_bounds__(64) void msm_rc_partial_kernel(const uint32_t* __restrict__ buckets, RcShape sh,
                                                             uint32_t nrow, uint32_t nrow_pad, uint32_t ncol,
                                                             uint32_t* pb, uint32_t* pa) {
@@ -250,8 +252,113 @@ void launch_msm_rc_combine(const uint32_t* planes, const RcShape& sh, uint32_t* 
     hipLaunchKernelGGL(msm_rc_combine_kernel, dim3(sh.nsets), dim3(64), 0, s, planes, sh, set_sums);
 }
 
-void launch_msm_rc_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* pb, uint32_t* pa, uint32_t* sums,
-                          uint32_t* bitsum, uint32_t* out, hipStream_t s) {
+// ---- the bit planes of the four-launch form with ONE ADDITION PER WAVEFRONT (fq30_rows.hpp) ------------------------------------
+// msm_rc2_planes_kernel sums the <= 2^(cl - 1) selected row / column sums of a plane with one workgroup: 1-2 sequential
+// additions, six butterfly levels and two more across its wavefronts, every level at the latency of a whole single-lane
+// addition (6.2 us a butterfly_add4 level, 76.6 us the kernel at 2^19 buckets) while ~20 of the chip's 256 CUs work.  Here an
+// addition is spread over a wavefront -- limb i of a field element on lane i of a 16-lane row, the four rows in the four roles
+// of butterfly_add4's schedule -- and a level costs 2.0 us (tools/ubench_rows.hip, profiles/r26_ab_reduce_rows.txt):
+//   stage 0   one workgroup of four wavefronts (one per SIMD) per (plane, group of n1 selected items): the items are read
+//             into the LDS in the limb layout and summed pairwise, level by level, log2 n1 levels      -> bitsum[plane][group]
+//   stage 1   one workgroup of eight wavefronts per plane: the <= 64 group sums likewise              -> the plane
+// Levels are chained through the LDS (two buffers, a barrier per level); the two stages are two launches, the only
+// cross-workgroup dependency.  Where the row form starts: its additions issue ~650 wave-instructions each, so a level of N
+// additions costs N / 1024 * 1.5 us of the chip against ~8 us for a butterfly level of any width: the row form wins below
+// ~2^12 additions a level.  The planes start at 3.7 k additions (20 planes of 2^8 or 2^9 items at 2^19 buckets) and are all in that range;
+// the levels before them (msm_rc_partial_kernel, msm_fold_seq_kernel: 2^16 .. 2^11 additions a level) stay one thread per point.
+// n1 = 16 (more where a plane has more than 2^10 items, so that a plane has <= 64 groups), G = groups per plane.
+constexpr uint32_t ROWS_MAX_ITEMS = 64;
+constexpr int ROWS_THREADS0 = 256, ROWS_THREADS1 = 512;
+
+struct RowsPlane {
+    uint32_t set, kind, bit, v, litems, nsel, ng;
+    bool top, live;
+};
+__device__ __forceinline__ RowsPlane rows_plane(const RcShape& sh, uint32_t plane, uint32_t ln1) {
+    RowsPlane p;
+    p.bit = plane % RC_NB;
+    p.kind = (plane / RC_NB) & 1u;
+    p.set = plane / (2 * RC_NB);
+    uint32_t nbr, nbc, shift;
+    rc_bits(sh, p.set, &nbr, &nbc, &shift);
+    p.live = p.bit < (p.kind ? nbc : nbr);
+    p.v = rc_set_v(sh, p.set);
+    p.litems = p.kind ? sh.cl : sh.ch;
+    // without virtual copies only the items whose weight has the bit are read (msm_rc2_planes_kernel): half of them, or the
+    // single weight 2^cl of the columns' top plane
+    p.top = p.v == 0 && p.kind && p.bit == sh.cl;
+    p.nsel = p.v == 0 ? (p.top ? 1u : 1u << (p.litems - 1)) : 1u << p.litems;
+    p.ng = (p.nsel + (1u << ln1) - 1) >> ln1;
+    return p;
+}
+// the idx-th item of a plane's sum: its packed words, or nullptr for an item whose weight lacks the bit (virtual copies)
+__device__ __forceinline__ const uint32_t* rows_item(const RcShape& sh, const RowsPlane& p, const uint32_t* rsum,
+                                                     const uint32_t* csum, uint32_t idx) {
+    const uint32_t* src = p.kind ? csum : rsum;
+    const uint64_t sbase = (uint64_t)p.set << p.litems;
+    if (p.v == 0) {
+        const uint32_t w = p.top ? (1u << sh.cl) : (((idx >> p.bit) << (p.bit + 1)) | (1u << p.bit) | (idx & ((1u << p.bit) - 1)));
+        return src + (sbase + (w - p.kind)) * 48;
+    }
+    return ((rc_weight(sh, p.set, p.kind, idx) >> p.bit) & 1u) ? src + (sbase + idx) * 48 : nullptr;
+}
+// limb i (0..15) of coordinate c of the identity in the limb layout: (1, 1, 0, 0)
+__device__ __forceinline__ uint32_t rows_inf_limb(uint32_t c, uint32_t i) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 13; ++j) r = (c < 2 && i == (uint32_t)j) ? fq30_one_limb(j) : r;
+    return r;
+}
+
+template <int STAGE>
+__global__ __launch_bounds__(STAGE ? ROWS_THREADS1 : ROWS_THREADS0) void msm_rows_planes_kernel(
+    const uint32_t* __restrict__ rsum, const uint32_t* __restrict__ csum, RcShape sh, uint32_t ln1, uint32_t G, uint32_t* part,
+    uint32_t* out) {
+    __shared__ uint32_t buf0[ROWS_MAX_ITEMS * FQR_POINT_WORDS];
+    __shared__ uint32_t buf1[ROWS_MAX_ITEMS / 2 * FQR_POINT_WORDS];
+    const uint32_t plane = STAGE ? blockIdx.x : blockIdx.x / G, g = STAGE ? 0u : blockIdx.x % G;
+    const RowsPlane p = rows_plane(sh, plane, ln1);
+    if (!p.live || g >= p.ng) return;                       // (the whole workgroup: before any barrier)
+    const uint32_t first = g << ln1;
+    const uint32_t valid = STAGE ? p.ng : min(1u << ln1, p.nsel - first);
+    uint32_t n = 1;
+    while (n < valid) n <<= 1;                              // <= ROWS_MAX_ITEMS: n1, G <= 64
+    // the items in the limb layout: a thread builds a limb from two adjacent packed words; the padding is the identity
+    for (uint32_t e = threadIdx.x; e < n * FQR_POINT_WORDS; e += blockDim.x) {
+        const uint32_t k = e >> 6, c = (e >> 4) & 3u, i = e & 15u;
+        const uint32_t* src = nullptr;
+        if (k < valid) src = STAGE ? part + ((uint64_t)plane * 64 + k) * 48 : rows_item(sh, p, rsum, csum, first + k);
+        buf0[e] = src ? fqr_limb_of_words(src + c * 12, i) : rows_inf_limb(c, i);
+    }
+    const uint32_t wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    uint32_t* cur = buf0;
+    uint32_t* nxt = buf1;
+#pragma unroll 1
+    for (uint32_t cnt = n; cnt > 1; cnt >>= 1) {
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t a = wave; a < cnt / 2; a += nwaves)
+            g1_add_rows<RowsDev>(cur + (2 * a) * FQR_POINT_WORDS, cur + (2 * a + 1) * FQR_POINT_WORDS, nxt + a * FQR_POINT_WORDS);
+        uint32_t* t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    __syncthreads();
+    // row r of the first wavefront normalises and packs coordinate r
+    uint32_t* dst = STAGE ? out + (uint64_t)plane * 48 : part + ((uint64_t)plane * 64 + g) * 48;
+    if (wave == 0) fqr_store_rows<RowsDev>(dst, cur[threadIdx.x]);
+}
+
+// the shapes the row-form planes take: cl, ch >= 6 and at most 2^12 items to a plane
+static bool msm_rows_ok(const RcShape& sh) {
+    const uint32_t lmax = sh.ch > sh.cl ? sh.ch : sh.cl;
+    return sh.ch >= 6 && sh.cl >= 6 && lmax - (sh.top_v == 0 ? 1u : 0u) <= 12;
+}
+
+// rows = false: the planes by msm_rc2_planes_kernel, one thread per point (the form before the row kernels; the harness
+// csrc/harness/device_reduce_rows.hip runs both on the same buckets)
+void launch_msm_rc_reduce_form(const uint32_t* buckets, const RcShape& sh, uint32_t* pb, uint32_t* pa, uint32_t* sums,
+                               uint32_t* bitsum, uint32_t* out, bool rows, hipStream_t s) {
     const uint32_t nrow = sh.nsets << (sh.c1 - sh.llc), ncol = sh.nsets << (sh.c1 - sh.lhc);
     const uint32_t nrow_pad = (nrow + 63) & ~63u;
     hipLaunchKernelGGL(msm_rc_partial_kernel, dim3((nrow_pad + ncol + 63) / 64), dim3(64), 0, s, buckets, sh, nrow, nrow_pad,
@@ -271,6 +378,16 @@ void launch_msm_rc_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* 
     const FoldSeg a = seg(pb, rsum, nrow, sh.cl - sh.llc), b = seg(pa, csum, ncol, sh.ch - sh.lhc);
     const uint32_t ba = (a.threads + 63) / 64, bb = (b.threads + 63) / 64;
     hipLaunchKernelGGL(msm_fold_seq_kernel, dim3((ba + bb + 3) / 4), dim3(256), 0, s, a, b, ba, ba + bb);
+    if (rows && msm_rows_ok(sh)) {
+        // the bit planes of the R + C sums, one addition per wavefront: groups of n1 items, then the groups of a plane
+        const uint32_t lmax = (sh.ch > sh.cl ? sh.ch : sh.cl) - (sh.top_v == 0 ? 1u : 0u);   // log2 of the most items a plane sums
+        const uint32_t ln1 = lmax > 10 ? lmax - 6 : 4;
+        const uint32_t G = lmax > ln1 ? 1u << (lmax - ln1) : 1u;
+        const uint32_t nplanes = sh.nsets * 2 * RC_NB;
+        hipLaunchKernelGGL(msm_rows_planes_kernel<0>, dim3(nplanes * G), dim3(ROWS_THREADS0), 0, s, rsum, csum, sh, ln1, G, bitsum, out);
+        hipLaunchKernelGGL(msm_rows_planes_kernel<1>, dim3(nplanes), dim3(ROWS_THREADS1), 0, s, rsum, csum, sh, ln1, G, bitsum, out);
+        return;
+    }
     if (sh.ch >= 6 && sh.cl >= 6) {
         // the bit planes of the R + C sums in ONE launch (msm_rc2_planes_kernel with one "partial" per row / column):
         // a workgroup per (set, kind, bit) butterfly-sums the selected sums per wavefront and across wavefronts
@@ -284,6 +401,11 @@ void launch_msm_rc_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* 
     const uint32_t wps = (sh.ch + 1) * rw + (sh.cl + 1) * cw;
     hipLaunchKernelGGL(msm_rc_bits_kernel, dim3(sh.nsets * wps), dim3(64), 0, s, sums, sh, rw, cw, bitsum);
     hipLaunchKernelGGL(msm_rc_final_kernel, dim3(sh.nsets * 2 * RC_NB), dim3(64), 0, s, bitsum, sh, rw, cw, out);
+}
+
+void launch_msm_rc_reduce(const uint32_t* buckets, const RcShape& sh, uint32_t* pb, uint32_t* pa, uint32_t* sums,
+                          uint32_t* bitsum, uint32_t* out, hipStream_t s) {
+    launch_msm_rc_reduce_form(buckets, sh, pb, pa, sums, bitsum, out, true, s);
 }
 
 }  // namespace ty
