@@ -754,6 +754,52 @@ int typlonk_witness_solve(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t 
                           const uint32_t* cells, size_t n_cells, const uint64_t* values,
                           const typlonk_buf* const* pi, const size_t* pi_len, size_t count, typlonk_buf* const* wire_out);
 
+/* ---- hints: advice the solve computes -------------------------------------------------------------------------------------------
+ * A circuit written for general selectors needs values that are no row's output: the bits of a computed value (a range check, a
+ * comparison), the inverse of a computed value (a non-zero or an equality test).  A HINT says: this free class's value is
+ * f(the value of that cell).  The solve schedules it as one more entry of its level lists, so the caller need not evaluate the
+ * circuit on the host to know the advice.
+ *   install     the hints are kept with the circuit; a call replaces the whole set; n_hints = 0 removes them (hints may then be
+ *               NULL).  Freed by typlonk_circuit_free / typlonk_destroy.  The call builds the solve plan under `cosets` at once,
+ *               so every refusal is reported here.  Blocks, never a collective, no SRS, works on a sharded context.
+ *   dst, src    flat cells col * n + row.  dst names a FREE class, and every cell of that class gets the hint's value.  src is read
+ *               as the value the solve writes to that very cell: for the c cell of a driven row that is not its class's driver
+ *               that is the row's own computed value, as src[] of the solve already says.  src may lie in a driven, a free or a
+ *               hinted class.
+ *   kinds       TYPLONK_HINT_INV0: dst = 1 / src, and 0 when src = 0 mod r; Montgomery in and out, canonical (shift and width are
+ *               not read).  TYPLONK_HINT_BITS: the value leaves Montgomery form, bits [shift, shift + width) of the integer in
+ *               [0, r) are taken, and that integer (below 2^64) is stored as a canonical Montgomery residue; shift in 0..254,
+ *               width in 1..64; bits 255 and above read as 0.
+ *   levels      a hint's level is 1 + the level of its source, a free, unhinted source being level 0; a row counts a hinted
+ *               source with the hint's level.  Within a level the rows come first, then the hints; a level's width, for the
+ *               256-entry decision between a run and a wide launch, is rows + hints.  typlonk_solve_info keeps its layout:
+ *               depth and launches include the hints' levels, driven_rows counts rows only, free_classes still counts every
+ *               class without a driver, hinted ones included.  For a circuit without hints every word of the info and of the
+ *               output is what it is without this call.
+ *   refusals    all TYPLONK_ERR_INVALID_ARG, and typlonk_last_error names the lowest offending hint as hints[i]: NULL hints with
+ *               n_hints != 0, an unknown circuit or a malformed one (as the solve refuses it), an unknown kind, dst or src >= 3n,
+ *               for BITS a width outside 1..64 or a shift > 254, dst in a driven class, two hints into one class (the higher one
+ *               is named, with the lower).  A dependency cycle is refused too -- src in dst's own class, two hints reading each
+ *               other, a hint reading a row that reads the hint: the text names the lowest row that could not be scheduled, or,
+ *               if every row could be, the lowest such hint.  A refused call leaves the installed hints, the cached plan and the
+ *               context as they were.
+ *   at solve    a cell of `cells` in a hinted class is refused: TYPLONK_ERR_INVALID_ARG, "cells[i] lies in a hinted class: its
+ *               value is computed".  Nothing else of typlonk_witness_solve changes.  The solve never papers over a hint the
+ *               circuit then contradicts: if x = 0 feeds INV0 and a row demands x * inv = 1, typlonk_witness_check names the row.
+ * Cost: a hint's value goes to a table of count * n_hints * 32 bytes in the call's workspace and is read from there by later
+ * levels and the fill; 16 bytes per hint are kept on the device with the plan.  A circuit with hints runs kernels of its own
+ * (the row path of a circuit without hints is the code it was).  An INV0 hint is about 25 rounds of 30 divsteps, some 60 times
+ * the work of a row, and a wavefront that holds one runs them for all its lanes; a BITS hint costs two Montgomery products.
+ * Measured (MI355X): 2^20 rows of 16-bit range checks, 524,272 BITS hints among them, solve in 0.57 ms for one
+ * witness (the one-thread CPU fill and upload: 43 ms).  In a narrow run every level that holds an INV0 hint adds the inversion's
+ * latency to the level's: 29 us per level of dependent inverses against 4.5 us per level of rows.  A deep chain of inverses is
+ * latency-bound like the deep circuits above, only six times more so: fill such a circuit on the CPU. */
+#define TYPLONK_HINT_INV0 1u  /* dst = 1 / src, and 0 when src = 0 mod r                                              */
+#define TYPLONK_HINT_BITS 2u  /* dst = (the canonical integer of src mod r, >> shift) & (2^width - 1), as a residue     */
+typedef struct typlonk_hint { uint32_t kind, dst, src; uint16_t shift, width; } typlonk_hint;   /* 16 bytes */
+int typlonk_circuit_set_hints(typlonk_ctx* ctx, uint32_t circuit_id, const uint64_t cosets[3][4],
+                              const typlonk_hint* hints, size_t n_hints);
+
 /* ---- wire format: compact proofs, verifying keys and SRS points as bytes, with compressed points ------------------------
  * Everything above works on in-memory arkworks limbs that the caller is trusted to have formed.  The byte forms below are
  * what leaves the process -- and what comes in from a peer that is NOT trusted: every decoded point is checked to lie on

@@ -574,6 +574,18 @@ impl Backend {
         info
     }
 
+    /// `typlonk_circuit_set_hints`: the advice the solve computes itself -- `TYPLONK_HINT_INV0` (dst = 1 / src, 0 for 0) and
+    /// `TYPLONK_HINT_BITS` (a window of at most 64 bits of src's integer).  `dst` names a free class, `src` any cell; both
+    /// are flat indices col * n + row.  Replaces the circuit's whole set; an empty slice removes it.  Panics for a refused
+    /// set (a hint into a driven class, two into one class, a dependency cycle ...), which leaves the installed one in force.
+    pub fn set_hints(&self, circuit: CircuitHandle, hints: &[ffi::TyplonkHint], cosets: [Fr; 3]) {
+        let k = [fr_limbs(&cosets[0]), fr_limbs(&cosets[1]), fr_limbs(&cosets[2])];
+        self.check(unsafe {
+            ffi::typlonk_circuit_set_hints(self.ctx, circuit.id, k.as_ptr(), if hints.is_empty() { ptr::null() } else { hints.as_ptr() },
+                                           hints.len())
+        });
+    }
+
     /// `typlonk_witness_solve`: the three wire columns of `values.len()` witnesses from the circuit's inputs, computed on
     /// the device (`C::run(ComputeVar..)` of the reference, builder.rs:381-396).  `cells`: the flat indices col * n + row of
     /// the assigned cells -- the inputs and, if wanted, the three blinding rows -- shared by all witnesses; `values[k]`: their

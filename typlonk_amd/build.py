@@ -12,6 +12,8 @@
   tests/cpp/ntt_plan_host         host build of ntt_plan, every decision of a batch of NTTs, a program of its own (tests/test_ntt_plan_host.py) -- g++
   tests/cpp/solve_plan_host[_san] host build of solve_plan, every decision of a witness solve, a program of its own, once plain and once under the
                                   address and undefined-behaviour sanitizers (tests/test_solve_plan_host.py) -- g++
+  tests/cpp/solve_hints_host[_san] the same header with hints (typlonk_circuit_set_hints): the hinted plan, plain and sanitized
+                                  (tests/test_solve_hints_host.py) -- g++
   tests/cpp/prove_plan_host[_san] host build of prove_plan, where a proof's data lives and what each workspace of a prover call holds, a program of its
                                   own, once plain and once under the address and undefined-behaviour sanitizers (tests/test_prove_plan_host.py) -- g++
   tests/cpp/madd_acc_host[_san]   host build of g1_madd_acc / g1_acc_finish, the accumulation loops' mixed addition, a program of its own, once plain
@@ -262,6 +264,18 @@ def build_madd_acc_host(force: bool = False, sanitize: bool = False) -> str:
     return out
 
 
+def build_solve_hints_host(force: bool = False, sanitize: bool = False) -> str:
+    """tests/cpp/solve_hints_host: solve_plan with hints (csrc/solve_plan.hpp) as the host compiles it, printing the hinted plan of each
+    circuit it reads; sanitize: the same program as tests/cpp/solve_hints_host_san, compiled with -fsanitize=address,undefined"""
+    src = os.path.join(ROOT, "tests", "cpp", "solve_hints_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "solve_hints_host_san" if sanitize else "solve_hints_host")
+    deps = [src, os.path.join(CSRC, "solve_plan.hpp")]
+    if force or _stale(out, deps):
+        extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+        _run(["g++", *extra, "-std=c++17", src, "-o", out])
+    return out
+
+
 def build_fq30_rows_host(force: bool = False, sanitize: bool = False) -> str:
     """tests/cpp/fq30_rows_host: csrc/fq30_rows.hpp as the host compiles it (the wave an array of 64), run over the commands it reads;
     sanitize: the same program as tests/cpp/fq30_rows_host_san, compiled with -fsanitize=address,undefined"""
@@ -308,9 +322,11 @@ def build_host_tests(force: bool = False) -> list[str]:
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
                  "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
-                 "test_circuit_pairs_host", "test_witness_solve_host"):
+                 "test_circuit_pairs_host", "test_witness_solve_host", "test_witness_hints_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
+        if name == "test_witness_hints_host" and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
+            continue
         if force or _stale(out, [src] + hdr):
             _run(["g++", "-O2", "-std=c++17", src, "-o", out, "-L", os.path.join(ROOT, "typlonk_amd"), "-ltyplonk_hip",
                   "-Wl,-rpath," + os.path.join(ROOT, "typlonk_amd"), "-Wl,-rpath,$ORIGIN/../../typlonk_amd"])
@@ -352,6 +368,9 @@ def build_all(force: bool = False) -> None:
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "solve_plan_host.cpp")):
         build_solve_plan_host(force)
         build_solve_plan_host(force, sanitize=True)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "solve_hints_host.cpp")):
+        build_solve_hints_host(force)
+        build_solve_hints_host(force, sanitize=True)
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "fq30_rows_host.cpp")):
         build_fq30_rows_host(force)
         build_fq30_rows_host(force, sanitize=True)

@@ -39,7 +39,7 @@ SYMBOLS = [
     "typlonk_circuit_permutation", "typlonk_witness_check", "typlonk_witness_check_host",
     "typlonk_circuit_compile", "typlonk_circuit_compile_host",
     "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
-    "typlonk_witness_solve_plan", "typlonk_witness_solve",
+    "typlonk_witness_solve_plan", "typlonk_witness_solve", "typlonk_circuit_set_hints",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -102,6 +102,17 @@ class WitnessReport(C.Structure):
 
 
 CELL_NONE = 0xFFFFFFFF   # TYPLONK_CELL_NONE
+
+
+HINT_INV0, HINT_BITS = 1, 2   # TYPLONK_HINT_*
+
+
+class Hint(C.Structure):
+    """typlonk_hint"""
+    _fields_ = [("kind", C.c_uint32), ("dst", C.c_uint32), ("src", C.c_uint32), ("shift", C.c_uint16), ("width", C.c_uint16)]
+
+
+HINT_DTYPE = np.dtype([("kind", "<u4"), ("dst", "<u4"), ("src", "<u4"), ("shift", "<u2"), ("width", "<u2")])   # typlonk_hint, 16 bytes
 
 
 class SolveInfo(C.Structure):
@@ -371,6 +382,8 @@ def load_library() -> C.CDLL:
         lib.typlonk_witness_solve_plan.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(SolveInfo)]
         lib.typlonk_witness_solve.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), u32p, C.c_size_t, u64p, C.POINTER(vp),
                                               C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(vp)]
+    if hasattr(lib, "typlonk_circuit_set_hints") or not os.environ.get("TYPLONK_LIB_PATH"):
+        lib.typlonk_circuit_set_hints.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Hint), C.c_size_t]
     _lib = lib
     return lib
 
@@ -1243,6 +1256,18 @@ class Context:
         self._chk(self.lib.typlonk_witness_solve_plan(self.h, circuit, C.byref(_cosets_arg(cosets)), C.byref(info)))
         return {"driven_rows": int(info.driven_rows), "free_classes": int(info.free_classes), "depth": int(info.depth),
                 "launches": int(info.launches)}
+
+    def circuit_set_hints(self, circuit: int, cosets, hints) -> None:
+        """typlonk_circuit_set_hints: hints = (kind, dst, src, shift, width) tuples (kind HINT_INV0 or HINT_BITS; dst, src flat
+        cells); replaces the circuit's whole set, an empty list removes it.  The solve plan is built at once: every refusal is
+        raised here, and a refused call leaves the installed hints in force.  A numpy array of HINT_DTYPE is passed as it is."""
+        if isinstance(hints, np.ndarray):
+            keep = np.ascontiguousarray(hints, dtype=HINT_DTYPE)
+            arr = keep.ctypes.data_as(C.POINTER(Hint))
+        else:
+            arr = (Hint * max(len(hints), 1))(*[Hint(*[int(v) for v in h]) for h in hints])
+        self._chk(self.lib.typlonk_circuit_set_hints(self.h, circuit, C.byref(_cosets_arg(cosets)), arr if len(hints) else None,
+                                                     len(hints)))
 
     def witness_solve(self, circuit: int, cosets, cells, values, wire_out, pi=None, pi_len=None) -> None:
         """typlonk_witness_solve: cells = the flat indices of the assigned cells (shared by all witnesses); values = a

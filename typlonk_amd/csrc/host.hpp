@@ -15,7 +15,7 @@
 //   verify.hip    typlonk_verify, typlonk_verify_compact (the prover of the compact shape is in prover.hip); which scalars and
 //                 points they and the wire format admit: host_checks.hpp; the linearisation commitment: lin_commit.hpp
 //   witness_solve.hip  typlonk_witness_solve: the wire columns of a witness from the circuit's inputs, level by level
-//                 (solve_plan.hpp: every decision, no device needed)
+//                 (solve_plan.hpp: every decision, no device needed); typlonk_circuit_set_hints: advice the solve computes
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
 //                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
@@ -105,7 +105,11 @@ struct CircuitEntry {
         uint32_t* d_order = nullptr;    // driven rows
         uint32_t* d_level_off = nullptr;  // depth + 1
         Fr* d_qo_inv = nullptr;         // n : 2^28 / q_o of a driven row, zero elsewhere
+        void* d_hints = nullptr;        // the plan's hints as the kernels read them (witness_solve.hip), null without hints
+        uint32_t n_hints = 0;           //   (= hints.size() of the entry when the cache was built)
     } solve;
+    // typlonk_circuit_set_hints: the installed hints; every plan of this circuit is built under them
+    std::vector<SolveHint> hints;
 };
 
 struct ProfStage {

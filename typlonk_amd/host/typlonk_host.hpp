@@ -956,6 +956,17 @@ class CompiledCircuit {
         release();
         check(rc, c);
     }
+    // The advice solve_witness computes itself (typlonk_circuit_set_hints): each hint fills the free class of cell `dst` with
+    // 1 / x (TYPLONK_HINT_INV0; 0 for x = 0) or with bits [shift, shift + width) of x (TYPLONK_HINT_BITS), x being the value the
+    // solve writes to cell `src`.  Replaces the circuit's whole set; an empty vector removes it.  Throws for a refused set (a hint
+    // into a driven class, two into one class, a dependency cycle ...), which leaves the installed one in force.  Cells of a
+    // hinted class are no longer accepted by solve_witness.
+    void set_hints(const std::vector<typlonk_hint>& hints) const {
+        typlonk_ctx* c = srs_.ctx().raw();
+        uint64_t ks[3][4];
+        for (int i = 0; i < 3; ++i) std::memcpy(ks[i], cosets_[i].limbs(), 32);
+        check(typlonk_circuit_set_hints(c, circuit_, ks, hints.empty() ? nullptr : hints.data(), hints.size()), c);
+    }
     // what a solve of this circuit costs: driven rows, free classes, levels and kernel launches (typlonk_witness_solve_plan)
     typlonk_solve_info solve_info() const {
         typlonk_ctx* c = srs_.ctx().raw();
