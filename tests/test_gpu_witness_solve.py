@@ -44,24 +44,27 @@ def _selector_bufs(ctx, q):
 
 class Compiled:
     """a circuit on the device through typlonk_circuit_compile (how="perm"), typlonk_circuit_compile_pairs ("pairs") or
-    typlonk_circuit_load ("load": the permutation is recovered from the sigma values)"""
+    typlonk_circuit_load ("load": the permutation is recovered from the sigma values), under the cosets `cosets` (integers);
+    .cosets = their limbs, which _solve passes on"""
 
-    def __init__(self, ctx, q, perm, how="perm"):
+    def __init__(self, ctx, q, perm, how="perm", cosets=PO.COSETS):
         self.ctx, self.n = ctx, len(perm) // 3
         log_n = self.n.bit_length() - 1
         self.loaded = None
+        self.cosets = [_limbs(k) for k in cosets]
         if how == "load":
             from test_gpu_witness_check import Loaded, _sel_arrays
 
-            self.loaded = Loaded(ctx, log_n, _sel_arrays(q, self.n), perm)
+            self.loaded = Loaded(ctx, log_n, _sel_arrays(q, self.n), perm, cosets)
             self.cid = self.loaded.cid
             return
         sel = _selector_bufs(ctx, q)
         try:
             if how == "pairs":
-                self.cid, _ = ctx.circuit_compile_pairs(log_n, sel, [(x, y) for x, y in enumerate(perm) if x != y] or np.zeros((0, 2)), COSETS)
+                self.cid, _ = ctx.circuit_compile_pairs(log_n, sel, [(x, y) for x, y in enumerate(perm) if x != y] or np.zeros((0, 2)),
+                                                        self.cosets)
             else:
-                self.cid = ctx.circuit_compile(log_n, sel, perm, COSETS)
+                self.cid = ctx.circuit_compile(log_n, sel, perm, self.cosets)
         finally:
             for b in sel:
                 b.free()
@@ -70,10 +73,12 @@ class Compiled:
         self.ctx.circuit_free(self.cid)
 
 
-def _solve(ctx, c, wits, garbage=3):
+def _solve(ctx, c, wits, garbage=3, raw_pi=False):
     """wits = [(assigned {cell: value}, pi)] over one set of cells -> (the solved columns as (n, 4) word arrays per witness, the
-    check's reports on the very buffers)"""
-    n = c.n
+    check's reports on the very buffers).  The public values are residues, uploaded as their canonical words; with raw_pi they
+    are raw values below 2^256 and go up as they are (a word w stands for w * 2^-256 mod r), with the largest words behind
+    them.  Solve and check run under c.cosets."""
+    n, cosets = c.n, c.cosets
     cells = sorted(wits[0][0])
     values = np.stack([fr_pack([a[x] % R for x in cells]) if cells else np.zeros((0, 4), dtype=np.uint64) for a, _ in wits])
     fill = np.full((n, 4), GARBAGE, dtype=np.uint64)
@@ -87,12 +92,15 @@ def _solve(ctx, c, wits, garbage=3):
             pb = None
             if len(pi):
                 pb = ctx.alloc(len(pi) + garbage)
-                pb.upload(W.mont_words(list(pi) + [0xBAD] * garbage))
+                if raw_pi:
+                    pb.upload(W.raw_words(list(pi) + [(1 << 256) - 1 - i for i in range(garbage)]))
+                else:
+                    pb.upload(W.mont_words(list(pi) + [0xBAD] * garbage))
             pibs.append(pb)
         lens = [len(pi) for _, pi in wits]
-        ctx.witness_solve(c.cid, COSETS, cells, values, outs, pibs, lens)
+        ctx.witness_solve(c.cid, cosets, cells, values, outs, pibs, lens)
         got = [[b.download() for b in bs] for bs in outs]
-        reports = ctx.witness_check(c.cid, outs, pibs, lens, COSETS, cap=8)
+        reports = ctx.witness_check(c.cid, outs, pibs, lens, cosets, cap=8)
         return got, reports
     finally:
         for b in [b for bs in outs for b in bs] + [b for b in pibs if b is not None]:

@@ -147,6 +147,42 @@ def solve(q, perm, hints, assigned, pi=()):
     return [cells[:n], cells[n:2 * n], cells[2 * n:]]
 
 
+def solve_many(q, perm, hints, wits):
+    """[solve(q, perm, hints, assigned, pi) for assigned, pi in wits], with the work that belongs to the circuit and its hints
+    (the sources, the levels, the order of rows and hints, one modular inverse per driven row) done once for all of them"""
+    n = len(q["q_o"])
+    src, free = sources(q, perm, hints)
+    level, hint_level = levels(q, perm, hints)
+    nodes = sorted([(level[j], j) for j in range(n) if level[j]] + [(hint_level[h], n + h) for h in range(len(hints))])
+    steps = []
+    for _, v in nodes:
+        if v >= n:
+            kind, _, frm, shift, width = hints[v - n]
+            steps.append((v, src[frm], kind, shift, width))
+        else:
+            steps.append((v, src[v], src[n + v], q["q_l"][v], q["q_r"][v], q["q_m"][v], q["q_c"][v], pow(q["q_o"][v], -1, R)))
+    out = []
+    for assigned, pi in wits:
+        slot = [0] * free
+        for x, v in assigned.items():
+            if not src[x] & FREE or is_hint(src[x]):
+                raise ValueError(f"cell {x} lies in a computed class")
+            slot[src[x] & ~FREE] = v % R
+        c, hv = [0] * n, [0] * len(hints)
+        value = lambda s: (hv[s & ~HINT] if is_hint(s) else slot[s & ~FREE]) if s & FREE else c[s]   # noqa: E731
+        for step in steps:
+            if step[0] >= n:
+                v, frm, kind, shift, width = step
+                hv[v - n] = hint_value(kind, value(frm), shift, width)
+            else:
+                j, sa, sb, ql, qr, qm, qc, inv = step
+                a, b = value(sa), value(sb)
+                c[j] = (ql * a + qr * b + qm * a * b + qc + (pi[j] if j < len(pi) else 0)) * inv % R
+        cells = [value(s) for s in src]
+        out.append([cells[:n], cells[n:2 * n], cells[2 * n:]])
+    return out
+
+
 # ---- circuits ------------------------------------------------------------------------------------------------------------------
 def _perm_of(n, classes):
     perm = list(range(3 * n))
@@ -264,3 +300,65 @@ def stacked(log_n, seed, shape, inputs=5):
     assigned = {classes[v][0]: rng.randrange(1, R) for v in range(inputs - 1) if classes[v]}
     assigned.update(S.blinding_cells(n))
     return {"n": n, "q": q, "perm": _perm_of(n, classes), "hints": hints, "assigned": assigned, "shape": list(shape)}
+
+
+def hint_wall(log_n, seed, rows=1000, mixed=37, n_hints=3041, run=130, readers=300, inputs=6):
+    """three wide levels around a level of thousands of hints.  Level 1: `rows` rows over the inputs.  Level 2: `mixed` rows over
+    the outputs of level 1, then `n_hints` hints, each of an output of level 1: hint h < rows is a BITS of output h, so every
+    output feeds one; the next `run` are INV0, the `run` after them BITS, the rest INV0 or BITS by a seeded coin; a BITS hint h
+    takes the window BIT_WINDOWS[h mod 12].  Level 3: `readers` rows whose operands are hint values.  Each hint writes the a cell
+    of an otherwise empty row of its own; selectors are uniform non-zero on driven rows; row order is shuffled.  Three sets of
+    inputs: under the last one the output that hint `zero_hint` (an INV0 inside the run) reads is 0, by that row's q_c -- the row
+    is `zero_row`, and a public value there would undo it.
+    Returns a dict: n, q, perm, hints, assigned (three {cell: value}), zero_row, zero_hint."""
+    rng = random.Random(seed)
+    n = 1 << log_n
+    g = n - 3
+    assert rows + mixed + n_hints + readers <= g and rows + 2 * run <= n_hints
+    pos = list(range(g))
+    rng.shuffle(pos)
+    q = _zero_q(n)
+    classes = [[] for _ in range(inputs)]          # variable -> its cells; an output's first cell is its row's c cell
+    ops, at = {}, iter(pos)
+
+    def driven(va, vb):
+        j = next(at)
+        classes[va].append(j)
+        classes[vb].append(n + j)
+        for name in W.SELECTORS:
+            q[name][j] = rng.randrange(1, R)
+        ops[len(classes)] = (j, va, vb)
+        classes.append([2 * n + j])
+        return len(classes) - 1
+
+    outs = [driven(rng.randrange(inputs), rng.randrange(inputs)) for _ in range(rows)]
+    for _ in range(mixed):
+        driven(rng.choice(outs), rng.choice(outs))
+    zero_out, zero_hint = outs[rows // 2], rows + run // 2
+    hints, hint_vars = [], []
+    for h in range(n_hints):
+        j = next(at)
+        if h < rows:
+            kind, v = BITS, outs[h]
+        elif h < rows + run:
+            kind, v = INV0, zero_out if h == zero_hint else rng.choice(outs)
+        elif h < rows + 2 * run:
+            kind, v = BITS, rng.choice(outs)
+        else:
+            kind, v = rng.choice((INV0, BITS)), rng.choice(outs)
+        shift, width = BIT_WINDOWS[h % len(BIT_WINDOWS)] if kind == BITS else (0, 0)
+        hints.append((kind, j, classes[v][0], shift, width))
+        hint_vars.append(len(classes))
+        classes.append([j])
+    for _ in range(readers):
+        driven(rng.choice(hint_vars), rng.choice(hint_vars))
+    assert all(classes[v] for v in range(inputs))
+    assigned = []
+    for _ in range(3):
+        assigned.append({classes[v][0]: rng.randrange(1, R) for v in range(inputs)})
+        assigned[-1].update(S.blinding_cells(n))
+    zero_row, va, vb = ops[zero_out]
+    a, b = assigned[2][classes[va][0]], assigned[2][classes[vb][0]]
+    q["q_c"][zero_row] = -(q["q_l"][zero_row] * a + q["q_r"][zero_row] * b + q["q_m"][zero_row] * a * b) % R
+    return {"n": n, "q": q, "perm": _perm_of(n, classes), "hints": hints, "assigned": assigned, "zero_row": zero_row,
+            "zero_hint": zero_hint}

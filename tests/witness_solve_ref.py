@@ -124,6 +124,31 @@ def solve(q, perm, assigned, pi=()):
     return [cells[:n], cells[n:2 * n], cells[2 * n:]]
 
 
+def solve_many(q, perm, wits):
+    """[solve(q, perm, assigned, pi) for assigned, pi in wits], with the work that belongs to the circuit (the sources, the
+    levels, the order of the rows, one modular inverse per driven row) done once for all of them"""
+    n = len(q["q_o"])
+    src, free = sources(q, perm)
+    level = levels(q, perm)
+    order = sorted((j for j in range(n) if level[j]), key=lambda j: level[j])
+    rows = [(j, src[j], src[n + j], q["q_l"][j], q["q_r"][j], q["q_m"][j], q["q_c"][j], pow(q["q_o"][j], -1, R)) for j in order]
+    out = []
+    for assigned, pi in wits:
+        slot = [0] * free
+        for x, v in assigned.items():
+            if not src[x] & FREE:
+                raise ValueError(f"cell {x} lies in a driven class")
+            slot[src[x] & ~FREE] = v % R
+        c = [0] * n
+        value = lambda s: slot[s & ~FREE] if s & FREE else c[s]   # noqa: E731
+        for j, sa, sb, ql, qr, qm, qc, inv in rows:
+            a, b = value(sa), value(sb)
+            c[j] = (ql * a + qr * b + qm * a * b + qc + (pi[j] if j < len(pi) else 0)) * inv % R
+        cells = [value(s) for s in src]
+        out.append([cells[:n], cells[n:2 * n], cells[2 * n:]])
+    return out
+
+
 # ---- circuits ------------------------------------------------------------------------------------------------------------------
 BLINDERS = [[(7 * i + 3 * j + 11) % R for j in range(3)] for i in range(3)]
 
