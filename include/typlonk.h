@@ -71,7 +71,8 @@ int typlonk_set_stream(typlonk_ctx* ctx, void* hip_stream);
 int typlonk_sync(typlonk_ctx* ctx);
 
 /* ---- SRS: the fixed MSM base vector ([s^i]G, affine), uploaded once per circuit ---------------- */
-/* xy: len*12 limbs; inf: len flag bytes or NULL (= no identity points).  Returns a handle id. */
+/* xy: len*12 limbs; inf: len flag bytes or NULL (= no identity points).  Returns a handle id.  Nothing is validated: points
+ * from outside go through typlonk_srs_check (below, "a powers-of-tau step") before they are used. */
 int typlonk_srs_load(typlonk_ctx* ctx, const uint64_t* xy, const uint8_t* inf, size_t len, uint32_t* srs_id);
 /* Build g1[i] = [secret^(start+i)] G, i < len, on the device (Srs::from_secret, kzg/src/srs.rs:15-34;
  * `start` lets each GPU create only its shard).  secret: 4 limbs (Montgomery).  Setup-time only. */
@@ -853,6 +854,63 @@ int typlonk_srs_load_compressed(typlonk_ctx* ctx, const uint8_t* bytes, size_t l
                                 size_t* first_bad);
 /* typlonk_srs_download as count*48 bytes, compressed on the device. */
 int typlonk_srs_download_compressed(typlonk_ctx* ctx, uint32_t srs_id, size_t offset, size_t count, uint8_t* out);
+
+/* ---- a powers-of-tau step: check a loaded SRS against [s]G2, add a contribution ------------------------------------------
+ * typlonk_srs_load_compressed judges every point on its own and typlonk_srs_load judges nothing.  typlonk_srs_check decides
+ * whether the entry as a whole is g1[i] = [s^i] G for the s of a given [s]G2 -- the one property the provers and verifiers
+ * rely on -- and names the lowest point that breaks it.  An invalid SRS is DATA in the report, not an error of the call.
+ *   membership  one thread per point over the device records every MSM reads: y^2 = x^3 + 4 and the subgroup of order r.
+ *               (A record's coordinates are always canonical: typlonk_srs_load reduces a coordinate >= p mod p, every
+ *               other way to make an entry writes canonical ones.)  An identity record passes; the next two steps deal with it.  The lowest failing
+ *               index, its class and the total number of failing points are reported, and with bad_points != 0 the call
+ *               stops here: nothing that is not a group element is summed or paired.
+ *   P0          point 0 is the fixed G1 generator, word for word (the verifiers subtract y G where a constant commits to
+ *               c P0).  Otherwise TYPLONK_SRS_BAD_P0, and the call stops here.
+ *   ratio       rho = Blake2b-512("typlonk/srs/check/v1" || seed || u64 len || [s]G2 as its 24 limbs), the integers
+ *               little-endian and the digest read as a little-endian integer mod r: the conventions of the compact
+ *               transcript.  With A_k = sum_{i<k} rho^i g1[i] and B_k = sum_{i<k} rho^i g1[i+1] (two MSMs in one batch over
+ *               the entry itself, in table mode where typlonk_srs_precompute has run), prefix k holds when
+ *                   e(A_k, [s]G2) * e(-B_k, G2) = 1        (one pairing product on the host: a "fold")
+ *               The whole SRS is k = len - 1.  If that fails, the least failing prefix is found by bisection on k with the
+ *               same weights, at most ceil(log2 len) more folds, and index = k - 1.  len = 1 runs no fold.
+ *   the seed    The library draws no randomness: the 32 bytes are the caller's.  THE SEED MUST BE UNKNOWN TO WHOEVER PRODUCED
+ *               THE POINTS: someone who knows it can compute rho and craft defects that cancel under these weights.  Draw it
+ *               after the points are fixed.  For a seed chosen independently of the points, a fold accepts a prefix with a
+ *               broken link with probability at most len / r (a non-zero polynomial of degree < len in rho), so both the
+ *               verdict and the bisection's index err with probability at most (1 + ceil(log2 len)) * len / r.
+ *   refusals    TYPLONK_ERR_INVALID_ARG: a null argument, an unknown id, g2s_xy off the twist (as typlonk_verify refuses
+ *               it), an SRS shard -- with or without a communicator.  An empty entry: TYPLONK_ERR_LENGTH.  A refused or failed
+ *               call leaves *report as it was.
+ * Blocks for the result; never a collective.  It uses the MSM lanes and allocations of its own, nothing of a prover's arena,
+ * so it may be made while a round-by-round prover is open (between its round calls).  The two len-element weight vectors
+ * (64 bytes per point together) are allocated by the call and freed on return. */
+#define TYPLONK_SRS_VALID 0
+#define TYPLONK_SRS_BAD_POINT 1   /* a point off the curve or outside the subgroup of order r */
+#define TYPLONK_SRS_BAD_P0 2      /* point 0 is not the fixed G1 generator */
+#define TYPLONK_SRS_BAD_RATIO 3   /* some g1[i+1] != [s] g1[i] for the s of g2s */
+typedef struct typlonk_srs_report {
+    uint32_t verdict;      /* the FIRST class that applies, in the order above */
+    uint32_t point_class;  /* BAD_POINT: TYPLONK_POINT_NOT_ON_CURVE / _NOT_IN_SUBGROUP of the lowest bad point, else 0 */
+    uint64_t index;        /* BAD_POINT: the lowest bad point.  BAD_RATIO: the lowest i with g1[i+1] != [s] g1[i].  else 0 */
+    uint64_t bad_points;   /* how many points fail membership (a total, as the witness check's counts are) */
+    uint32_t folds;        /* pairing products computed */
+} typlonk_srs_report;
+int typlonk_srs_check(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t g2s_xy[24], const uint8_t seed[32],
+                      typlonk_srs_report* report);
+/* Host-only, no GPU: the weight rho the check derives from (seed, len, g2s_xy), as 4 Montgomery limbs.  It hashes the 24
+ * limbs as given (no curve check); a null argument returns TYPLONK_ERR_INVALID_ARG. */
+int typlonk_srs_check_challenge(const uint8_t seed[32], uint64_t len, const uint64_t g2s_xy[24], uint64_t rho[4]);
+/* A new SRS entry new[i] = [t^i] g1[i], i < len (canonical affine records; no tables, no shard), and g2s_out = [t] g2s_in
+ * (on the host): if the old pair was an SRS for s, the new one is an SRS for s t.  t: 4 Montgomery limbs.  The old entry is
+ * untouched (it may hold tables; table 0 is read).  One thread per point: t^i, then 255 doublings and ~128 mixed additions.
+ * The result is [t^i] P by the group law for ANY curve point in a record, points of small order included, and an identity
+ * stays an identity.  The call does not demand a checked input: check first, or check the result.
+ * TYPLONK_ERR_INVALID_ARG: a null argument, an unknown id, t not a canonical residue, t = 0, g2s_in off the twist, an SRS shard
+ * (with or without a communicator), and [t] g2s_in = the identity -- which no g2s_in of order r gives; a twist point of
+ * small order can, and 24 limbs cannot hold the identity; then *new_srs_id and g2s_out are left as they were.  Blocks.  Out of scope: a proof of knowledge of t and the transcript of
+ * a ceremony -- whoever runs one publishes those beside the points. */
+int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4], const uint64_t g2s_in[24],
+                           uint32_t* new_srs_id, uint64_t g2s_out[24]);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -653,6 +653,25 @@ impl Backend {
         self.check(unsafe { ffi::typlonk_srs_download_compressed(self.ctx, srs.id, 0, srs.len, out.as_mut_ptr()) });
         out
     }
+    /// `typlonk_srs_check`: is the SRS `[s^i] G` for the s of `g2s`?  `seed`: 32 bytes that whoever produced the points
+    /// cannot have known (draw them after the points are fixed).  An invalid SRS is the report's `verdict`
+    /// (`TYPLONK_SRS_*`), not a panic; bad arguments panic like everywhere else.
+    pub fn check_srs(&self, srs: SrsHandle, g2s: &[u64; 24], seed: &[u8; 32]) -> ffi::TyplonkSrsReport {
+        let mut report: ffi::TyplonkSrsReport = unsafe { std::mem::zeroed() };
+        self.check(unsafe { ffi::typlonk_srs_check(self.ctx, srs.id, g2s.as_ptr(), seed.as_ptr(), &mut report) });
+        report
+    }
+    /// `typlonk_srs_contribute`: a new SRS `[t^i] P_i` (no tables) and `[t] g2s`; the old SRS is untouched.  Check the
+    /// input before, or the output after: the call itself demands neither.  Unlike the other makers of an `SrsHandle`
+    /// this one builds NO fixed-base tables, whatever the old SRS had: call `precompute_tables` on the returned handle
+    /// if they are wanted.
+    pub fn contribute_srs(&self, srs: SrsHandle, t: &Fr, g2s: &[u64; 24]) -> (SrsHandle, [u64; 24]) {
+        let tl = fr_limbs(t);
+        let mut id = 0u32;
+        let mut out = [0u64; 24];
+        self.check(unsafe { ffi::typlonk_srs_contribute(self.ctx, srs.id, tl.as_ptr(), g2s.as_ptr(), &mut id, out.as_mut_ptr()) });
+        (SrsHandle { id, len: srs.len }, out)
+    }
     /// `typlonk_proof_compact_from_bytes`: `bytes` = count x 656; every point through one kernel launch.  Entry k is the
     /// proof (its challenge fields zero) or why it was refused.
     pub fn proofs_from_bytes(&self, bytes: &[u8], flags: u32) -> Vec<Result<ffi::TyplonkProofCompact, DecodeError>> {

@@ -40,6 +40,7 @@ SYMBOLS = [
     "typlonk_circuit_compile", "typlonk_circuit_compile_host",
     "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
     "typlonk_witness_solve_plan", "typlonk_witness_solve", "typlonk_circuit_set_hints",
+    "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute",
 ]
 VERIFY_PI_AS_PROVER = 1
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
@@ -113,6 +114,15 @@ class Hint(C.Structure):
 
 
 HINT_DTYPE = np.dtype([("kind", "<u4"), ("dst", "<u4"), ("src", "<u4"), ("shift", "<u2"), ("width", "<u2")])   # typlonk_hint, 16 bytes
+
+
+SRS_VALID, SRS_BAD_POINT, SRS_BAD_P0, SRS_BAD_RATIO = 0, 1, 2, 3   # TYPLONK_SRS_*
+
+
+class SrsReport(C.Structure):
+    """typlonk_srs_report"""
+    _fields_ = [("verdict", C.c_uint32), ("point_class", C.c_uint32), ("index", C.c_uint64), ("bad_points", C.c_uint64),
+                ("folds", C.c_uint32)]
 
 
 class SolveInfo(C.Structure):
@@ -384,6 +394,10 @@ def load_library() -> C.CDLL:
                                               C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(vp)]
     if hasattr(lib, "typlonk_circuit_set_hints") or not os.environ.get("TYPLONK_LIB_PATH"):
         lib.typlonk_circuit_set_hints.argtypes = [vp, C.c_uint32, C.POINTER((C.c_uint64 * 4) * 3), C.POINTER(Hint), C.c_size_t]
+    if hasattr(lib, "typlonk_srs_check") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_srs_check.argtypes = [vp, C.c_uint32, u64p, u8p, C.POINTER(SrsReport)]
+        lib.typlonk_srs_check_challenge.argtypes = [u8p, C.c_uint64, u64p, u64p]
+        lib.typlonk_srs_contribute.argtypes = [vp, C.c_uint32, u64p, u64p, C.POINTER(C.c_uint32), u64p]
     _lib = lib
     return lib
 
@@ -559,6 +573,25 @@ def transcript_challenges(points, n: int):
     return [out[i].copy() for i in range(n)]
 
 
+def _seed_arg(seed) -> np.ndarray:
+    a = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    if a.size != 32:
+        raise ValueError("the seed of an SRS check is 32 bytes")
+    return a
+
+
+def srs_check_challenge(seed, length: int, g2s_xy) -> np.ndarray:
+    """typlonk_srs_check_challenge (host-only): the weight rho typlonk_srs_check derives from (seed, len, [s]G2), 4 Montgomery limbs"""
+    lib = load_library()
+    s = _seed_arg(seed)
+    g = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
+    out = np.zeros(4, dtype=np.uint64)
+    rc = lib.typlonk_srs_check_challenge(_u8p(s), length, _u64p(g), _u64p(out))
+    if rc:
+        raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
+    return out
+
+
 class DeviceBuffer:
     """typlonk_buf: a device-resident vector of Fr elements."""
 
@@ -680,6 +713,26 @@ class Context:
         out = np.zeros(max(count, 1) * G1_BYTES, dtype=np.uint8)
         self._chk(self.lib.typlonk_srs_download_compressed(self.h, sid, offset, count, _u8p(out)))
         return out[:count * G1_BYTES].tobytes()
+
+    def srs_check(self, sid: int, g2s_xy, seed) -> dict:
+        """typlonk_srs_check: is entry `sid` [s^i] G for the s of g2s_xy (24 limbs)?  seed: 32 bytes that whoever made the points
+        cannot have known.  Returns {"verdict": SRS_*, "point_class", "index", "bad_points", "folds"}; an invalid SRS is a
+        verdict, not an exception."""
+        g = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
+        s = _seed_arg(seed)
+        rep = SrsReport()
+        self._chk(self.lib.typlonk_srs_check(self.h, sid, _u64p(g), _u8p(s), C.byref(rep)))
+        return {"verdict": rep.verdict, "point_class": rep.point_class, "index": rep.index, "bad_points": rep.bad_points,
+                "folds": rep.folds}
+
+    def srs_contribute(self, sid: int, t_limbs, g2s_xy):
+        """typlonk_srs_contribute: (new sid holding [t^i] P_i, [t] g2s as 24 limbs); t as 4 Montgomery limbs"""
+        t = np.ascontiguousarray(t_limbs, dtype=np.uint64).reshape(4)
+        g = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
+        new = C.c_uint32()
+        out = np.zeros(24, dtype=np.uint64)
+        self._chk(self.lib.typlonk_srs_contribute(self.h, sid, _u64p(t), _u64p(g), C.byref(new), _u64p(out)))
+        return new.value, out
 
     def g1_decompress(self, data, skip_subgroup: bool = False):
         """g1_decompress on this context's device"""

@@ -126,5 +126,13 @@ void launch_fq_inv_selftest(uint64_t seed, uint32_t threads, uint32_t per_thread
 size_t srs_comb_bytes();
 void launch_srs_comb(uint32_t* comb, hipStream_t st);
 void launch_srs_generate(const Fr& s, uint64_t start, uint64_t n, const uint32_t* comb, uint32_t* pts, hipStream_t st);
+// typlonk_srs_check / typlonk_srs_contribute (kernels: srs_gen.hip; host: srs_check.hip)
+// out: three 64-bit words -- {all ones, 0, 0} going in; {min (index << 8 | class) of the failing points, their number,
+// 1 when record 0 is not the fixed generator} coming out
+void launch_srs_membership(const uint32_t* pts, uint64_t n, unsigned long long* out, hipStream_t st);
+// pw[i] = rho^i, pw_shift[i] = rho^(i - 1) with pw_shift[0] = 0; n elements each
+void launch_fr_powers(const Fr& rho, uint64_t n, Fr* pw, Fr* pw_shift, hipStream_t st);
+// dst[i] = [t^i] src[i], canonical affine records; src and dst must not overlap
+void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st);
 
 }  // namespace ty

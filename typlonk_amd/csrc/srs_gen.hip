@@ -4,6 +4,7 @@
 // can create 2^20..2^22-point SRS shards directly in HBM.
 #include "launch.hpp"
 #include "msm_common.hpp"
+#include "point_codec.hpp"
 
 namespace ty {
 
@@ -231,6 +232,109 @@ void launch_srs_generate(const Fr& s, uint64_t start, uint64_t n, const uint32_t
     a.comb = comb;
     a.pts = pts;
     hipLaunchKernelGGL(srs_generate_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
+}
+
+// ---- typlonk_srs_check / typlonk_srs_contribute (srs_check.hip) -------------------------------------------------------------
+// b^ex by the 64-step ladder of srs_generate_kernel
+__device__ __forceinline__ Fr fr_pow_u64(const Fr& b, uint64_t ex) {
+    Fr e = Fr::one();
+#pragma unroll 1
+    for (int bit = 63; bit >= 0; --bit) {
+        e = fe_sqr(e);
+        if ((ex >> bit) & 1) e = fe_mul(e, b);
+    }
+    return e;
+}
+
+// Membership of every record of an SRS entry, one thread per point: on y^2 = x^3 + 4 (else
+// PC_NOT_ON_CURVE) and in the subgroup of order r (g1_in_subgroup, point_codec.hpp; else PC_NOT_IN_SUBGROUP).  An identity
+// record passes.  out[0] <- min over the failing points of (index << 8 | class) (the caller sets it to all ones),
+// out[1] += the number of failing points (one ballot per wavefront, one atomic add), out[2] <- 1 when record 0 is not the
+// fixed generator word for word (the caller clears both).  No lane leaves before the ballot.
+__global__ __launch_bounds__(64) void srs_membership_kernel(const uint32_t* pts, uint64_t n, unsigned long long* out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = i < n;
+    const G1Affine p = ld_affine(pts, live ? i : n - 1);
+    uint32_t st = PC_OK;
+    if (live && !p.is_inf()) {
+        // (coordinates are canonical in every record: the generator, the decoder and the contribution write them so, and
+        // typlonk_srs_load reduces what it is given -- fq30_from_ark, msm_convert_points_kernel)
+        const Fq30 four = fq30_mulk_lazy<2>(fq30_mulk_lazy<2>(fq30_one()));                // < 4.1
+        const Fq30 rhs = fq30_add_lazy(fq30_mul(fq30_sqr(p.x), p.x), four);                // x^3 + 4 < 5.2
+        if (!pc_eq_mod(fq30_sqr(p.y), rhs)) st = PC_NOT_ON_CURVE;
+        else if (!g1_in_subgroup(p.x, p.y)) st = PC_NOT_IN_SUBGROUP;
+    }
+    if (i == 0) {
+        Fq30 gx, gy;
+        g1_generator(gx, gy);
+        bool same = true;
+#pragma unroll
+        for (int l = 0; l < 13; ++l) same = same && p.x.v[l] == gx.v[l] && p.y.v[l] == gy.v[l];
+        if (!same) out[2] = 1ull;
+    }
+    const unsigned long long bad = __ballot(st != PC_OK);
+    if (st != PC_OK) atomicMin(&out[0], (unsigned long long)((i << 8) | st));
+    if (threadIdx.x == 0 && bad) atomicAdd(&out[1], (unsigned long long)__popcll(bad));
+}
+void launch_srs_membership(const uint32_t* pts, uint64_t n, unsigned long long* out, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(srs_membership_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pts, n, out);
+}
+
+// The weights of the ratio test: pw[i] = rho^i and pw_shift[i] = rho^(i - 1), pw_shift[0] = 0 (n elements each), so that
+// the first k entries of pw weigh P_0 .. P_(k-1) and the first k + 1 entries of pw_shift weigh P_1 .. P_k alike.
+__global__ __launch_bounds__(256) void fr_powers_kernel(Fr rho, uint64_t n, Fr* pw, Fr* pw_shift) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Fr e = fr_pow_u64(rho, i);
+    pw[i] = e;
+    if (i == 0) pw_shift[0] = Fr::zero();
+    if (i + 1 < n) pw_shift[i + 1] = e;
+}
+void launch_fr_powers(const Fr& rho, uint64_t n, Fr* pw, Fr* pw_shift, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(fr_powers_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rho, n, pw, pw_shift);
+}
+
+// dst[i] = [t^i] src[i], canonical affine, one thread per point: t^i by the ladder above, then 255 steps of doubling and
+// mixed addition, most significant bit first (r < 2^255).  The base is whatever the record holds: g1_madd_xy's equal and
+// opposite branches make the result [k]P by the group law for every curve point, those of small order included; an identity
+// stays one.  Spare lanes shadow the last point and skip only the store (srs_generate_kernel: the inversion's exit test is
+// wave-uniform).
+struct SrsContributeArgs {
+    Fr t;
+    uint64_t n;
+    const uint32_t* src;
+    uint32_t* dst;
+};
+__global__ __launch_bounds__(64) void srs_contribute_kernel(SrsContributeArgs a) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t i = i0 < a.n ? i0 : a.n - 1;
+    const Fr k = fe_from_mont(fr_pow_u64(a.t, i));
+    const G1Affine p = ld_affine(a.src, i);
+    G1Xyzz acc = G1Xyzz::inf();
+#pragma unroll 1
+    for (int bit = 254; bit >= 0; --bit) {
+        acc = g1_dbl(acc);
+        uint32_t word = 0;   // (a select over the eight words: no indexed private array, no scratch)
+#pragma unroll
+        for (int w = 0; w < 8; ++w) word = (bit >> 5) == w ? k.v[w] : word;
+        if ((word >> (bit & 31)) & 1u) g1_madd(acc, p, false);
+    }
+    const G1Affine r = g1_to_affine(acc);
+    if (i0 >= a.n) return;
+    uint32_t* q = a.dst + i0 * PT_WORDS;
+    st_fq(q, r.x);
+    st_fq(q + 12, r.y);
+}
+void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st) {
+    if (n == 0) return;
+    SrsContributeArgs a;
+    a.t = t;
+    a.n = n;
+    a.src = src;
+    a.dst = dst;
+    hipLaunchKernelGGL(srs_contribute_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
 }
 
 }  // namespace ty

@@ -255,7 +255,7 @@ class Srs {
     static Srs from_secret(const Context& ctx, const Fr& s, size_t gates) {
         Srs r(ctx);
         r.len_ = gates + 3;
-        check(typlonk_srs_generate(ctx.raw(), s.limbs(), 0, r.len_, &r.id_), ctx.raw());
+        typlonk::check(typlonk_srs_generate(ctx.raw(), s.limbs(), 0, r.len_, &r.id_), ctx.raw());
         // srs.rs:26-34: g2 = generator, g2s = [s] generator (host-side: the verifier's two G2 elements)
         r.g2_ = pairing::g2_generator();
         r.g2s_ = pairing::g2_mul(r.g2_, s.v);
@@ -270,8 +270,8 @@ class Srs {
         r.len_ = gates + 3;
         r.local_len_ = count;
         r.sharded_ = true;
-        check(typlonk_srs_generate(ctx.raw(), s.limbs(), first, count, &r.id_), ctx.raw());
-        check(typlonk_srs_set_shard(ctx.raw(), r.id_, first, r.len_), ctx.raw());
+        typlonk::check(typlonk_srs_generate(ctx.raw(), s.limbs(), first, count, &r.id_), ctx.raw());
+        typlonk::check(typlonk_srs_set_shard(ctx.raw(), r.id_, first, r.len_), ctx.raw());
         r.g2_ = pairing::g2_generator();
         r.g2s_ = pairing::g2_mul(r.g2_, s.v);
         r.has_g2_ = true;
@@ -301,7 +301,7 @@ class Srs {
             std::memcpy(&xy[i * 12], pts[i].xy, 96);
             inf[i] = pts[i].infinity;
         }
-        check(typlonk_srs_load(ctx.raw(), xy.data(), inf.data(), pts.size(), &r.id_), ctx.raw());
+        typlonk::check(typlonk_srs_load(ctx.raw(), xy.data(), inf.data(), pts.size(), &r.id_), ctx.raw());
         return r;
     }
     Srs(Srs&& o) noexcept
@@ -316,12 +316,39 @@ class Srs {
     size_t len() const { return len_; }   // of the whole SRS, also on a shard
     // optional, once per SRS: fixed-base tables in HBM (window chosen by the library from the length when 0); every later
     // commitment over this SRS is faster, results are unchanged -- nothing in the reference corresponds to it
-    void precompute(uint32_t window_bits = 0) const { check(typlonk_srs_precompute(ctx_->raw(), id_, window_bits), ctx_->raw()); }
+    void precompute(uint32_t window_bits = 0) const { typlonk::check(typlonk_srs_precompute(ctx_->raw(), id_, window_bits), ctx_->raw()); }
+    // typlonk_srs_check against this SRS's own g2s: is g1[i] = [s^i] G for the s of g2s()?  seed: 32 bytes that whoever
+    // produced the points cannot have known (typlonk.h).  An invalid SRS is the report's verdict, not an exception; nothing
+    // in the reference corresponds to it (Srs::from_secret trusts itself).  (The name hides the status check typlonk::check
+    // inside this class, which is why the calls here are qualified.)
+    typlonk_srs_report check(const uint8_t seed[32]) const {
+        uint64_t limbs[24];
+        g2s_limbs(limbs);
+        typlonk_srs_report rep;
+        typlonk::check(typlonk_srs_check(ctx_->raw(), id_, limbs, seed, &rep), ctx_->raw());
+        return rep;
+    }
+    // typlonk_srs_contribute: a new SRS [t^i] g1[i] with its own g2s = [t] g2s() (and the same g2): an SRS for s t
+    Srs contribute(const Fr& t) const {
+        uint64_t in[24], out[24];
+        g2s_limbs(in);
+        Srs r(*ctx_);
+        r.len_ = len_;
+        typlonk::check(typlonk_srs_contribute(ctx_->raw(), id_, t.limbs(), in, &r.id_, out), ctx_->raw());
+        pairing::G2Affine q;
+        std::memcpy(q.x.a.v, out, 48);
+        std::memcpy(q.x.b.v, out + 6, 48);
+        std::memcpy(q.y.a.v, out + 12, 48);
+        std::memcpy(q.y.b.v, out + 18, 48);
+        q.infinity = false;
+        r.set_g2(g2_, q);
+        return r;
+    }
     std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>); a shard: its slice
         const size_t cnt = sharded_ ? local_len_ : len_;
         std::vector<uint64_t> xy(cnt * 12);
         std::vector<uint8_t> inf(cnt);
-        check(typlonk_srs_download(ctx_->raw(), id_, 0, cnt, xy.data(), inf.data()), ctx_->raw());
+        typlonk::check(typlonk_srs_download(ctx_->raw(), id_, 0, cnt, xy.data(), inf.data()), ctx_->raw());
         std::vector<G1Point> out(cnt);
         for (size_t i = 0; i < cnt; ++i) {
             std::memcpy(out[i].xy, &xy[i * 12], 96);
@@ -332,7 +359,7 @@ class Srs {
     G1Point g1_generator() const {  // g1_ref()[0] without the other len - 1 points
         G1Point g;
         uint8_t inf = 0;
-        check(typlonk_srs_download(ctx_->raw(), id_, 0, 1, g.xy, &inf), ctx_->raw());
+        typlonk::check(typlonk_srs_download(ctx_->raw(), id_, 0, 1, g.xy, &inf), ctx_->raw());
         g.infinity = inf != 0;
         return g;
     }
@@ -341,6 +368,13 @@ class Srs {
 
    private:
     explicit Srs(const Context& c) : ctx_(&c) {}
+    void g2s_limbs(uint64_t out[24]) const {   // x.c0 x.c1 y.c0 y.c1 (throws without G2 elements)
+        const pairing::G2Affine& q = g2s();
+        std::memcpy(out, q.x.a.v, 48);
+        std::memcpy(out + 6, q.x.b.v, 48);
+        std::memcpy(out + 12, q.y.a.v, 48);
+        std::memcpy(out + 18, q.y.b.v, 48);
+    }
     const Context* ctx_;
     uint32_t id_ = 0;
     size_t len_ = 0, local_len_ = 0;
