@@ -667,15 +667,29 @@ def test_every_form_of_the_bucket_sort_gives_the_same_point(built, scatter, monk
 
 @pytest.mark.slow
 def test_more_than_2_23_terms_takes_the_counting_sort_fallback(ctx):
-    """The segmented sort indexes terms with 23 bits; a longer MSM falls back to the global counting sort (msm_host.hip
-    msm_enqueue -- the path has no switch of its own since round 4, so this is the test that reaches it): 2^23 + 5 terms
-    over [s^i]G against commit(p) == [p(s)]G (kzg/src/lib.rs:102-105), with the ragged lengths m - 1 and m - 3, and a
-    chunk-sized control below the limit through the ordinary path over the same SRS."""
+    """2^23 + 5 terms over the plain SRS [s^i]G, s = 2, against commit(p) == [p(s)]G (kzg/src/lib.rs:102-105).
+
+    Stand-alone (the four lengths this test has always had: m, the ragged m - 1 and m - 3, and 2^23 - 1): msm_chunks() cuts a
+    stand-alone MSM of this length into eight chunks of about 2^20 terms, every one with a segmented-sort shape, so these calls
+    do NOT reach the atomic counting sort (they did when the test was written, before stand-alone MSMs were chunked); the
+    stage names of the call say so: one exposed sort, seven overlapped ones, none of the atomic sort's stages.
+
+    Queued (typlonk_msm_g1_batch_devptr with two entries -- what every commitment of a proof is): one chunk per MSM.
+      [m, m - 1], m = 2^23 + 5: more than 2^23 terms have no segmented shape -- the atomic counting sort (msm_digits_kernel,
+        launch_scan, msm_scatter_kernel, order_hist_kernel, order_fused_kernel), on both MSMs of the batch;
+      [m, m - 1], m = 2^22 + 1: 16384 segments, more than the fused row-prefix form takes -- the three-launch scan over the
+        whole workgroup x segment matrix and the direct level-1 scatter; the second MSM, 2^22 terms, is the fused form beside it.
+    A batch records no stage events (its MSMs run with the per-call stage timers off), so the run cannot name its path; the
+    plan of exactly these calls is pinned on the host by tests/test_msm_sort_ref.py::test_what_only_the_long_msms_reach, and
+    both sorts are held to their full output at small sizes by tests/test_gpu_msm_sort.py.
+    Scalars: uniform, against the C oracle's Horner; all equal, and 0 / r - 1 alternating, whose commitments are geometric sums
+    in s: a (s^m - 1)/(s - 1) and -(s^(2 ceil(m/2)) - 1)/(s^2 - 1)."""
     import torch
     from conftest import need_resources
     from oracle import coracle as CO
 
-    need_resources(host_gib=3, hbm_gib=6)
+    # the SRS is 1 GiB; two queued MSMs of 2^23 + 5 terms keep two sets of keys and sorted, 4 x 512 MiB, and their buckets
+    need_resources(host_gib=3, hbm_gib=9)
     m = (1 << 23) + 5
     s_limbs = np.array(O.fr_to_mont_limbs(2), dtype=np.uint64)
     sid = ctx.srs_generate(s_limbs, m)
@@ -684,10 +698,59 @@ def test_more_than_2_23_terms_takes_the_counting_sort_fallback(ctx):
     sc[:, 3] &= np.uint64(0x3FFFFFFFFFFFFFFF)
     buf = ctx.alloc(m)
     buf.upload(sc)
-    for mm in (m, m - 1, m - 3, (1 << 23) - 1):
-        exp_xy, exp_inf = CO.g1_mul_generator(CO.poly_eval(sc[:mm], s_limbs))
-        got, ginf = ctx.msm_devptr(sid, buf.devptr, mm)
-        assert (got == exp_xy).all() and ginf == exp_inf, mm
+    atomic_stages = {"msm_digits", "msm_scan", "msm_scatter", "msm_order"}
+    exp = {}
+    ctx.set_profiling(1)
+    try:
+        for mm in (m, m - 1, m - 3, (1 << 23) - 1):
+            exp_xy, exp_inf = exp[mm] = CO.g1_mul_generator(CO.poly_eval(sc[:mm], s_limbs))
+            got, ginf = ctx.msm_devptr(sid, buf.devptr, mm)
+            assert (got == exp_xy).all() and ginf == exp_inf, mm
+            names = [name for name, _ in ctx.profile()]
+            assert names.count("msm_sort") == 1 and names.count("msm_sort_overlapped") == 7 and not atomic_stages & set(names), (mm, names)
+    finally:
+        ctx.set_profiling(0)
+
+    def queued(mq, want):
+        """[mq, mq - 1] terms of the scalars in buf, two MSMs in flight"""
+        outs = ctx.msm_batch_devptr(sid, [buf.devptr, buf.devptr], [mq, mq - 1])
+        for k, (xy, inf) in enumerate(outs):
+            assert (np.asarray(xy) == want[k][0]).all() and inf == want[k][1], (mq, k)
+
+    wide = (1 << 22) + 1
+    for mm in (wide, wide - 1):
+        exp[mm] = CO.g1_mul_generator(CO.poly_eval(sc[:mm], s_limbs))
+    queued(m, [exp[m], exp[m - 1]])               # the atomic counting sort
+    queued(wide, [exp[wide], exp[wide - 1]])      # the segmented sort, not fused
+    del sc
+
+    def point(value):
+        return CO.g1_mul_generator(np.array(O.fr_to_mont_limbs(value % O.R), dtype=np.uint64))
+
+    a = O.random_frs(823, 1)[0]
+    a_limbs, rm1_limbs = O.fr_to_mont_limbs(a), O.fr_to_mont_limbs(O.R - 1)
+
+    def equal(n):
+        return a * (pow(2, n, O.R) - 1)
+
+    def alternating(n):          # r - 1 = -1 at the even indices
+        return -(pow(4, (n + 1) // 2, O.R) - 1) * pow(3, -1, O.R)
+
+    def fill(v, closed):
+        if closed is equal:
+            v[:] = a_limbs
+        else:
+            v[0::2] = rm1_limbs
+        return v
+
+    for n in (1000, 1001):       # the closed forms themselves, against the oracle
+        for closed in (equal, alternating):
+            small = fill(np.zeros((n, 4), dtype=np.uint64), closed)
+            assert (CO.g1_mul_generator(CO.poly_eval(small, s_limbs))[0] == point(closed(n))[0]).all(), (closed.__name__, n)
+    for closed in (equal, alternating):
+        buf.upload(fill(np.zeros((m, 4), dtype=np.uint64), closed))
+        for mq in (m, wide):
+            queued(mq, [point(closed(mq)), point(closed(mq - 1))])
     buf.free()
     ctx.srs_free(sid)
     torch.cuda.empty_cache()

@@ -5,6 +5,7 @@
   tests/cpp/libff_host_shim.so    host shim over the shared arithmetic headers  -- g++
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
   tests/cpp/libdevice_reduce.so   device harness over msm_reduce.hip, the bucket reduction (tests/test_gpu_reduce.py) -- hipcc
+  tests/cpp/libdevice_sort.so     device harness over msm_sort.hip, the MSM's bucket sorts (tests/test_gpu_msm_sort.py) -- hipcc
   tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
@@ -173,6 +174,18 @@ def build_device_reduce(force: bool = False) -> str:
     src = os.path.join(CSRC, "harness", "device_reduce.hip")
     out = os.path.join(ROOT, "tests", "cpp", "libdevice_reduce.so")
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "msm_reduce.hip")]
+    if force or _stale(out, [src] + deps):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
+def build_device_sort(force: bool = False) -> str:
+    """tests/cpp/libdevice_sort.so: csrc/harness/device_sort.hip, msm_sort.hip compiled as a unit behind an entry point that plans an MSM
+    and runs one chunk's bucket sort -- segmented or atomic -- into guarded buffers of the plan's sizes (tests/test_gpu_msm_sort.py).
+    Test-only and not linked into the shipped library; the flags are build_hip()'s."""
+    src = os.path.join(CSRC, "harness", "device_sort.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_sort.so")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "msm_sort.hip")]
     if force or _stale(out, [src] + deps):
         _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
     return out
@@ -350,6 +363,7 @@ def build_all(force: bool = False) -> None:
     build_host_shim(force)
     build_device_arith(force)
     build_device_reduce(force)
+    build_device_sort(force)
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
     build_perm_pairs_host(force)
