@@ -6,6 +6,7 @@
   tests/cpp/libdevice_arith.so    device harness over the same headers (tests/test_gpu_arith.py) -- hipcc
   tests/cpp/libdevice_reduce.so   device harness over msm_reduce.hip, the bucket reduction (tests/test_gpu_reduce.py) -- hipcc
   tests/cpp/libdevice_sort.so     device harness over msm_sort.hip, the MSM's bucket sorts (tests/test_gpu_msm_sort.py) -- hipcc
+  tests/cpp/libdevice_accum.so    device harness over msm_accum.hip, the MSM's bucket accumulation (tests/test_gpu_accum.py) -- hipcc
   tests/cpp/libfq30_pair_host.so  host build of the paired Fq30 products (tests/test_fq30_pair.py) -- g++
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
@@ -191,6 +192,18 @@ def build_device_sort(force: bool = False) -> str:
     return out
 
 
+def build_device_accum(force: bool = False) -> str:
+    """tests/cpp/libdevice_accum.so: csrc/harness/device_accum.hip, msm_accum.hip compiled as a unit behind an entry point that runs the
+    accumulation and the heavy-bucket pass on caller-made sort outputs, points and stored buckets, after checking on the host that no index
+    leaves its array (tests/test_gpu_accum.py).  Test-only and not linked into the shipped library; the flags are build_hip()'s."""
+    src = os.path.join(CSRC, "harness", "device_accum.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_accum.so")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "msm_accum.hip")]
+    if force or _stale(out, [src] + deps):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
 def build_fq30_pair_host(force: bool = False) -> str:
     """tests/cpp/libfq30_pair_host.so: fq30_mul_pair / fq30_sqr_pair / fq30_mul2_add as the host compiles them"""
     src = os.path.join(ROOT, "tests", "cpp", "fq30_pair_host.cpp")
@@ -364,6 +377,7 @@ def build_all(force: bool = False) -> None:
     build_device_arith(force)
     build_device_reduce(force)
     build_device_sort(force)
+    build_device_accum(force)
     build_fq30_pair_host(force)
     build_sigma_cell_host(force)
     build_perm_pairs_host(force)

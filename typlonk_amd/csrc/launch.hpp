@@ -13,7 +13,7 @@ namespace ty {
 // accumulate kernel then touches exactly one 128-B line instead of 1.75 on average (PMC FETCH_SIZE
 // of msm_accum_kernel: 3.9 GB -> see profiles/).
 constexpr int PT_WORDS = 32;
-constexpr int MSM_HEAVY_GRID = 1024;   // workgroups of msm_heavy_kernel (four wavefronts each; grid-strided over the tasks)
+constexpr int MSM_HEAVY_GRID = 1024;   // workgroups of msm_heavy_kernel (two wavefronts each; grid-strided over the tasks)
 
 // arguments of the quotient pointwise kernel (quotient.hip): every array holds 4n coset evaluations
 struct QuotientArgs {
