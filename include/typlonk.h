@@ -911,6 +911,31 @@ int typlonk_srs_check_challenge(const uint8_t seed[32], uint64_t len, const uint
  * a ceremony -- whoever runs one publishes those beside the points. */
 int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4], const uint64_t g2s_in[24],
                            uint32_t* new_srs_id, uint64_t g2s_out[24]);
+/* The Lagrange form of an SRS and back: an NTT over the first n = 2^log_n points of the entry, taken in the group.
+ *   TYPLONK_SRS_TO_LAGRANGE    out[i] = [1/n] sum_{j<n} [w^(-i j)] g1[j]: for g1[j] = [s^j] G this is [L_i(s)] G, L_i the
+ *                              Lagrange basis of the domain {w^i}.  s stays unknown: only the points are needed.
+ *   TYPLONK_SRS_FROM_LAGRANGE  out[j] = sum_{i<n} [w^(i j)] g1[i], no scaling: the exact inverse of the above, for a caller
+ *                              who is handed only Lagrange points and wants the monomial prefix.
+ * w is the generator of the size-n domain that typlonk_ntt_fr* uses for the same log_n, and the index order is natural: out[i]
+ * goes with row i of an evaluation column, so a commitment to a column of EVALUATIONS (a wire column, selector evaluations)
+ * is one typlonk_msm_g1* over the Lagrange entry, with no inverse transform in front.  The new entry has exactly n points
+ * (canonical affine records, an identity the all-zero record with its flag; no tables, no shard) and is an SRS entry like
+ * any other: every MSM entry point, typlonk_srs_precompute, typlonk_srs_download[_compressed], typlonk_srs_len and
+ * typlonk_srs_free take it.  The old entry is untouched (it may hold tables; table 0 is read) and may hold more than n
+ * points -- a PLONK SRS holds n + 3 --: the rest is ignored.  The result is the stated sum by the group law for ANY curve
+ * points in the records: identities, points of small order, points that are no progression.  (Outside the group of order
+ * r an element of Fr is no scalar; there each butterfly applies its twiddle as the canonical integer, -1 as a negation, and
+ * the sum is the one the stages spell out -- no step fails on such a point, and the order-r part of every output is exact.)
+ * typlonk_srs_check tests the MONOMIAL form only: check first, then convert (or convert back, then check).  The provers
+ * keep taking the monomial entry: quotient and opening polynomials are not columns of evaluations.
+ * One launch per stage, one thread per butterfly (P, Q) -> (P + [w^k]Q, P - [w^k]Q): about (n/2)(log_n - 1) scalar
+ * multiplications of 255 doublings each, and n more for the 1/n of TO_LAGRANGE.  Setup-time.  Blocks.
+ * TYPLONK_ERR_INVALID_ARG: a null ctx or new_srs_id, an unknown id, an SRS shard (with or without a communicator), a
+ * direction other than the two, 2^log_n > the entry's length, log_n > 25 (the SRS length cap); then nothing is allocated
+ * and *new_srs_id is left as it was.  TYPLONK_ERR_OOM if the n x 128 bytes of the new entry are refused. */
+#define TYPLONK_SRS_TO_LAGRANGE 0
+#define TYPLONK_SRS_FROM_LAGRANGE 1
+int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t direction, uint32_t* new_srs_id);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -787,6 +787,16 @@ impl OwnedSrs {
     pub fn handle(&self) -> SrsHandle {
         self.handle
     }
+    /// `typlonk_srs_g1_ntt`, TO_LAGRANGE: the Lagrange form `[L_i(s)] G`, i < 2^log_n, of this monomial SRS as an SRS of its own
+    /// (no tables): the MSM of a column of evaluations over it is the commitment to the column's polynomial.  Check the
+    /// monomial SRS first (`Backend::check_srs` tests that form only).
+    pub fn lagrange(&self, log_n: u32) -> OwnedSrs {
+        let mut id = 0u32;
+        self.backend.check(unsafe {
+            ffi::typlonk_srs_g1_ntt(self.backend.ctx, self.handle.id, log_n, ffi::TYPLONK_SRS_TO_LAGRANGE as u32, &mut id)
+        });
+        OwnedSrs { backend: self.backend.clone(), handle: SrsHandle { id, len: 1usize << log_n } }
+    }
 }
 impl Drop for OwnedSrs {
     fn drop(&mut self) {

@@ -348,10 +348,11 @@ def build_host_tests(force: bool = False) -> list[str]:
     for name in ("test_poly_host", "test_kzg_host", "test_plonk_host", "test_pairing_host", "test_circuit_tables_host", "test_circuit_host",
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
                  "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
-                 "test_circuit_pairs_host", "test_witness_solve_host", "test_witness_hints_host", "test_srs_check_host"):
+                 "test_circuit_pairs_host", "test_witness_solve_host", "test_witness_hints_host", "test_srs_check_host",
+                 "test_srs_lagrange_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
-        if name in ("test_witness_hints_host", "test_srs_check_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
+        if name in ("test_witness_hints_host", "test_srs_check_host", "test_srs_lagrange_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
             continue
         if force or _stale(out, [src] + hdr):
             _run(["g++", "-O2", "-std=c++17", src, "-o", out, "-L", os.path.join(ROOT, "typlonk_amd"), "-ltyplonk_hip",

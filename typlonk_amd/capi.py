@@ -40,9 +40,10 @@ SYMBOLS = [
     "typlonk_circuit_compile", "typlonk_circuit_compile_host",
     "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
     "typlonk_witness_solve_plan", "typlonk_witness_solve", "typlonk_circuit_set_hints",
-    "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute",
+    "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute", "typlonk_srs_g1_ntt",
 ]
 VERIFY_PI_AS_PROVER = 1
+SRS_TO_LAGRANGE, SRS_FROM_LAGRANGE = 0, 1   # typlonk_srs_g1_ntt's direction
 # the wire format (include/typlonk.h): reject classes of a decoded field, the decode flag, the sizes
 POINT_ENCODING, POINT_X_RANGE, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP, SCALAR_RANGE = 1, 2, 3, 4, 5
 DECODE_SKIP_SUBGROUP = 1
@@ -398,6 +399,8 @@ def load_library() -> C.CDLL:
         lib.typlonk_srs_check.argtypes = [vp, C.c_uint32, u64p, u8p, C.POINTER(SrsReport)]
         lib.typlonk_srs_check_challenge.argtypes = [u8p, C.c_uint64, u64p, u64p]
         lib.typlonk_srs_contribute.argtypes = [vp, C.c_uint32, u64p, u64p, C.POINTER(C.c_uint32), u64p]
+    if hasattr(lib, "typlonk_srs_g1_ntt") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_srs_g1_ntt.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = lib
     return lib
 
@@ -733,6 +736,20 @@ class Context:
         out = np.zeros(24, dtype=np.uint64)
         self._chk(self.lib.typlonk_srs_contribute(self.h, sid, _u64p(t), _u64p(g), C.byref(new), _u64p(out)))
         return new.value, out
+
+    def srs_lagrange(self, sid: int, log_n: int) -> int:
+        """typlonk_srs_g1_ntt, TO_LAGRANGE: a new sid holding [L_i(s)] G, i < 2^log_n, for the monomial entry `sid`: the MSM of a
+        column of evaluations over it is the commitment to the column's polynomial"""
+        return self._srs_g1_ntt(sid, log_n, SRS_TO_LAGRANGE)
+
+    def srs_from_lagrange(self, sid: int, log_n: int) -> int:
+        """typlonk_srs_g1_ntt, FROM_LAGRANGE: a new sid holding the 2^log_n monomial points of the Lagrange entry `sid`"""
+        return self._srs_g1_ntt(sid, log_n, SRS_FROM_LAGRANGE)
+
+    def _srs_g1_ntt(self, sid: int, log_n: int, direction: int) -> int:
+        new = C.c_uint32()
+        self._chk(self.lib.typlonk_srs_g1_ntt(self.h, sid, log_n, direction, C.byref(new)))
+        return new.value
 
     def g1_decompress(self, data, skip_subgroup: bool = False):
         """g1_decompress on this context's device"""

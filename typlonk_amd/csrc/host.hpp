@@ -18,7 +18,8 @@
 //                 (solve_plan.hpp: every decision, no device needed); typlonk_circuit_set_hints: advice the solve computes
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
 //                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
-//   srs_check.hip typlonk_srs_check, typlonk_srs_contribute: a loaded SRS against [s]G2, and [t^i] g1[i] (kernels: srs_gen.hip)
+//   srs_check.hip typlonk_srs_check, typlonk_srs_contribute: a loaded SRS against [s]G2, and [t^i] g1[i]; typlonk_srs_g1_ntt:
+//                 the Lagrange form of an SRS and back (kernels: srs_gen.hip)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"

@@ -134,5 +134,11 @@ void launch_srs_membership(const uint32_t* pts, uint64_t n, unsigned long long* 
 void launch_fr_powers(const Fr& rho, uint64_t n, Fr* pw, Fr* pw_shift, hipStream_t st);
 // dst[i] = [t^i] src[i], canonical affine records; src and dst must not overlap
 void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st);
+// typlonk_srs_g1_ntt: stage 1 <= stage <= log_n of the transform of 2^log_n >= 2 points, root = the generator of the domain of
+// size 2^stage (forward) or its inverse.  Stage 1 reads src[0, 2^log_n) bit-reversed into dst; later stages work on dst in
+// place.  src and dst must not overlap.
+void launch_srs_g1_ntt_stage(const Fr& root, uint32_t log_n, uint32_t stage, const uint32_t* src, uint32_t* dst, hipStream_t st);
+// pts[i] <- [k] pts[i], canonical affine records, in place
+void launch_srs_g1_scale(const Fr& k, uint64_t n, uint32_t* pts, hipStream_t st);
 
 }  // namespace ty

@@ -1,6 +1,7 @@
 // libtyplonk_hip.so -- a powers-of-tau step (include/typlonk.h): typlonk_srs_check, typlonk_srs_check_challenge,
-// typlonk_srs_contribute.  Host side only; the three kernels (srs_membership_kernel, fr_powers_kernel,
-// srs_contribute_kernel) are in srs_gen.hip, beside the generator they share a ladder and the fixed base with.
+// typlonk_srs_contribute -- and typlonk_srs_g1_ntt, the Lagrange form of an SRS (at the end).  Host side only; the kernels
+// (srs_membership_kernel, fr_powers_kernel, srs_contribute_kernel, srs_g1_ntt_stage_kernel, srs_g1_scale_kernel) are in
+// srs_gen.hip, beside the generator they share a ladder and the fixed base with.
 //
 // The check: g1[i+1] = [s] g1[i] for every i is  e(g1[i], [s]G2) = e(g1[i+1], G2)  for every i; weighted with rho^i and
 // summed on the G1 side -- both pairings are linear there -- the len - 1 equations become ONE product
@@ -183,5 +184,44 @@ int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4
     memcpy(g2s_out + 6, q.x.b.v, 48);
     memcpy(g2s_out + 12, q.y.a.v, 48);
     memcpy(g2s_out + 18, q.y.b.v, 48);
+    return TYPLONK_OK;
+}
+
+// The Lagrange form of a monomial SRS and back: an NTT over the first 2^log_n points of the entry, in the group.  Stage by
+// stage on the new entry's own records (srs_g1_ntt_stage_kernel, srs_gen.hip); the inverse direction's 1/n is a pass of its
+// own behind the last stage (srs_g1_scale_kernel).
+int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t direction, uint32_t* new_srs_id) {
+    if (!ctx) return TYPLONK_ERR_INVALID_ARG;
+    if (!new_srs_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
+    const SrsEntry* src = nullptr;
+    int rc = whole_srs(ctx, srs_id, &src);
+    if (rc) return rc;
+    if (direction != TYPLONK_SRS_TO_LAGRANGE && direction != TYPLONK_SRS_FROM_LAGRANGE)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG, "direction is neither TYPLONK_SRS_TO_LAGRANGE nor TYPLONK_SRS_FROM_LAGRANGE");
+    if (log_n > 25) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "log_n > 25: an SRS holds at most 2^25 points");
+    const size_t n = (size_t)1 << log_n;
+    if (n > src->len) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "the entry holds fewer than 2^log_n points");
+    HIPCHK(hipSetDevice(ctx->device));
+    SrsEntry e;
+    e.len = n;
+    DevGuard guard;
+    HIPCHK(hipMalloc((void**)&e.d_points, n * PT_WORDS * 4));
+    guard.add(e.d_points);
+    const bool inverse = direction == TYPLONK_SRS_TO_LAGRANGE;
+    if (log_n == 0) HIPCHK(hipMemcpyAsync(e.d_points, src->d_points, PT_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint32_t stage = 1; stage <= log_n; ++stage) {
+        launch_srs_g1_ntt_stage(inverse ? fr_domain_root_inv(stage) : fr_domain_root(stage), log_n, stage, src->d_points, e.d_points,
+                                ctx->stream);
+        HIPCHK(hipGetLastError());
+    }
+    if (inverse && log_n) {
+        launch_srs_g1_scale(fr_inv_pow2(log_n), (uint64_t)n, e.d_points, ctx->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    guard.dismiss();
+    const uint32_t id = ctx->next_srs++;
+    ctx->srs[id] = e;
+    *new_srs_id = id;
     return TYPLONK_OK;
 }

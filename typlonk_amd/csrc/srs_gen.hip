@@ -296,11 +296,24 @@ void launch_fr_powers(const Fr& rho, uint64_t n, Fr* pw, Fr* pw_shift, hipStream
     hipLaunchKernelGGL(fr_powers_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rho, n, pw, pw_shift);
 }
 
-// dst[i] = [t^i] src[i], canonical affine, one thread per point: t^i by the ladder above, then 255 steps of doubling and
-// mixed addition, most significant bit first (r < 2^255).  The base is whatever the record holds: g1_madd_xy's equal and
-// opposite branches make the result [k]P by the group law for every curve point, those of small order included; an identity
-// stays one.  Spare lanes shadow the last point and skip only the store (srs_generate_kernel: the inversion's exit test is
-// wave-uniform).
+// [k] p for a canonical k < 2^255 and an affine p: 255 steps of doubling and mixed addition, most significant bit first
+__device__ __forceinline__ G1Xyzz g1_ladder(const Fr& k, const G1Affine& p) {
+    G1Xyzz acc = G1Xyzz::inf();
+#pragma unroll 1
+    for (int bit = 254; bit >= 0; --bit) {
+        acc = g1_dbl(acc);
+        uint32_t word = 0;   // (a select over the eight words: no indexed private array, no scratch)
+#pragma unroll
+        for (int w = 0; w < 8; ++w) word = (bit >> 5) == w ? k.v[w] : word;
+        if ((word >> (bit & 31)) & 1u) g1_madd(acc, p, false);
+    }
+    return acc;
+}
+
+// dst[i] = [t^i] src[i], canonical affine, one thread per point: t^i by fr_pow_u64, then g1_ladder (r < 2^255).  The base is
+// whatever the record holds: g1_madd_xy's equal and opposite branches make the result [k]P by the group law for every curve
+// point, those of small order included; an identity stays one.  Spare lanes shadow the last point and skip only the store
+// (srs_generate_kernel: the inversion's exit test is wave-uniform).
 struct SrsContributeArgs {
     Fr t;
     uint64_t n;
@@ -311,17 +324,7 @@ __global__ __launch_bounds__(64) void srs_contribute_kernel(SrsContributeArgs a)
     const uint64_t i0 = (uint64_t)blockIdx.x * 64 + threadIdx.x;
     const uint64_t i = i0 < a.n ? i0 : a.n - 1;
     const Fr k = fe_from_mont(fr_pow_u64(a.t, i));
-    const G1Affine p = ld_affine(a.src, i);
-    G1Xyzz acc = G1Xyzz::inf();
-#pragma unroll 1
-    for (int bit = 254; bit >= 0; --bit) {
-        acc = g1_dbl(acc);
-        uint32_t word = 0;   // (a select over the eight words: no indexed private array, no scratch)
-#pragma unroll
-        for (int w = 0; w < 8; ++w) word = (bit >> 5) == w ? k.v[w] : word;
-        if ((word >> (bit & 31)) & 1u) g1_madd(acc, p, false);
-    }
-    const G1Affine r = g1_to_affine(acc);
+    const G1Affine r = g1_to_affine(g1_ladder(k, ld_affine(a.src, i)));
     if (i0 >= a.n) return;
     uint32_t* q = a.dst + i0 * PT_WORDS;
     st_fq(q, r.x);
@@ -335,6 +338,96 @@ void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_
     a.src = src;
     a.dst = dst;
     hipLaunchKernelGGL(srs_contribute_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
+}
+
+// ---- typlonk_srs_g1_ntt (srs_check.hip): a radix-2 NTT whose elements are G1 points ----------------------------------------
+// Decimation in time over the bit-reversed first n = 2^log_n records, one launch per stage, one thread per butterfly, the
+// points canonical affine records between the stages.  Butterfly j of a block of 2^stage points:
+//     (P, Q) -> (P + [w]Q, P - [w]Q),   w = root^j,   root = the generator of the domain of size 2^stage (or its inverse).
+// [w]Q is g1_ladder; j = 0 (all of stage 1) skips it.  Both sums go through g1_madd, so P = +-[w]Q and an identity on either
+// side are g1_madd_xy's own branches; the two results share one inversion.  Stage 1 reads `src` -- the source entry --
+// through the bit reversal and every later stage works in place on `dst`: a butterfly reads and writes its own two records
+// only.  Spare lanes (n / 2 < 64) shadow the last butterfly of their own wavefront and skip only the stores.
+struct SrsNttStageArgs {
+    Fr root;
+    const uint32_t* src;
+    uint32_t* dst;
+    uint32_t log_n, stage;
+};
+// both of a butterfly's results as canonical affine records with ONE inversion, of ZZ ZZZ of the one times ZZ ZZZ of the
+// other (an identity contributes 1, so every lane inverts)
+__device__ __forceinline__ void g1_pair_to_affine(const G1Xyzz& a, const G1Xyzz& b, G1Affine& ra, G1Affine& rb) {
+    const bool ia = a.is_inf(), ib = b.is_inf();
+    const Fq30 ta = ia ? fq30_one() : fq30_mul(a.zz, a.zzz), tb = ib ? fq30_one() : fq30_mul(b.zz, b.zzz);   // < 1.01
+    const Fq30 inv = fq30_inv(fq30_mul(ta, tb));                       // < 1.01
+    const Fq30 va = fq30_mul(inv, tb), vb = fq30_mul(inv, ta);         // 1 / (ZZ ZZZ) of a, of b
+    ra.x = fq30_canon(fq30_mul(a.x, fq30_mul(va, a.zzz)));             // X / ZZ
+    ra.y = fq30_canon(fq30_mul(a.y, fq30_mul(va, a.zz)));              // Y / ZZZ
+    rb.x = fq30_canon(fq30_mul(b.x, fq30_mul(vb, b.zzz)));
+    rb.y = fq30_canon(fq30_mul(b.y, fq30_mul(vb, b.zz)));
+    if (ia) ra = G1Affine::inf();
+    if (ib) rb = G1Affine::inf();
+}
+__global__ __launch_bounds__(64) void srs_g1_ntt_stage_kernel(SrsNttStageArgs a) {
+    const uint32_t t0 = blockIdx.x * 64 + threadIdx.x, nb = 1u << (a.log_n - 1);
+    const uint32_t t = t0 < nb ? t0 : nb - 1;
+    const uint32_t half = 1u << (a.stage - 1), j = t & (half - 1);
+    const uint32_t ip = ((t - j) << 1) + j, iq = ip + half;            // < 2^log_n
+    // (P is loaded behind the ladder: across it the kernel holds what srs_contribute_kernel holds, and no more)
+    const uint32_t sh = 32 - a.log_n;                                  // stage 1: src through the bit reversal
+    const uint32_t* in = a.stage == 1 ? a.src : a.dst;
+    const G1Affine q = ld_affine(in, a.stage == 1 ? __brev(iq) >> sh : iq);
+    G1Xyzz wq = G1Xyzz::from_affine(q);
+    if (j != 0) wq = g1_ladder(fe_from_mont(fr_pow_u64(a.root, j)), q);
+    const G1Affine p = ld_affine(in, a.stage == 1 ? __brev(ip) >> sh : ip);
+    G1Xyzz sum = wq, dif = wq;
+    dif.y = fq30_neg_lazy<4>(wq.y);                                    // -[w]Q: 4p - Y <= 4p, the bound g1_madd_xy needs of Y1
+    g1_madd(sum, p, false);
+    g1_madd(dif, p, false);
+    G1Affine rs, rd;
+    g1_pair_to_affine(sum, dif, rs, rd);
+    if (t0 >= nb) return;
+    uint32_t* o = a.dst + (uint64_t)ip * PT_WORDS;
+    st_fq(o, rs.x);
+    st_fq(o + 12, rs.y);
+    o = a.dst + (uint64_t)iq * PT_WORDS;
+    st_fq(o, rd.x);
+    st_fq(o + 12, rd.y);
+}
+// stage 1 <= stage <= log_n of the transform of 2^log_n points, log_n >= 1; root: see above
+void launch_srs_g1_ntt_stage(const Fr& root, uint32_t log_n, uint32_t stage, const uint32_t* src, uint32_t* dst, hipStream_t st) {
+    SrsNttStageArgs a;
+    a.root = root;
+    a.src = src;
+    a.dst = dst;
+    a.log_n = log_n;
+    a.stage = stage;
+    const uint32_t nb = 1u << (log_n - 1);
+    hipLaunchKernelGGL(srs_g1_ntt_stage_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, a);
+}
+
+// pts[i] <- [k] pts[i], i < n, in place (the transform's 1/n): srs_contribute_kernel with one scalar for every point
+struct SrsScaleArgs {
+    Fr k;
+    uint64_t n;
+    uint32_t* pts;
+};
+__global__ __launch_bounds__(64) void srs_g1_scale_kernel(SrsScaleArgs a) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t i = i0 < a.n ? i0 : a.n - 1;
+    const G1Affine r = g1_to_affine(g1_ladder(fe_from_mont(a.k), ld_affine(a.pts, i)));
+    if (i0 >= a.n) return;
+    uint32_t* q = a.pts + i0 * PT_WORDS;
+    st_fq(q, r.x);
+    st_fq(q + 12, r.y);
+}
+void launch_srs_g1_scale(const Fr& k, uint64_t n, uint32_t* pts, hipStream_t st) {
+    if (n == 0) return;
+    SrsScaleArgs a;
+    a.k = k;
+    a.n = n;
+    a.pts = pts;
+    hipLaunchKernelGGL(srs_g1_scale_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
 }
 
 }  // namespace ty

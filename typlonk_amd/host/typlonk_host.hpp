@@ -344,6 +344,11 @@ class Srs {
         r.set_g2(g2_, q);
         return r;
     }
+    // typlonk_srs_g1_ntt: the Lagrange form [L_i(s)] G, i < 2^log_n, of this (monomial) SRS as an SRS of its own, with the same
+    // G2 elements, and the way back: the 2^log_n monomial points of a Lagrange SRS.  check() tests the monomial form only.
+    // KzgScheme::commit_evaluations commits over the Lagrange form; the provers keep taking the monomial one.
+    Srs lagrange(uint32_t log_n) const { return g1_ntt(log_n, TYPLONK_SRS_TO_LAGRANGE); }
+    Srs from_lagrange(uint32_t log_n) const { return g1_ntt(log_n, TYPLONK_SRS_FROM_LAGRANGE); }
     std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>); a shard: its slice
         const size_t cnt = sharded_ ? local_len_ : len_;
         std::vector<uint64_t> xy(cnt * 12);
@@ -368,6 +373,13 @@ class Srs {
 
    private:
     explicit Srs(const Context& c) : ctx_(&c) {}
+    Srs g1_ntt(uint32_t log_n, uint32_t direction) const {
+        Srs r(*ctx_);
+        typlonk::check(typlonk_srs_g1_ntt(ctx_->raw(), id_, log_n, direction, &r.id_), ctx_->raw());
+        r.len_ = (size_t)1 << log_n;
+        if (has_g2_) r.set_g2(g2_, g2s_);
+        return r;
+    }
     void g2s_limbs(uint64_t out[24]) const {   // x.c0 x.c1 y.c0 y.c1 (throws without G2 elements)
         const pairing::G2Affine& q = g2s();
         std::memcpy(out, q.x.a.v, 48);
@@ -406,6 +418,12 @@ class KzgScheme {
         return KzgOpening{evaluate_in_s(q), y};
     }
     KzgCommitment identity() const { return commit(Poly::from_coefficients_vec({Fr(1)})); }
+    // over a LAGRANGE Srs (Srs::lagrange): the commitment to the polynomial whose evaluations over the domain of srs.len()
+    // points these are -- commit(interpolate(evals)) over the monomial Srs -- as one MSM, with no transform
+    KzgCommitment commit_evaluations(const std::vector<Fr>& evals) const {
+        if (evals.size() > srs_.len()) throw std::runtime_error("more evaluations than Lagrange points");
+        return KzgCommitment{msm(evals)};
+    }
     // kzg/src/lib.rs:66-81: pairing(W, [s]G2 - z G2) == pairing(C - y G1, G2), as e(W, A) * e(-(C - y G1), G2) == 1
     bool verify(const KzgCommitment& commitment, const KzgOpening& opening, const Fr& z) const;
     const Srs& srs() const { return srs_; }
@@ -414,10 +432,13 @@ class KzgScheme {
     // kzg/src/lib.rs:41-54: assert!(srs.len() > degree) then sum coeff_i * srs_i -> the MSM
     G1Point evaluate_in_s(const Poly& polynomial) const {
         if (!(srs_.len() > polynomial.degree())) throw std::runtime_error("assertion failed: srs.len() > polynomial.degree()");
+        return msm(polynomial.coeffs);
+    }
+    G1Point msm(const std::vector<Fr>& scalars) const {   // sum scalars_i * srs_i
         G1Point out;
         uint8_t inf = 0;
-        const uint64_t* sc = polynomial.coeffs.empty() ? nullptr : polynomial.coeffs[0].limbs();
-        check(typlonk_msm_g1(srs_.ctx().raw(), srs_.id(), sc, polynomial.coeffs.size(), out.xy, &inf), srs_.ctx().raw());
+        const uint64_t* sc = scalars.empty() ? nullptr : scalars[0].limbs();
+        check(typlonk_msm_g1(srs_.ctx().raw(), srs_.id(), sc, scalars.size(), out.xy, &inf), srs_.ctx().raw());
         out.infinity = inf != 0;
         return out;
     }
