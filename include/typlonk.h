@@ -936,6 +936,47 @@ int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4
 #define TYPLONK_SRS_TO_LAGRANGE 0
 #define TYPLONK_SRS_FROM_LAGRANGE 1
 int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t direction, uint32_t* new_srs_id);
+/* ---- open() at EVERY point of the evaluation domain in one call (Feist-Khovratovich).  n = 2^log_n, w the generator of the
+ * size-n domain that typlonk_ntt_fr* uses, S_m = g1[m] the source entry's points ([s^m]G for a valid SRS), f_0 .. f_(n-1) the
+ * coefficients, zero above the m given.  The opening at w^k is pi_k = [q_k(s)]G, q_k = (f - f(w^k)) / (X - w^k); expanded,
+ *     h_i  = sum_{m=0}^{n-2-i} f_(m+i+1) S_m   (i = 0 .. n-2),   h_(n-1) = O
+ *     pi_k = sum_{i<n} [w^(i k)] h_i            (the direction of TYPLONK_SRS_FROM_LAGRANGE, no scaling)
+ * and h, a correlation, is taken as a circular product of size 2n: the TABLE is y = DFT_2n(S_(n-2), ..., S_0, O x (n+1)) in
+ * the group (root: the generator of the size-2n domain, no scaling), made once per (SRS, log_n); a call computes
+ * v = NTT_2n(f_(n-1), 0 x n, f_0, ..., f_(n-2)) / 2n over Fr, u_i = [v_i] y_i (one scalar multiplication per record),
+ * h^ = DFT_2n^-1(u) without scaling -- h_i = h^_i for i < n -- and pi = DFT_n(h).  About n log_n scalar
+ * multiplications for the table and n (1.5 log_n + 1.5) per polynomial, where n separate openings cost n MSMs of n terms.
+ * As for typlonk_srs_g1_ntt the sums hold by the group law for ANY curve points in the source's records; outside the
+ * group of order r a twiddle acts as its canonical integer.
+ *
+ * typlonk_srs_open_all_table: a new entry of the SRS list holding the 2n records of y (canonical affine; 2n x 128 bytes, and as
+ * much again while the call runs).  typlonk_srs_len reports 2n, typlonk_srs_free releases it, typlonk_srs_download reads it; it
+ * is no SRS to commit over.  The source entry is untouched (it may hold tables; table 0 is read), may hold more than the
+ * n - 1 points the table reads, and may be freed afterwards.  Blocks.
+ *   TYPLONK_ERR_DOMAIN       log_n outside 1..24 (2n <= 2^25, the SRS length cap)
+ *   TYPLONK_ERR_INVALID_ARG  a null ctx or table_id, an unknown id, an SRS shard (with or without a communicator), a source that
+ *                            is itself such a table, a source of fewer than n - 1 points
+ *   TYPLONK_ERR_OOM          an allocation is refused
+ * A refused call leaves *table_id as it was. */
+int typlonk_srs_open_all_table(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t* table_id);
+/* Opening k and evaluation k of the m coefficients from `offset` of poly, 1 <= m <= n, in natural order, k < n:
+ *   proofs_xy / proofs_inf  n records of 12 limbs and n flags: canonical affine Montgomery coordinates, an identity flagged
+ *                           -- exactly what typlonk_srs_download writes for the same points
+ *   evals                   n x 4 limbs, f(w^k) as canonical Montgomery Fr -- what typlonk_ntt_fr gives for the padded
+ *                           coefficients; may be NULL
+ * (pi_k, evals[k]) is what typlonk_open_dev at z = w^k followed by typlonk_msm_g1_dev over the source entry gives.  A
+ * constant polynomial opens to identities.  Blocks.  Temporaries, freed on return: two buffers of 2n records (2n x 128 bytes
+ * each) and one of 2n Fr (2n x 32 bytes) -- 576 n bytes, 576 MiB at n = 2^20 -- beside the transforms' own workspace.
+ *   TYPLONK_ERR_INVALID_ARG  a null pointer other than evals, an unknown id, an id that is not such a table
+ *   TYPLONK_ERR_LENGTH       m = 0 or m > n
+ *   TYPLONK_ERR_RANGE        offset / m outside poly
+ *   TYPLONK_ERR_OOM          an allocation is refused
+ * A refused call leaves the outputs as they were. */
+int typlonk_open_all_dev(typlonk_ctx* ctx, uint32_t table_id, const typlonk_buf* poly, size_t offset, size_t m,
+                         uint64_t* proofs_xy /* n*12 */, uint8_t* proofs_inf /* n */, uint64_t* evals /* n*4 or NULL */);
+/* The same for m coefficients in HOST memory (4 Montgomery limbs each): they are uploaded into one of the temporaries. */
+int typlonk_open_all_host(typlonk_ctx* ctx, uint32_t table_id, const uint64_t* coeffs, size_t m,
+                          uint64_t* proofs_xy, uint8_t* proofs_inf, uint64_t* evals);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -797,6 +797,27 @@ impl OwnedSrs {
         });
         OwnedSrs { backend: self.backend.clone(), handle: SrsHandle { id, len: 1usize << log_n } }
     }
+    /// `typlonk_srs_open_all_table`: the table `open_all` needs for the domain of 2^log_n points over this monomial SRS -- 2^(log_n + 1)
+    /// records held like an SRS (freed when dropped) that are no SRS to commit over.
+    pub fn open_all_table(&self, log_n: u32) -> OwnedSrs {
+        let mut id = 0u32;
+        self.backend.check(unsafe { ffi::typlonk_srs_open_all_table(self.backend.ctx, self.handle.id, log_n, &mut id) });
+        OwnedSrs { backend: self.backend.clone(), handle: SrsHandle { id, len: 2usize << log_n } }
+    }
+    /// `typlonk_open_all_host` over `self`, a table made by `open_all_table`: the openings of `coeffs` (1..=n coefficients, 4
+    /// Montgomery limbs each) at every point w^k of the table's domain, k < n = len / 2, in natural order -- (12 limbs x || y,
+    /// identity flag) per proof and the 4 limbs of f(w^k).  What `KzgScheme::open` gives at each w^k, in one call.
+    pub fn open_all(&self, coeffs: &[[u64; 4]]) -> (Vec<[u64; 12]>, Vec<u8>, Vec<[u64; 4]>) {
+        let n = self.handle.len / 2;
+        let mut xy = vec![[0u64; 12]; n];
+        let mut inf = vec![0u8; n];
+        let mut evals = vec![[0u64; 4]; n];
+        self.backend.check(unsafe {
+            ffi::typlonk_open_all_host(self.backend.ctx, self.handle.id, coeffs.as_ptr() as *const u64, coeffs.len(),
+                                       xy.as_mut_ptr() as *mut u64, inf.as_mut_ptr(), evals.as_mut_ptr() as *mut u64)
+        });
+        (xy, inf, evals)
+    }
 }
 impl Drop for OwnedSrs {
     fn drop(&mut self) {

@@ -58,7 +58,7 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip", "open_all.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -349,10 +349,10 @@ def build_host_tests(force: bool = False) -> list[str]:
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
                  "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
                  "test_circuit_pairs_host", "test_witness_solve_host", "test_witness_hints_host", "test_srs_check_host",
-                 "test_srs_lagrange_host"):
+                 "test_srs_lagrange_host", "test_open_all_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
-        if name in ("test_witness_hints_host", "test_srs_check_host", "test_srs_lagrange_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
+        if name in ("test_witness_hints_host", "test_srs_check_host", "test_srs_lagrange_host", "test_open_all_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
             continue
         if force or _stale(out, [src] + hdr):
             _run(["g++", "-O2", "-std=c++17", src, "-o", out, "-L", os.path.join(ROOT, "typlonk_amd"), "-ltyplonk_hip",

@@ -41,6 +41,7 @@ SYMBOLS = [
     "typlonk_permutation_from_pairs", "typlonk_circuit_compile_pairs", "typlonk_circuit_compile_pairs_host",
     "typlonk_witness_solve_plan", "typlonk_witness_solve", "typlonk_circuit_set_hints",
     "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute", "typlonk_srs_g1_ntt",
+    "typlonk_srs_open_all_table", "typlonk_open_all_dev", "typlonk_open_all_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 SRS_TO_LAGRANGE, SRS_FROM_LAGRANGE = 0, 1   # typlonk_srs_g1_ntt's direction
@@ -401,6 +402,10 @@ def load_library() -> C.CDLL:
         lib.typlonk_srs_contribute.argtypes = [vp, C.c_uint32, u64p, u64p, C.POINTER(C.c_uint32), u64p]
     if hasattr(lib, "typlonk_srs_g1_ntt") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
         lib.typlonk_srs_g1_ntt.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "typlonk_open_all_dev") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_srs_open_all_table.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.typlonk_open_all_dev.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.c_size_t, u64p, u8p, u64p]
+        lib.typlonk_open_all_host.argtypes = [vp, C.c_uint32, u64p, C.c_size_t, u64p, u8p, u64p]
     _lib = lib
     return lib
 
@@ -750,6 +755,31 @@ class Context:
         new = C.c_uint32()
         self._chk(self.lib.typlonk_srs_g1_ntt(self.h, sid, log_n, direction, C.byref(new)))
         return new.value
+
+    def srs_open_all_table(self, sid: int, log_n: int) -> int:
+        """typlonk_srs_open_all_table: the id of the table `open_all` needs for the domain of 2^log_n points over the entry
+        `sid` (2^(log_n + 1) records; released by srs_free)"""
+        new = C.c_uint32()
+        self._chk(self.lib.typlonk_srs_open_all_table(self.h, sid, log_n, C.byref(new)))
+        return new.value
+
+    def open_all(self, table: int, coeffs_or_buf, m: int | None = None, evals: bool = True, offset: int = 0):
+        """typlonk_open_all_dev / _host: the openings of a polynomial at every point w^k of the table's domain, k < n.
+        coeffs_or_buf: a DeviceBuffer (m coefficients from `offset`; m = None: all behind it) or host coefficients (k, 4) u64
+        Montgomery.  Returns (xy (n, 12), inf (n,)[, evals (n, 4)])."""
+        n = self.srs_len(table) // 2
+        xy = np.zeros((n, 12), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        ev = np.zeros((n, 4), dtype=np.uint64) if evals else None
+        evp = _u64p(ev) if evals else None
+        if isinstance(coeffs_or_buf, DeviceBuffer):
+            m = coeffs_or_buf.n - offset if m is None else m
+            self._chk(self.lib.typlonk_open_all_dev(self.h, table, coeffs_or_buf.handle, offset, m, _u64p(xy), _u8p(inf), evp))
+        else:
+            co = _as_u64(coeffs_or_buf, 4)
+            m = co.shape[0] if m is None else m
+            self._chk(self.lib.typlonk_open_all_host(self.h, table, _u64p(co), m, _u64p(xy), _u8p(inf), evp))
+        return (xy, inf, ev) if evals else (xy, inf)
 
     def g1_decompress(self, data, skip_subgroup: bool = False):
         """g1_decompress on this context's device"""

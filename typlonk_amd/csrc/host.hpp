@@ -20,6 +20,8 @@
 //                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
 //   srs_check.hip typlonk_srs_check, typlonk_srs_contribute: a loaded SRS against [s]G2, and [t^i] g1[i]; typlonk_srs_g1_ntt:
 //                 the Lagrange form of an SRS and back (kernels: srs_gen.hip)
+//   open_all.hip  typlonk_srs_open_all_table, typlonk_open_all_*: a polynomial's openings at every point of its domain
+//                 (kernels: srs_gen.hip)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -60,6 +62,9 @@ struct SrsEntry {
     bool table_centred = false;         // table_T counts the windows of CENTRED scalars (launch.hpp, msm_windows)
     // typlonk_srs_set_shard: this entry holds bases [shard_first, shard_first + len) of a total_len-point SRS
     size_t shard_first = 0, total_len = 0;
+    // typlonk_srs_open_all_table: this entry is the table of the domain of 2^open_all_log_n points (len = twice that many
+    // records); 0: not a table
+    uint32_t open_all_log_n = 0;
     size_t total() const { return total_len ? total_len : len; }
     // part [off, off + ml) of an m-term MSM that falls into this entry
     void local_range(size_t m, size_t* off, size_t* ml) const {
@@ -361,6 +366,13 @@ int msm_run(typlonk_ctx* ctx, uint32_t srs_id, const Fr* d_scalars, size_t m, ui
 int msm_batch(typlonk_ctx* ctx, uint32_t srs_id, const void* const* d_scalars, const size_t* m, size_t count, uint64_t* out_xy,
               uint8_t* out_inf);
 int msm_finish(typlonk_ctx* ctx, MsmWs& ws);
+// `count` resident records from d_points -> the C-ABI's arkworks form (typlonk_srs_download's output); blocks
+int points_to_host(typlonk_ctx* ctx, const uint32_t* d_points, size_t count, uint64_t* xy, uint8_t* inf);
+
+// ---- srs_check.hip --------------------------------------------------------------------------------------------------
+// the log_n >= 1 stages of the transform of 2^log_n records in the group, queued on the context's stream: stage 1 reads src
+// through the bit reversal into dst, the later ones work on dst in place (src and dst must not overlap).  No scaling.
+int g1_ntt_stages(typlonk_ctx* ctx, const uint32_t* src, uint32_t* dst, uint32_t log_n, bool inverse);
 
 // Asynchronous MSM submissions over one SRS (a prover round, or typlonk_msm_g1_batch_devptr).
 //   submit()    puts an MSM on the next lane of [lane_lo, lanes): the lane first waits for everything queued on the

@@ -140,5 +140,12 @@ void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_
 void launch_srs_g1_ntt_stage(const Fr& root, uint32_t log_n, uint32_t stage, const uint32_t* src, uint32_t* dst, hipStream_t st);
 // pts[i] <- [k] pts[i], canonical affine records, in place
 void launch_srs_g1_scale(const Fr& k, uint64_t n, uint32_t* pts, hipStream_t st);
+// typlonk_open_all_* (kernels: srs_gen.hip; host: open_all.hip)
+// dst[i] = [k[i]] src[i], i < n: k Montgomery residues on the device, canonical affine records; dst may be src
+void launch_g1_pointwise_mul(const Fr* k, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st);
+// dst[0, 2n) = (src[n-2], ..., src[0], identity x (n + 1)); n >= 2; src and dst must not overlap
+void launch_open_all_gather(const uint32_t* src, uint32_t* dst, uint64_t n, hipStream_t st);
+// c[0, 2n) = k * (f[n-1], 0 x n, f[0], ..., f[n-2]) for the m <= n coefficients of f (zero above); f and c must not overlap
+void launch_open_all_coeffs(const Fr* f, uint64_t m, uint64_t n, const Fr& k, Fr* c, hipStream_t st);
 
 }  // namespace ty

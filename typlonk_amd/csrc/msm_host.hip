@@ -516,8 +516,11 @@ int typlonk_srs_download(typlonk_ctx* ctx, uint32_t srs_id, size_t offset, size_
     if (!e) return TYPLONK_ERR_INVALID_ARG;
     if (offset > e->len || count > e->len - offset) return fail(ctx, TYPLONK_ERR_RANGE, "range outside SRS");
     if (!count) return TYPLONK_OK;
-    HIPCHK(hipMemcpy2DAsync(xy, 96, e->d_points + offset * PT_WORDS, PT_WORDS * 4, 96, count, hipMemcpyDeviceToHost,
-                            ctx->stream));
+    return points_to_host(ctx, e->d_points + offset * PT_WORDS, count, xy, inf);
+}
+
+int tyh::points_to_host(typlonk_ctx* ctx, const uint32_t* d_points, size_t count, uint64_t* xy, uint8_t* inf) {
+    HIPCHK(hipMemcpy2DAsync(xy, 96, d_points, PT_WORDS * 4, 96, count, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < count; ++i) {  // internal packed form -> arkworks; (0,0) -> ark-ec (0, 1, inf)
         G1Affine a;

@@ -187,6 +187,16 @@ int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4
     return TYPLONK_OK;
 }
 
+// One launch per stage (srs_g1_ntt_stage_kernel, srs_gen.hip); typlonk_srs_g1_ntt below and the three transforms of
+// typlonk_open_all_* (open_all.hip)
+int tyh::g1_ntt_stages(typlonk_ctx* ctx, const uint32_t* src, uint32_t* dst, uint32_t log_n, bool inverse) {
+    for (uint32_t stage = 1; stage <= log_n; ++stage) {
+        launch_srs_g1_ntt_stage(inverse ? fr_domain_root_inv(stage) : fr_domain_root(stage), log_n, stage, src, dst, ctx->stream);
+        HIPCHK(hipGetLastError());
+    }
+    return TYPLONK_OK;
+}
+
 // The Lagrange form of a monomial SRS and back: an NTT over the first 2^log_n points of the entry, in the group.  Stage by
 // stage on the new entry's own records (srs_g1_ntt_stage_kernel, srs_gen.hip); the inverse direction's 1/n is a pass of its
 // own behind the last stage (srs_g1_scale_kernel).
@@ -209,11 +219,7 @@ int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32
     guard.add(e.d_points);
     const bool inverse = direction == TYPLONK_SRS_TO_LAGRANGE;
     if (log_n == 0) HIPCHK(hipMemcpyAsync(e.d_points, src->d_points, PT_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    for (uint32_t stage = 1; stage <= log_n; ++stage) {
-        launch_srs_g1_ntt_stage(inverse ? fr_domain_root_inv(stage) : fr_domain_root(stage), log_n, stage, src->d_points, e.d_points,
-                                ctx->stream);
-        HIPCHK(hipGetLastError());
-    }
+    if (log_n && (rc = g1_ntt_stages(ctx, src->d_points, e.d_points, log_n, inverse))) return rc;
     if (inverse && log_n) {
         launch_srs_g1_scale(fr_inv_pow2(log_n), (uint64_t)n, e.d_points, ctx->stream);
         HIPCHK(hipGetLastError());

@@ -430,4 +430,60 @@ void launch_srs_g1_scale(const Fr& k, uint64_t n, uint32_t* pts, hipStream_t st)
     hipLaunchKernelGGL(srs_g1_scale_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
 }
 
+// ---- typlonk_open_all_* (open_all.hip): every opening of a polynomial over its domain ---------------------------------------
+// dst[i] = [k_i] src[i], canonical affine, one thread per record: srs_contribute_kernel with the scalar read from a device
+// vector of Montgomery residues instead of computed.  k_i = 0 and an identity record both give the all-zero record (the
+// ladder never leaves the identity).  Spare lanes shadow the last point and skip only the store.
+struct G1PointwiseArgs {
+    const Fr* k;
+    uint64_t n;
+    const uint32_t* src;
+    uint32_t* dst;
+};
+__global__ __launch_bounds__(64) void g1_pointwise_mul_kernel(G1PointwiseArgs a) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t i = i0 < a.n ? i0 : a.n - 1;
+    const Fr k = fe_from_mont(a.k[i]);
+    const G1Affine r = g1_to_affine(g1_ladder(k, ld_affine(a.src, i)));
+    if (i0 >= a.n) return;
+    uint32_t* q = a.dst + i0 * PT_WORDS;
+    st_fq(q, r.x);
+    st_fq(q + 12, r.y);
+}
+void launch_g1_pointwise_mul(const Fr* k, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st) {
+    if (n == 0) return;
+    G1PointwiseArgs a;
+    a.k = k;
+    a.n = n;
+    a.src = src;
+    a.dst = dst;
+    hipLaunchKernelGGL(g1_pointwise_mul_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
+}
+
+// The first operand of the circular product, 2n records: dst = (src[n-2], src[n-3], ..., src[0], identity x (n + 1)).  One
+// thread per 16 bytes of a record's 128 (the stride's padding is copied along: it is never read).
+__global__ __launch_bounds__(256) void open_all_gather_kernel(const uint4* src, uint4* dst, uint64_t n) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    constexpr uint64_t Q = PT_WORDS / 4;
+    const uint64_t i = t / Q, q = t % Q;
+    if (i >= 2 * n) return;
+    dst[t] = i + 1 < n ? src[(n - 2 - i) * Q + q] : make_uint4(0, 0, 0, 0);
+}
+void launch_open_all_gather(const uint32_t* src, uint32_t* dst, uint64_t n, hipStream_t st) {
+    const uint64_t threads = 2 * n * (PT_WORDS / 4);
+    hipLaunchKernelGGL(open_all_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const uint4*)src, (uint4*)dst, n);
+}
+
+// The second operand, 2n elements, with the 1/(2n) of the inverse group transform folded in (the Fr transform is linear):
+// c[0] = k f[n-1], c[1 .. n] = 0, c[n+1+j] = k f[j] for j < n - 1; f holds m <= n coefficients, zero above.
+__global__ __launch_bounds__(256) void open_all_coeffs_kernel(const Fr* f, uint64_t m, uint64_t n, Fr k, Fr* c) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * n) return;
+    const uint64_t j = i == 0 ? n - 1 : i - n - 1;      // (1 <= i <= n wraps around: >= m, zero)
+    c[i] = (i == 0 || i > n) && j < m ? fe_mul(f[j], k) : Fr::zero();
+}
+void launch_open_all_coeffs(const Fr* f, uint64_t m, uint64_t n, const Fr& k, Fr* c, hipStream_t st) {
+    hipLaunchKernelGGL(open_all_coeffs_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, f, m, n, k, c);
+}
+
 }  // namespace ty

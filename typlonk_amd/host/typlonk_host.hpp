@@ -349,6 +349,16 @@ class Srs {
     // KzgScheme::commit_evaluations commits over the Lagrange form; the provers keep taking the monomial one.
     Srs lagrange(uint32_t log_n) const { return g1_ntt(log_n, TYPLONK_SRS_TO_LAGRANGE); }
     Srs from_lagrange(uint32_t log_n) const { return g1_ntt(log_n, TYPLONK_SRS_FROM_LAGRANGE); }
+    // typlonk_srs_open_all_table: the table KzgScheme::open_all needs for the domain of 2^log_n points over this (monomial) SRS:
+    // 2^(log_n + 1) records held like an SRS (len() reports them, the destructor frees them) that are no SRS to commit over.
+    // Nothing in the reference corresponds to it (it opens point by point).
+    Srs open_all_table(uint32_t log_n) const {
+        Srs r(*ctx_);
+        typlonk::check(typlonk_srs_open_all_table(ctx_->raw(), id_, log_n, &r.id_), ctx_->raw());
+        r.len_ = (size_t)2 << log_n;
+        if (has_g2_) r.set_g2(g2_, g2s_);
+        return r;
+    }
     std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>); a shard: its slice
         const size_t cnt = sharded_ ? local_len_ : len_;
         std::vector<uint64_t> xy(cnt * 12);
@@ -416,6 +426,26 @@ class KzgScheme {
         Fr y;
         const Poly q = polynomial.divide_by_linear(z, &y);
         return KzgOpening{evaluate_in_s(q), y};
+    }
+    // open(polynomial, w^k) for every k < n in one call (typlonk_open_all_host), n = table.len() / 2 the domain of `table`
+    // (Srs::open_all_table of this scheme's SRS) and w its generator: result[k] is what open() gives at Radix2EvaluationDomain
+    // (n).element(k).  1 <= coefficients <= n.
+    std::vector<KzgOpening> open_all(const Srs& table, const Poly& polynomial) const {
+        if (polynomial.coeffs.empty()) throw std::runtime_error("at least 1");
+        const size_t n = table.len() / 2;
+        std::vector<uint64_t> xy(n * 12);
+        std::vector<uint8_t> inf(n);
+        std::vector<Fr> ys(n);
+        check(typlonk_open_all_host(srs_.ctx().raw(), table.id(), polynomial.coeffs[0].limbs(), polynomial.coeffs.size(), xy.data(),
+                                    inf.data(), ys[0].limbs()),
+              srs_.ctx().raw());
+        std::vector<KzgOpening> out(n);
+        for (size_t k = 0; k < n; ++k) {
+            std::memcpy(out[k].p.xy, &xy[k * 12], 96);
+            out[k].p.infinity = inf[k] != 0;
+            out[k].y = ys[k];
+        }
+        return out;
     }
     KzgCommitment identity() const { return commit(Poly::from_coefficients_vec({Fr(1)})); }
     // over a LAGRANGE Srs (Srs::lagrange): the commitment to the polynomial whose evaluations over the domain of srs.len()
