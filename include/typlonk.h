@@ -977,6 +977,55 @@ int typlonk_open_all_dev(typlonk_ctx* ctx, uint32_t table_id, const typlonk_buf*
 /* The same for m coefficients in HOST memory (4 Montgomery limbs each): they are uploaded into one of the temporaries. */
 int typlonk_open_all_host(typlonk_ctx* ctx, uint32_t table_id, const uint64_t* coeffs, size_t m,
                           uint64_t* proofs_xy, uint8_t* proofs_inf, uint64_t* evals);
+/* ---- open() on every COSET of the evaluation domain in one call: multi-proofs (Feist-Khovratovich, chunked).  n = 2^log_n,
+ * l = 2^log_l, r = n / l >= 2; w, S_m, f as above, and w^l the generator of the size-r domain.  Coset k < r is
+ * {w^(k + r t) : t < l}, the roots of X^l - a_k with a_k = w^(k l).  One proof opens f at all l points of a coset:
+ *     f    = q_k (X^l - a_k) + I_k,   deg I_k < l,   I_k = f on coset k
+ *     pi_k = [q_k(s)] G = sum_{i<r} [w^(l i k)] h_i
+ *     h_i  = sum_{m=0}^{n-1-(i+1)l} f_(m+(i+1)l) S_m   (i <= r - 2),   h_(r-1) = O
+ * and a verifier that holds [s^l]G2 checks e(C - [I_k(s)]G + [a_k] pi_k, G2) = e(pi_k, [s^l]G2).  With f^(j)_a = f_(a l + j)
+ * and S^(j)_a = S_(a l + j) (j < l, a < r), h is the sum over j of the correlations above at size r, and the l of them are
+ * summed in the Fourier domain: the TABLE is, for each j, y^(j) = DFT_2r(S^(j)_(r-2), ..., S^(j)_0, O x (r+1)) in the group
+ * (root: the generator of the size-2r domain, no scaling), y^(j)_i at record j 2r + i; a call computes
+ * v^(j) = NTT_2r(f^(j)_(r-1), 0 x r, f^(j)_0, ..., f^(j)_(r-2)) / 2r over Fr, u_i = sum_{j<l} [v^(j)_i] y^(j)_i for i < 2r
+ * (2n scalar multiplications whose doublings are shared among the terms of a sum), h^ = DFT_2r^-1(u) without scaling --
+ * h_i = h^_i for i < r -- and pi = DFT_r(h) with root w^l.  The group transforms are of 2r and r records, not 2n and n.
+ * With log_l = 0 everything is the section above, record for record.
+ *
+ * typlonk_srs_open_chunks_table: a new entry of the SRS list holding the 2n records of the l blocks (canonical affine; 2n x 128
+ * bytes, and as much again while the call runs); typlonk_srs_len reports 2n, typlonk_srs_free releases it.  With log_l = 0 it
+ * holds, word for word, what typlonk_srs_open_all_table makes, and typlonk_open_all_* takes exactly the tables of log_l = 0,
+ * of either constructor (others: TYPLONK_ERR_INVALID_ARG).  The source entry is untouched, may hold more than the n - l
+ * points the table reads, and may be freed afterwards.  Blocks.
+ *   TYPLONK_ERR_DOMAIN       log_n outside 1..24, or log_l >= log_n
+ *   TYPLONK_ERR_INVALID_ARG  a null ctx or table_id, an unknown id, an SRS shard (with or without a communicator), a source that
+ *                            is itself a table of either constructor, a source of fewer than n - l points
+ *   TYPLONK_ERR_OOM          an allocation is refused
+ * A refused call leaves *table_id as it was. */
+int typlonk_srs_open_chunks_table(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t log_l, uint32_t* table_id);
+/* The r proofs and n evaluations of each of `count` polynomials over one table (of either constructor): polynomial p is the m
+ * coefficients from offsets[p] (offsets = NULL: from 0) of polys[p], 1 <= m <= n, the same m for all.  The same buffer may
+ * appear more than once.
+ *   proofs_xy / proofs_inf  count x r records of 12 limbs and count x r flags, proof k of polynomial p at p r + k, as
+ *                           typlonk_srs_download writes points
+ *   evals                   count x n x 4 limbs, CHUNK-MAJOR: evals[(p n + k l + t) 4 ..] = f_p(w^(k + r t)), the l values
+ *                           that go with proof k contiguous; canonical Montgomery Fr; may be NULL
+ * A polynomial of degree < l opens to identities.  Blocks.  Temporaries, freed on return: two buffers of count x 2r records
+ * (128 bytes each), one of count x 2n Fr (32 bytes each) and `count` pointers -- count x (512 r + 64 n + 8) bytes, 72 MiB for
+ * one polynomial at n = 2^20, l = 64 -- beside the transforms' own workspace.
+ *   TYPLONK_ERR_INVALID_ARG  a null pointer other than offsets / evals, a null entry of polys, an unknown id, an id that is
+ *                            no table
+ *   TYPLONK_ERR_LENGTH       m = 0 or m > n, count = 0, count x 2r > 2^25 records
+ *   TYPLONK_ERR_RANGE        offsets[p] / m outside polys[p]
+ *   TYPLONK_ERR_OOM          an allocation is refused
+ * A refused call leaves the outputs as they were. */
+int typlonk_open_chunks_dev(typlonk_ctx* ctx, uint32_t table_id, const typlonk_buf* const* polys, const size_t* offsets, size_t m,
+                            size_t count, uint64_t* proofs_xy /* count*r*12 */, uint8_t* proofs_inf /* count*r */,
+                            uint64_t* evals /* count*n*4, chunk-major, or NULL */);
+/* The same for coefficients in HOST memory, coeffs[p]: m x 4 Montgomery limbs; they are uploaded into one more temporary of
+ * count x m Fr. */
+int typlonk_open_chunks_host(typlonk_ctx* ctx, uint32_t table_id, const uint64_t* const* coeffs, size_t m, size_t count,
+                             uint64_t* proofs_xy, uint8_t* proofs_inf, uint64_t* evals);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -818,6 +818,34 @@ impl OwnedSrs {
         });
         (xy, inf, evals)
     }
+    /// `typlonk_srs_open_chunks_table`: the table `open_chunks` needs for the domain of 2^log_n points cut into cosets of 2^log_l
+    /// over this monomial SRS -- 2^(log_n + 1) records held like an SRS (freed when dropped).  log_l = 0 is `open_all_table`.
+    pub fn open_chunks_table(&self, log_n: u32, log_l: u32) -> OwnedSrs {
+        let mut id = 0u32;
+        self.backend.check(unsafe { ffi::typlonk_srs_open_chunks_table(self.backend.ctx, self.handle.id, log_n, log_l, &mut id) });
+        OwnedSrs { backend: self.backend.clone(), handle: SrsHandle { id, len: 2usize << log_n } }
+    }
+    /// `typlonk_open_chunks_host` over `self`, a table made by `open_chunks_table` with this `log_l`: for each polynomial (all of one
+    /// length, 1..=n coefficients of 4 Montgomery limbs) the r = n >> log_l multi-proofs, proof k of polynomial p at p r + k, and the
+    /// n evaluations chunk-major: evals[p n + k l + t] = f_p(w^(k + r t)).  (The buffers are sized for the table's domain, not for
+    /// log_l, so a log_l other than the table's mis-sizes the result and nothing else.)
+    pub fn open_chunks(&self, log_l: u32, polys: &[&[[u64; 4]]]) -> (Vec<[u64; 12]>, Vec<u8>, Vec<[u64; 4]>) {
+        let n = self.handle.len / 2;
+        let count = polys.len();
+        let m = polys.first().map_or(0, |p| p.len());
+        assert!(polys.iter().all(|p| p.len() == m), "open_chunks: the polynomials of one call have one length");
+        let ptrs: Vec<*const u64> = polys.iter().map(|p| p.as_ptr() as *const u64).collect();
+        let mut xy = vec![[0u64; 12]; count * n];
+        let mut inf = vec![0u8; count * n];
+        let mut evals = vec![[0u64; 4]; count * n];
+        self.backend.check(unsafe {
+            ffi::typlonk_open_chunks_host(self.backend.ctx, self.handle.id, ptrs.as_ptr(), m, count,
+                                          xy.as_mut_ptr() as *mut u64, inf.as_mut_ptr(), evals.as_mut_ptr() as *mut u64)
+        });
+        xy.truncate(count * (n >> log_l));
+        inf.truncate(count * (n >> log_l));
+        (xy, inf, evals)
+    }
 }
 impl Drop for OwnedSrs {
     fn drop(&mut self) {

@@ -42,6 +42,7 @@ SYMBOLS = [
     "typlonk_witness_solve_plan", "typlonk_witness_solve", "typlonk_circuit_set_hints",
     "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute", "typlonk_srs_g1_ntt",
     "typlonk_srs_open_all_table", "typlonk_open_all_dev", "typlonk_open_all_host",
+    "typlonk_srs_open_chunks_table", "typlonk_open_chunks_dev", "typlonk_open_chunks_host",
 ]
 VERIFY_PI_AS_PROVER = 1
 SRS_TO_LAGRANGE, SRS_FROM_LAGRANGE = 0, 1   # typlonk_srs_g1_ntt's direction
@@ -406,6 +407,10 @@ def load_library() -> C.CDLL:
         lib.typlonk_srs_open_all_table.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.typlonk_open_all_dev.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.c_size_t, u64p, u8p, u64p]
         lib.typlonk_open_all_host.argtypes = [vp, C.c_uint32, u64p, C.c_size_t, u64p, u8p, u64p]
+    if hasattr(lib, "typlonk_open_chunks_dev") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        lib.typlonk_srs_open_chunks_table.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.typlonk_open_chunks_dev.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, u64p, u8p, u64p]
+        lib.typlonk_open_chunks_host.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_size_t, u64p, u8p, u64p]
     _lib = lib
     return lib
 
@@ -779,6 +784,44 @@ class Context:
             co = _as_u64(coeffs_or_buf, 4)
             m = co.shape[0] if m is None else m
             self._chk(self.lib.typlonk_open_all_host(self.h, table, _u64p(co), m, _u64p(xy), _u8p(inf), evp))
+        return (xy, inf, ev) if evals else (xy, inf)
+
+    def srs_open_chunks_table(self, sid: int, log_n: int, log_l: int) -> int:
+        """typlonk_srs_open_chunks_table: the id of the table `open_chunks` needs for the domain of 2^log_n points cut into cosets
+        of 2^log_l over the entry `sid` (2^(log_n + 1) records; released by srs_free).  log_l = 0 is srs_open_all_table's table."""
+        new = C.c_uint32()
+        self._chk(self.lib.typlonk_srs_open_chunks_table(self.h, sid, log_n, log_l, C.byref(new)))
+        self._chunk_log_l = getattr(self, "_chunk_log_l", {})
+        self._chunk_log_l[new.value] = log_l   # (the outputs of open_chunks are sized by it; ids are never reused)
+        return new.value
+
+    def open_chunks(self, table: int, polys, m: int | None = None, evals: bool = True, offsets=None):
+        """typlonk_open_chunks_dev / _host: the multi-proofs of `count` polynomials on every coset of the table's domain.
+        polys: a list of DeviceBuffers (m coefficients from offsets[p], default 0; m = None: all of the first behind its offset) or
+        a list of host coefficient arrays (m, 4) u64 Montgomery, all of one length.  With r = n / l cosets of l points, returns
+        (xy (count, r, 12), inf (count, r)[, evals (count, r, l, 4) -- evals[p, k, t] = f_p(w^(k + r t))])."""
+        n = self.srs_len(table) // 2
+        log_l = getattr(self, "_chunk_log_l", {}).get(table, 0)   # (a table of srs_open_all_table: 0)
+        l = 1 << log_l
+        r = n // l
+        polys = list(polys)
+        count = len(polys)
+        xy = np.zeros((count, r, 12), dtype=np.uint64)
+        inf = np.zeros((count, r), dtype=np.uint8)
+        ev = np.zeros((count, r, l, 4), dtype=np.uint64) if evals else None
+        evp = _u64p(ev) if evals else None
+        if count and isinstance(polys[0], DeviceBuffer):
+            offs = [0] * count if offsets is None else [int(o) for o in offsets]
+            m = polys[0].n - offs[0] if m is None else m
+            handles = (C.c_void_p * count)(*[p.handle for p in polys])
+            self._chk(self.lib.typlonk_open_chunks_dev(self.h, table, handles, (C.c_size_t * count)(*offs), m, count, _u64p(xy), _u8p(inf), evp))
+        else:
+            cos = [_as_u64(p, 4) for p in polys]
+            m = (cos[0].shape[0] if count else 0) if m is None else m
+            if any(c.shape[0] < m for c in cos):
+                raise ValueError("open_chunks: a polynomial holds fewer than m coefficients")
+            ptrs = (C.c_void_p * max(count, 1))(*[c.ctypes.data for c in cos])
+            self._chk(self.lib.typlonk_open_chunks_host(self.h, table, ptrs, m, count, _u64p(xy), _u8p(inf), evp))
         return (xy, inf, ev) if evals else (xy, inf)
 
     def g1_decompress(self, data, skip_subgroup: bool = False):

@@ -65,6 +65,9 @@ struct SrsEntry {
     // typlonk_srs_open_all_table: this entry is the table of the domain of 2^open_all_log_n points (len = twice that many
     // records); 0: not a table
     uint32_t open_all_log_n = 0;
+    // typlonk_srs_open_chunks_table: the table's cosets hold 2^open_chunks_log_l points each (l blocks of 2n / l records);
+    // 0: one point per coset, the table of typlonk_srs_open_all_table
+    uint32_t open_chunks_log_l = 0;
     size_t total() const { return total_len ? total_len : len; }
     // part [off, off + ml) of an m-term MSM that falls into this entry
     void local_range(size_t m, size_t* off, size_t* ml) const {

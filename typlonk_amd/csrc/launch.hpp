@@ -147,5 +147,25 @@ void launch_g1_pointwise_mul(const Fr* k, uint64_t n, const uint32_t* src, uint3
 void launch_open_all_gather(const uint32_t* src, uint32_t* dst, uint64_t n, hipStream_t st);
 // c[0, 2n) = k * (f[n-1], 0 x n, f[0], ..., f[n-2]) for the m <= n coefficients of f (zero above); f and c must not overlap
 void launch_open_all_coeffs(const Fr* f, uint64_t m, uint64_t n, const Fr& k, Fr* c, hipStream_t st);
+// typlonk_open_chunks_* (kernels: srs_gen.hip; host: open_chunks.hip)
+// launch_srs_g1_ntt_stage for `blocks` transforms of 2^l >= 2 records in one launch: block b is src[b * src_stride, + 2^l), read by
+// stage 1 bit-reversed, and dst[b * dst_stride, + 2^l), worked on in place by the later stages.  Strides in records, >= 2^l;
+// src and dst must not overlap.
+void launch_srs_g1_ntt_batch_stage(const Fr& root, uint32_t l, uint32_t stage, uint64_t blocks, const uint32_t* src, uint64_t src_stride,
+                                   uint32_t* dst, uint64_t dst_stride, hipStream_t st);
+// dst[o] = sum_{j < l} [k[(p l + j) period + i]] tab[j period + i], p = o / period, i = o % period, o < outputs: k CANONICAL words
+// (not Montgomery residues) on the device, canonical affine records.  l and g powers of two, g <= min(l, 64) the slices an
+// output's terms are cut into (open_chunks_plan.hpp); every g gives the same words.  outputs a multiple of period >= 1.
+void launch_g1_pointwise_msm(const Fr* k, const uint32_t* tab, uint32_t* dst, uint64_t outputs, uint64_t period, uint32_t l, uint32_t g,
+                             hipStream_t st);
+// dst[j 2r + i] = src[(r - 2 - i) l + j] for i + 1 < r, the identity for r - 1 <= i < 2r; j < l.  r >= 2; reads src[0, r l - l)
+void launch_open_chunks_gather(const uint32_t* src, uint32_t* dst, uint64_t r, uint64_t l, hipStream_t st);
+// c[(p l + j) 2r + i] = k * (f_((r-1) l + j), 0 x r, f_(j), f_(l + j), ..., f_((r-2) l + j))[i] for the m <= r l coefficients of
+// f[p] (zero above), p < count; f: `count` device pointers, on the device
+void launch_open_chunks_coeffs(const Fr* const* f, uint64_t m, uint64_t r, uint64_t l, uint64_t count, const Fr& k, Fr* c, hipStream_t st);
+// e[p n + i] = f[p][i] for i < m, zero for m <= i < n
+void launch_open_chunks_pad(const Fr* const* f, uint64_t m, uint64_t n, uint64_t count, Fr* e, hipStream_t st);
+// out[p r l + k l + t] = ev[p r l + k + r t]; ev and out must not overlap
+void launch_open_chunks_evals(const Fr* ev, uint64_t r, uint64_t l, uint64_t count, Fr* out, hipStream_t st);
 
 }  // namespace ty

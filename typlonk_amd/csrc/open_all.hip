@@ -26,6 +26,8 @@ int table_entry(typlonk_ctx* ctx, uint32_t table_id, const SrsEntry** out) {
     auto it = ctx->srs.find(table_id);
     if (it == ctx->srs.end()) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "unknown table id");
     if (!it->second.open_all_log_n) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "this SRS entry is not a table of typlonk_srs_open_all_table");
+    if (it->second.open_chunks_log_l)
+        return fail(ctx, TYPLONK_ERR_INVALID_ARG, "this table's cosets hold more than one point (typlonk_srs_open_chunks_table, log_l > 0): typlonk_open_chunks_* takes it");
     *out = &it->second;
     return TYPLONK_OK;
 }

@@ -359,6 +359,17 @@ class Srs {
         if (has_g2_) r.set_g2(g2_, g2s_);
         return r;
     }
+    // typlonk_srs_open_chunks_table: the table KzgScheme::open_chunks needs for the domain of 2^log_n points cut into cosets of 2^log_l
+    // points -- held as open_all_table's, which it is, word for word, at log_l = 0.  chunk_log_l() reports the log_l of a table.
+    Srs open_chunks_table(uint32_t log_n, uint32_t log_l) const {
+        Srs r(*ctx_);
+        typlonk::check(typlonk_srs_open_chunks_table(ctx_->raw(), id_, log_n, log_l, &r.id_), ctx_->raw());
+        r.len_ = (size_t)2 << log_n;
+        r.chunk_log_l_ = log_l;
+        if (has_g2_) r.set_g2(g2_, g2s_);
+        return r;
+    }
+    uint32_t chunk_log_l() const { return chunk_log_l_; }
     std::vector<G1Point> g1_ref() const {  // downloads the points (the reference returns &Vec<G1Point>); a shard: its slice
         const size_t cnt = sharded_ ? local_len_ : len_;
         std::vector<uint64_t> xy(cnt * 12);
@@ -401,6 +412,7 @@ class Srs {
     uint32_t id_ = 0;
     size_t len_ = 0, local_len_ = 0;
     bool sharded_ = false;
+    uint32_t chunk_log_l_ = 0;
     pairing::G2Affine g2_{}, g2s_{};
     bool has_g2_ = false;
 };
@@ -414,6 +426,12 @@ struct KzgOpening {
     G1Point p;
     Fr y;
     Fr eval() const { return y; }
+};
+
+// one multi-proof: the opening of a polynomial at the l points w^(k + r t), t < l, of coset k, with its l evaluations in that order
+struct KzgChunkOpening {
+    G1Point p;
+    std::vector<Fr> ys;
 };
 
 class KzgScheme {
@@ -445,6 +463,33 @@ class KzgScheme {
             out[k].p.infinity = inf[k] != 0;
             out[k].y = ys[k];
         }
+        return out;
+    }
+    // typlonk_open_chunks_host: for each polynomial (all of one length, 1 <= coefficients <= n) its r = n / l multi-proofs over
+    // `table` (Srs::open_chunks_table or open_all_table of this scheme's SRS), l = 2^table.chunk_log_l(): result[p][k] opens
+    // polynomial p on coset k, the roots of X^l - w^(k l).  A verifier needs [s^l]G2, which an Srs does not hold.
+    std::vector<std::vector<KzgChunkOpening>> open_chunks(const Srs& table, const std::vector<Poly>& polynomials) const {
+        if (polynomials.empty() || polynomials[0].coeffs.empty()) throw std::runtime_error("at least 1");
+        const size_t n = table.len() / 2, l = (size_t)1 << table.chunk_log_l(), r = n / l, count = polynomials.size();
+        const size_t m = polynomials[0].coeffs.size();
+        std::vector<const uint64_t*> co(count);
+        for (size_t p = 0; p < count; ++p) {
+            if (polynomials[p].coeffs.size() != m) throw std::runtime_error("open_chunks: the polynomials of one call have one length");
+            co[p] = polynomials[p].coeffs[0].limbs();
+        }
+        std::vector<uint64_t> xy(count * r * 12);
+        std::vector<uint8_t> inf(count * r);
+        std::vector<Fr> ys(count * n);
+        check(typlonk_open_chunks_host(srs_.ctx().raw(), table.id(), co.data(), m, count, xy.data(), inf.data(), ys[0].limbs()),
+              srs_.ctx().raw());
+        std::vector<std::vector<KzgChunkOpening>> out(count, std::vector<KzgChunkOpening>(r));
+        for (size_t p = 0; p < count; ++p)
+            for (size_t k = 0; k < r; ++k) {
+                KzgChunkOpening& o = out[p][k];
+                std::memcpy(o.p.xy, &xy[(p * r + k) * 12], 96);
+                o.p.infinity = inf[p * r + k] != 0;
+                o.ys.assign(ys.begin() + (p * n + k * l), ys.begin() + (p * n + (k + 1) * l));
+            }
         return out;
     }
     KzgCommitment identity() const { return commit(Poly::from_coefficients_vec({Fr(1)})); }
