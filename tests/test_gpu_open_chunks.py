@@ -104,6 +104,10 @@ def test_the_table_is_the_reference_table(ctx):
 # ---- 2. l = 1 against the code that exists ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("log_n", [1, 4, 7])
 def test_one_point_per_coset_is_open_all(ctx, log_n):
+    """typlonk_open_all_* and typlonk_srs_open_all_table are now entry points over the code of typlonk_open_chunks_* at
+    log_l = 0, so both sides of every comparison below run the same kernels: what it still checks is the entry points' wrapping
+    (one polynomial, one offset, count = 1) and the refusal open_all alone makes.  The independent check of the one-point path
+    is tests/test_gpu_open_all.py, against the Python oracle."""
     from typlonk_amd.capi import ERR_INVALID_ARG, TyplonkError
 
     n = 1 << log_n

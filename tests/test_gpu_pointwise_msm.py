@@ -1,4 +1,4 @@
-"""The two kernels typlonk_open_chunks_* adds to the hot path -- srs_gen.hip compiled as the library compiles it, behind the test-only
+"""The two kernels the FK20 openings run on their hot path -- g1_fft.hip compiled as the library compiles it, behind the test-only
 harness tests/cpp/libdevice_chunks.so -- with their launchers called directly.
 
 g1_pointwise_msm_kernel: dst[o] = sum_{j<l} [k_(o,j)] y_(o,j).  Through the library a small shape only ever reaches the largest
@@ -187,7 +187,10 @@ def _point_of_words(words):
 @pytest.mark.parametrize("blocks", [1, 3, 4])
 def test_batched_stages(ctx, lib, pool, l, blocks):
     """block b of the launch equals typlonk_srs_g1_ntt over that block alone: forward as TYPLONK_SRS_FROM_LAGRANGE gives it, the
-    inverse direction, which the stages leave unscaled, as the same records in the order 0, N - 1, ..., 1"""
+    inverse direction, which the stages leave unscaled, as the same records in the order 0, N - 1, ..., 1.
+    typlonk_srs_g1_ntt shares the stage loop and the butterfly with this launcher but runs its single block through
+    srs_g1_ntt_stage_kernel, so the two sides differ in the indexing kernel only; the independent check of the butterfly is
+    tests/test_gpu_srs_lagrange.py, against closed forms."""
     n = 1 << l
     src_stride, dst_stride = n + 3, n + 1
     rng = np.random.default_rng(0x57A + 16 * l + blocks)

@@ -4,8 +4,9 @@ session.  Median host wall time of REPS blocking calls (REPS_BIG at 2^20 and abo
 
 Then the pointwise pass alone, through the test harness tests/cpp/libdevice_chunks.so (event times of the launch, median of
 REPS_KERNEL after one untimed launch): g1_pointwise_msm_kernel at g = 1, at the plan's g (tests/cpp/open_chunks_plan_host) and at
-the largest g, and g1_pointwise_mul_kernel -- the parent's kernel -- over the same count x 2n (scalar, record) pairs one by one,
-which is what the plain route pays before it has summed anything.  The records are multiples of G drawn from a small pool and the
+the largest g, and the same kernel at l = 1, g = 1 -- one ladder per record, one launch per polynomial, as the one-point opening
+runs it -- over the same count x 2n (scalar, record) pairs one by one, which is what the plain route pays before it has summed
+anything (pointwise_mul_same_pairs_ms; up to profiles/r31 that figure was g1_pointwise_mul_kernel's, which is gone).  The records are multiples of G drawn from a small pool and the
 scalars random below 2^254; one shape's outputs at the plan's g are compared word for word with those at g = 1.
 
     SHAPES=16:4:1:1,20:6:1:1,13:6:2:1,13:6:2:64 REPS=10 REPS_BIG=3 python tools/open_chunks_time.py

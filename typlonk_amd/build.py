@@ -11,7 +11,7 @@
   tests/cpp/libsigma_cell_host.so host build of sigma_cell, the per-cell body of typlonk_circuit_compile (tests/test_circuit_compile_host.py) -- g++
   tests/cpp/perm_pairs_host       host build of the union-find of typlonk_permutation_from_pairs, a program of its own (tests/test_perm_pairs_host.py) -- g++
   tests/cpp/msm_plan_host         host build of msm_plan, every decision of an MSM, a program of its own (tests/test_msm_plan_host.py) -- g++
-  tests/cpp/libdevice_chunks.so   device harness over srs_gen.hip, the pointwise pass and the batched group transform of typlonk_open_chunks_*
+  tests/cpp/libdevice_chunks.so   device harness over g1_fft.hip, the pointwise pass and the batched group transform of typlonk_open_chunks_*
                                   (tests/test_gpu_pointwise_msm.py) -- hipcc
   tests/cpp/open_chunks_plan_host host build of open_chunks_plan, the launch shape of that pointwise pass, a program of its own
                                   (tests/test_open_chunks_plan_host.py) -- g++
@@ -62,7 +62,7 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip", "open_all.hip", "open_chunks.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip", "g1_fft.hip", "open_chunks.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -209,12 +209,12 @@ def build_device_accum(force: bool = False) -> str:
 
 
 def build_device_chunks(force: bool = False) -> str:
-    """tests/cpp/libdevice_chunks.so: csrc/harness/device_chunks.hip, srs_gen.hip compiled as a unit behind entry points that run the
+    """tests/cpp/libdevice_chunks.so: csrc/harness/device_chunks.hip, g1_fft.hip compiled as a unit behind entry points that run the
     pointwise pass of typlonk_open_chunks_* with a named number of slices and the batched stages of the group transform at named
     strides (tests/test_gpu_pointwise_msm.py).  Test-only and not linked into the shipped library; the flags are build_hip()'s."""
     src = os.path.join(CSRC, "harness", "device_chunks.hip")
     out = os.path.join(ROOT, "tests", "cpp", "libdevice_chunks.so")
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "srs_gen.hip")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "g1_fft.hip")]
     if force or _stale(out, [src] + deps):
         _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
     return out

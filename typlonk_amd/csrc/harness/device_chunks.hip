@@ -1,13 +1,13 @@
 // Test-only device harness over the kernels of typlonk_open_chunks_* (tests/test_gpu_pointwise_msm.py).
 //
-// srs_gen.hip is compiled here as a unit, exactly as the library compiles it (same flags, no extra defines).  dc_pointwise_msm runs
+// g1_fft.hip is compiled here as a unit, exactly as the library compiles it (same flags, no extra defines).  dc_pointwise_msm runs
 // launch_g1_pointwise_msm with the number of slices the caller names -- through the library a small shape only ever reaches the
 // largest -- and dc_ntt_stages runs the stages of launch_srs_g1_ntt_batch_stage over blocks at the strides the caller names, with
 // the roots the caller hands in.  Points come and go in the SRS's internal form (PT_WORDS words a record).  Every output buffer
 // is allocated at exactly the size the launcher may write, followed by a guard band.
 // Nothing is launched on a shape a kernel could leave its buffers with: the checks run on the host before the first HIP call.
 // Not linked into libtyplonk_hip.so.  It lives beside the unit it wraps, as device_reduce.hip and device_accum.hip do.
-#include "../srs_gen.hip"
+#include "../g1_fft.hip"
 
 #include <vector>
 
@@ -71,9 +71,10 @@ extern "C" int dc_pointwise_msm(const uint32_t* k, const uint32_t* tab, uint64_t
 }
 
 // The same launch `reps` times between events, after one untimed launch, for tools/open_chunks_time.py: msm_ms[reps] the
-// milliseconds of launch_g1_pointwise_msm with g slices (g = 0: skipped), mul_ms[reps] (NULL: skipped) those of
-// launch_g1_pointwise_mul over the same outputs * l (scalar, record) pairs one by one, the table repeated for every polynomial --
-// the ladders the joint kernel's sums would cost as separate scalar multiplications, without the additions that sum them.
+// milliseconds of launch_g1_pointwise_msm with g slices (g = 0: skipped), mul_ms[reps] (NULL: skipped) those of the same
+// launcher at l = 1, g = 1 -- one ladder per record, as the one-point opening runs it -- over the same outputs * l (scalar,
+// record) pairs one by one, one launch per polynomial over the whole table: the ladders the joint kernel's sums would cost as
+// separate scalar multiplications, without the additions that sum them.
 extern "C" int dc_time_pointwise(const uint32_t* k, const uint32_t* tab, uint64_t outputs, uint64_t period, uint32_t l, uint32_t g,
                                  uint32_t reps, float* msm_ms, float* mul_ms) {
     if (!k || !tab || (g && !msm_ms) || reps == 0 || reps > 100) return (int)hipErrorInvalidValue;
@@ -98,7 +99,7 @@ extern "C" int dc_time_pointwise(const uint32_t* k, const uint32_t* tab, uint64_
     for (uint32_t it = 0; it <= reps && err == hipSuccess && mul_ms; ++it) {
         err = hipEventRecord(a, 0);
         for (uint64_t p = 0; p < polys; ++p)
-            launch_g1_pointwise_mul(static_cast<const Fr*>(d_k.p) + p * l * period, l * period, d_tab.u32(), d_rec.u32(), 0);
+            launch_g1_pointwise_msm(static_cast<const Fr*>(d_k.p) + p * l * period, d_tab.u32(), d_rec.u32(), l * period, l * period, 1, 1, 0);
         if (err == hipSuccess) err = hipEventRecord(b, 0);
         if (err == hipSuccess) err = hipEventSynchronize(b);
         if (err == hipSuccess && it) err = hipEventElapsedTime(&mul_ms[it - 1], a, b);

@@ -19,9 +19,9 @@
 //   witness_check.hip  typlonk_circuit_permutation, typlonk_witness_check: which gate rows and copy constraints a witness fails;
 //                 typlonk_circuit_compile: a circuit from selector evaluations and the permutation itself (sigma_cell.hpp)
 //   srs_check.hip typlonk_srs_check, typlonk_srs_contribute: a loaded SRS against [s]G2, and [t^i] g1[i]; typlonk_srs_g1_ntt:
-//                 the Lagrange form of an SRS and back (kernels: srs_gen.hip)
-//   open_all.hip  typlonk_srs_open_all_table, typlonk_open_all_*: a polynomial's openings at every point of its domain
-//                 (kernels: srs_gen.hip)
+//                 the Lagrange form of an SRS and back (kernels: srs_gen.hip, g1_fft.hip)
+//   open_chunks.hip  typlonk_srs_open_chunks_table, typlonk_open_chunks_*: a polynomial's openings on every coset of its domain,
+//                 and typlonk_srs_open_all_table, typlonk_open_all_*: the same at one point per coset (kernels: g1_fft.hip)
 // There is deliberately no CPU compute fallback: without a HIP device typlonk_init fails with TYPLONK_ERR_NO_DEVICE.
 #pragma once
 #include "../../include/typlonk.h"
@@ -373,9 +373,11 @@ int msm_finish(typlonk_ctx* ctx, MsmWs& ws);
 int points_to_host(typlonk_ctx* ctx, const uint32_t* d_points, size_t count, uint64_t* xy, uint8_t* inf);
 
 // ---- srs_check.hip --------------------------------------------------------------------------------------------------
-// the log_n >= 1 stages of the transform of 2^log_n records in the group, queued on the context's stream: stage 1 reads src
-// through the bit reversal into dst, the later ones work on dst in place (src and dst must not overlap).  No scaling.
-int g1_ntt_stages(typlonk_ctx* ctx, const uint32_t* src, uint32_t* dst, uint32_t log_n, bool inverse);
+// the l >= 1 stages of `blocks` transforms of 2^l records each in the group, queued on the context's stream, one launch per
+// stage: stage 1 reads block b at src + b * src_stride records through the bit reversal into dst + b * dst_stride, the later
+// ones work on dst in place (strides >= 2^l; src and dst must not overlap).  No scaling.
+int g1_ntt_stages(typlonk_ctx* ctx, uint32_t l, uint64_t blocks, const uint32_t* src, uint64_t src_stride, uint32_t* dst,
+                  uint64_t dst_stride, bool inverse);
 
 // Asynchronous MSM submissions over one SRS (a prover round, or typlonk_msm_g1_batch_devptr).
 //   submit()    puts an MSM on the next lane of [lane_lo, lanes): the lane first waits for everything queued on the

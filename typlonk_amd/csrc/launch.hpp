@@ -134,25 +134,16 @@ void launch_srs_membership(const uint32_t* pts, uint64_t n, unsigned long long* 
 void launch_fr_powers(const Fr& rho, uint64_t n, Fr* pw, Fr* pw_shift, hipStream_t st);
 // dst[i] = [t^i] src[i], canonical affine records; src and dst must not overlap
 void launch_srs_contribute(const Fr& t, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st);
-// typlonk_srs_g1_ntt: stage 1 <= stage <= log_n of the transform of 2^log_n >= 2 points, root = the generator of the domain of
-// size 2^stage (forward) or its inverse.  Stage 1 reads src[0, 2^log_n) bit-reversed into dst; later stages work on dst in
-// place.  src and dst must not overlap.
+// typlonk_srs_g1_ntt and the FK20 openings (kernels: g1_fft.hip; host: srs_check.hip, open_chunks.hip)
+// Stage 1 <= stage <= l of `blocks` transforms of 2^l >= 2 points in one launch, l <= 25, root = the generator of the domain of
+// size 2^stage (forward) or its inverse: block b is src[b * src_stride, + 2^l), read by stage 1 bit-reversed, and
+// dst[b * dst_stride, + 2^l), worked on in place by the later stages.  Strides in records, >= 2^l; src and dst must not overlap.
+void launch_srs_g1_ntt_batch_stage(const Fr& root, uint32_t l, uint32_t stage, uint64_t blocks, const uint32_t* src, uint64_t src_stride,
+                                   uint32_t* dst, uint64_t dst_stride, hipStream_t st);
+// the same stage of one transform, blocks = 1, src and dst its first records: the faster kernel there (g1_fft.hip)
 void launch_srs_g1_ntt_stage(const Fr& root, uint32_t log_n, uint32_t stage, const uint32_t* src, uint32_t* dst, hipStream_t st);
 // pts[i] <- [k] pts[i], canonical affine records, in place
 void launch_srs_g1_scale(const Fr& k, uint64_t n, uint32_t* pts, hipStream_t st);
-// typlonk_open_all_* (kernels: srs_gen.hip; host: open_all.hip)
-// dst[i] = [k[i]] src[i], i < n: k Montgomery residues on the device, canonical affine records; dst may be src
-void launch_g1_pointwise_mul(const Fr* k, uint64_t n, const uint32_t* src, uint32_t* dst, hipStream_t st);
-// dst[0, 2n) = (src[n-2], ..., src[0], identity x (n + 1)); n >= 2; src and dst must not overlap
-void launch_open_all_gather(const uint32_t* src, uint32_t* dst, uint64_t n, hipStream_t st);
-// c[0, 2n) = k * (f[n-1], 0 x n, f[0], ..., f[n-2]) for the m <= n coefficients of f (zero above); f and c must not overlap
-void launch_open_all_coeffs(const Fr* f, uint64_t m, uint64_t n, const Fr& k, Fr* c, hipStream_t st);
-// typlonk_open_chunks_* (kernels: srs_gen.hip; host: open_chunks.hip)
-// launch_srs_g1_ntt_stage for `blocks` transforms of 2^l >= 2 records in one launch: block b is src[b * src_stride, + 2^l), read by
-// stage 1 bit-reversed, and dst[b * dst_stride, + 2^l), worked on in place by the later stages.  Strides in records, >= 2^l;
-// src and dst must not overlap.
-void launch_srs_g1_ntt_batch_stage(const Fr& root, uint32_t l, uint32_t stage, uint64_t blocks, const uint32_t* src, uint64_t src_stride,
-                                   uint32_t* dst, uint64_t dst_stride, hipStream_t st);
 // dst[o] = sum_{j < l} [k[(p l + j) period + i]] tab[j period + i], p = o / period, i = o % period, o < outputs: k CANONICAL words
 // (not Montgomery residues) on the device, canonical affine records.  l and g powers of two, g <= min(l, 64) the slices an
 // output's terms are cut into (open_chunks_plan.hpp); every g gives the same words.  outputs a multiple of period >= 1.

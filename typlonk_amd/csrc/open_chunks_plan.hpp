@@ -1,4 +1,4 @@
-// The launch shape of typlonk_open_chunks_*'s pointwise pass (g1_pointwise_msm_kernel, srs_gen.hip), decided on the host before
+// The launch shape of typlonk_open_chunks_*'s pointwise pass (g1_pointwise_msm_kernel, g1_fft.hip), decided on the host before
 // anything is queued, in the manner of msm_plan / ntt_plan / solve_plan: a pure function of (count, r, l) with no HIP include, so
 // that a host program can walk it over a grid (tests/cpp/open_chunks_plan_host.cpp).
 //

@@ -1,7 +1,7 @@
 // libtyplonk_hip.so -- a powers-of-tau step (include/typlonk.h): typlonk_srs_check, typlonk_srs_check_challenge,
 // typlonk_srs_contribute -- and typlonk_srs_g1_ntt, the Lagrange form of an SRS (at the end).  Host side only; the kernels
-// (srs_membership_kernel, fr_powers_kernel, srs_contribute_kernel, srs_g1_ntt_stage_kernel, srs_g1_scale_kernel) are in
-// srs_gen.hip, beside the generator they share a ladder and the fixed base with.
+// (srs_membership_kernel, fr_powers_kernel, srs_contribute_kernel) are in srs_gen.hip, beside the generator they share the
+// fixed base with, and the transform's (srs_g1_ntt_stage_kernel, srs_g1_ntt_batch_stage_kernel, srs_g1_scale_kernel) in g1_fft.hip.
 //
 // The check: g1[i+1] = [s] g1[i] for every i is  e(g1[i], [s]G2) = e(g1[i+1], G2)  for every i; weighted with rho^i and
 // summed on the G1 side -- both pairings are linear there -- the len - 1 equations become ONE product
@@ -187,19 +187,22 @@ int typlonk_srs_contribute(typlonk_ctx* ctx, uint32_t srs_id, const uint64_t t[4
     return TYPLONK_OK;
 }
 
-// One launch per stage (srs_g1_ntt_stage_kernel, srs_gen.hip); typlonk_srs_g1_ntt below and the three transforms of
-// typlonk_open_all_* (open_all.hip)
-int tyh::g1_ntt_stages(typlonk_ctx* ctx, const uint32_t* src, uint32_t* dst, uint32_t log_n, bool inverse) {
-    for (uint32_t stage = 1; stage <= log_n; ++stage) {
-        launch_srs_g1_ntt_stage(inverse ? fr_domain_root_inv(stage) : fr_domain_root(stage), log_n, stage, src, dst, ctx->stream);
+// One launch per stage (g1_fft.hip); typlonk_srs_g1_ntt below, one block, and the transforms of the openings (open_chunks.hip).
+// A single block goes to srs_g1_ntt_stage_kernel, which measures faster there, several to the batched kernel.
+int tyh::g1_ntt_stages(typlonk_ctx* ctx, uint32_t l, uint64_t blocks, const uint32_t* src, uint64_t src_stride, uint32_t* dst,
+                       uint64_t dst_stride, bool inverse) {
+    for (uint32_t stage = 1; stage <= l; ++stage) {
+        const Fr root = inverse ? fr_domain_root_inv(stage) : fr_domain_root(stage);
+        if (blocks == 1) launch_srs_g1_ntt_stage(root, l, stage, src, dst, ctx->stream);
+        else launch_srs_g1_ntt_batch_stage(root, l, stage, blocks, src, src_stride, dst, dst_stride, ctx->stream);
         HIPCHK(hipGetLastError());
     }
     return TYPLONK_OK;
 }
 
 // The Lagrange form of a monomial SRS and back: an NTT over the first 2^log_n points of the entry, in the group.  Stage by
-// stage on the new entry's own records (srs_g1_ntt_stage_kernel, srs_gen.hip); the inverse direction's 1/n is a pass of its
-// own behind the last stage (srs_g1_scale_kernel).
+// stage on the new entry's own records (g1_ntt_stages at one block; log_n <= 25: the stage kernels' indices within a block are
+// 32-bit, g1_fft.hip); the inverse direction's 1/n is a pass of its own behind the last stage (srs_g1_scale_kernel).
 int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t direction, uint32_t* new_srs_id) {
     if (!ctx) return TYPLONK_ERR_INVALID_ARG;
     if (!new_srs_id) return fail(ctx, TYPLONK_ERR_INVALID_ARG, "null argument");
@@ -219,7 +222,7 @@ int typlonk_srs_g1_ntt(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32
     guard.add(e.d_points);
     const bool inverse = direction == TYPLONK_SRS_TO_LAGRANGE;
     if (log_n == 0) HIPCHK(hipMemcpyAsync(e.d_points, src->d_points, PT_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    if (log_n && (rc = g1_ntt_stages(ctx, src->d_points, e.d_points, log_n, inverse))) return rc;
+    if (log_n && (rc = g1_ntt_stages(ctx, log_n, 1, src->d_points, n, e.d_points, n, inverse))) return rc;
     if (inverse && log_n) {
         launch_srs_g1_scale(fr_inv_pow2(log_n), (uint64_t)n, e.d_points, ctx->stream);
         HIPCHK(hipGetLastError());
