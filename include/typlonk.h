@@ -1026,6 +1026,74 @@ int typlonk_open_chunks_dev(typlonk_ctx* ctx, uint32_t table_id, const typlonk_b
  * count x m Fr. */
 int typlonk_open_chunks_host(typlonk_ctx* ctx, uint32_t table_id, const uint64_t* const* coeffs, size_t m, size_t count,
                              uint64_t* proofs_xy, uint8_t* proofs_inf, uint64_t* evals);
+/* ---- verify multi-proofs: a batch of cells per call.  n, l, r, w and a_k = w^(k l) as above.  A CELL i < N is
+ * (c_i, k_i, E_i, pi_i): an index c_i < M into the M commitments, a coset index k_i < r, the l evaluations in the order
+ * typlonk_open_chunks_* writes them, E_i[t] = f(w^(k_i + r t)), and a proof.  It is valid iff
+ *     e(C_(c_i) - [I_i(s)] G + [a_(k_i)] pi_i, G2) = e(pi_i, [s^l] G2)
+ * with I_i the polynomial of degree < l that takes the values E_i on coset k_i.  With the weights rho_i = rho^i, i the cell's
+ * position in the call, the live cells of a range [lo, hi) are checked by ONE product (a "fold"):
+ *     e(sum rho_i pi_i, [s^l]G2) * e(-(sum_c w_c C_c + sum rho_i a_(k_i) pi_i - [A(s)] G), G2) = 1
+ *     w_c = sum_{c_i = c} rho_i,    A_j = sum_i rho_i w^(-k_i j) (1/l) sum_t E_i[t] mu^(-j t),   mu = w^r,  j < l
+ * Two MSMs over a temporary entry holding the N proofs and the M commitments, one l-term MSM of A over the first l points of
+ * entry srs_id (they must be [s^j] G of the same s as g2sl_xy: typlonk_srs_check decides that), a G1 addition and two Miller
+ * loops with one final exponentiation on the host.  A, w_c and the weights are computed on the device.
+ *   inputs      all in HOST memory.  commits_xy / commits_inf: M points, proofs_xy / proofs_inf: N points, 12 limbs and a flag
+ *               each, as typlonk_srs_download writes them (a coordinate >= p is reduced mod p, as typlonk_srs_load does);
+ *               cell_commit, cell_coset: N indices each; evals: N x l x 4 limbs, canonical Montgomery Fr; g2sl_xy: [s^l]G2 as
+ *               x.c0 x.c1 y.c0 y.c1.
+ *   status[i]   the FIRST class that applies to cell i; a bad cell is DATA, not an error of the call:
+ *                 TYPLONK_CELL_OK              the equation holds
+ *                 TYPLONK_CELL_BAD_EVAL        an evaluation is not a canonical residue (judged on the host before the upload)
+ *                 TYPLONK_CELL_BAD_POINT       the proof is off the curve or outside the subgroup of order r
+ *                 TYPLONK_CELL_BAD_COMMITMENT  the same, for the cell's commitment
+ *                 TYPLONK_CELL_BAD_PROOF       the equation fails
+ *               Membership of the N + M points is decided on the device, one flag per point; an identity proof or commitment
+ *               is a group element.  A cell of one of the middle three classes is not LIVE: its weights are zero, a point that
+ *               failed membership is replaced by the identity, and nothing that is not a group element is summed or paired.
+ *   the fold    One fold over all live cells.  If it fails, the live cells are bisected: a range whose fold holds is
+ *               accepted, one that fails is cut in half by its live cells, down to single cells; b bad cells cost at most
+ *               2 b ceil(log2 N) + 1 folds.  rho_i stays the power of the cell's position in the whole call: the fold of a
+ *               sub-range only zeroes the weights outside it.
+ *   the seed    rho = Blake2b-512("typlonk/chunks/verify/v1" || seed || u64 log_n || u64 log_l || u64 N || u64 M || [s^l]G2 as
+ *               its 24 limbs), read as typlonk_srs_check reads its digest.  The library draws no randomness.  THE SEED MUST BE
+ *               UNKNOWN TO WHOEVER PRODUCED THE CELLS: someone who knows it can compute rho and craft defects that cancel
+ *               under these weights.  Draw it after the cells are fixed.  For a seed chosen independently of the cells a fold
+ *               accepts a range holding a bad cell with probability at most N l / r (r the group order, about 2^255), so a
+ *               call errs with probability at most (2 b ceil(log2 N) + 1) N l / r.
+ *   report      folds: the pairing products computed; live: the cells that reached the fold; count[s]: the cells of status s.
+ *   refusals    judged in this order; a refused or failed call leaves status and *report as they were:
+ *     TYPLONK_ERR_INVALID_ARG  a null pointer
+ *     TYPLONK_ERR_DOMAIN       log_n outside 1..24; log_l >= log_n; log_l > 10 (a cell's l elements are held in the LDS)
+ *     TYPLONK_ERR_LENGTH       N = 0, M = 0, N x l > 2^25 or N + M > 2^25
+ *     TYPLONK_ERR_INVALID_ARG  an unknown id; an SRS shard (with or without a communicator) or a table of
+ *                              typlonk_srs_open_*_table as srs_id; an entry of fewer than l points; g2sl_xy off the twist
+ *     TYPLONK_ERR_RANGE        some cell_commit[i] >= M or cell_coset[i] >= r
+ *     TYPLONK_ERR_OOM          an allocation is refused
+ * Blocks for the result; never a collective.  Temporaries, allocated by the call and freed on return: (N + M) x 128 bytes of
+ * records, N x l x 32 bytes of evaluations, 32 (6 N + 2 M) bytes of weights, 4 (2 N + M + 1) bytes of indices and at most
+ * 2048 x l x 32 bytes of partial sums (allocated once, for the whole call's workgroups; every fold of a bisection is cut into
+ * strips of the whole call's length and so never has more).  The temporary entry takes an id from the context's SRS ids for the
+ * duration of the call, as the temporary entries of typlonk_verify do: the ids handed out afterwards are higher by one. */
+#define TYPLONK_CELL_OK 0
+#define TYPLONK_CELL_BAD_EVAL 1
+#define TYPLONK_CELL_BAD_POINT 2
+#define TYPLONK_CELL_BAD_COMMITMENT 3
+#define TYPLONK_CELL_BAD_PROOF 4
+typedef struct typlonk_chunks_report {
+    uint32_t folds;      /* pairing products computed */
+    uint32_t reserved;   /* 0 */
+    uint64_t live;       /* cells that passed the per-cell checks and reached the fold */
+    uint64_t count[5];   /* cells per status, indexed by TYPLONK_CELL_* */
+} typlonk_chunks_report;
+int typlonk_verify_chunks(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uint32_t log_l, const uint64_t g2sl_xy[24],
+                          const uint8_t seed[32], const uint64_t* commits_xy /* M*12 */, const uint8_t* commits_inf /* M */,
+                          size_t M, const uint32_t* cell_commit /* N */, const uint32_t* cell_coset /* N */,
+                          const uint64_t* evals /* N*l*4 */, const uint64_t* proofs_xy /* N*12 */,
+                          const uint8_t* proofs_inf /* N */, size_t N, uint8_t* status /* N */, typlonk_chunks_report* report);
+/* Host-only, no GPU: the weight rho the call derives from (seed, log_n, log_l, N, M, g2sl_xy), as 4 Montgomery limbs.  It
+ * hashes the 24 limbs as given (no curve check); a null argument returns TYPLONK_ERR_INVALID_ARG. */
+int typlonk_verify_chunks_challenge(const uint8_t seed[32], uint32_t log_n, uint32_t log_l, uint64_t N, uint64_t M,
+                                    const uint64_t g2sl_xy[24], uint64_t rho[4]);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -43,6 +43,7 @@ SYMBOLS = [
     "typlonk_srs_check", "typlonk_srs_check_challenge", "typlonk_srs_contribute", "typlonk_srs_g1_ntt",
     "typlonk_srs_open_all_table", "typlonk_open_all_dev", "typlonk_open_all_host",
     "typlonk_srs_open_chunks_table", "typlonk_open_chunks_dev", "typlonk_open_chunks_host",
+    "typlonk_verify_chunks", "typlonk_verify_chunks_challenge",
 ]
 VERIFY_PI_AS_PROVER = 1
 SRS_TO_LAGRANGE, SRS_FROM_LAGRANGE = 0, 1   # typlonk_srs_g1_ntt's direction
@@ -126,6 +127,14 @@ class SrsReport(C.Structure):
     """typlonk_srs_report"""
     _fields_ = [("verdict", C.c_uint32), ("point_class", C.c_uint32), ("index", C.c_uint64), ("bad_points", C.c_uint64),
                 ("folds", C.c_uint32)]
+
+
+CELL_OK, CELL_BAD_EVAL, CELL_BAD_POINT, CELL_BAD_COMMITMENT, CELL_BAD_PROOF = 0, 1, 2, 3, 4   # TYPLONK_CELL_* of typlonk_verify_chunks
+
+
+class ChunksReport(C.Structure):
+    """typlonk_chunks_report"""
+    _fields_ = [("folds", C.c_uint32), ("reserved", C.c_uint32), ("live", C.c_uint64), ("count", C.c_uint64 * 5)]
 
 
 class SolveInfo(C.Structure):
@@ -411,6 +420,11 @@ def load_library() -> C.CDLL:
         lib.typlonk_srs_open_chunks_table.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.typlonk_open_chunks_dev.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, u64p, u8p, u64p]
         lib.typlonk_open_chunks_host.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.c_size_t, C.c_size_t, u64p, u8p, u64p]
+    if hasattr(lib, "typlonk_verify_chunks") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_verify_chunks.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u8p, C.c_size_t, u32p, u32p, u64p,
+                                              u64p, u8p, C.c_size_t, u8p, C.POINTER(ChunksReport)]
+        lib.typlonk_verify_chunks_challenge.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p]
     _lib = lib
     return lib
 
@@ -600,6 +614,19 @@ def srs_check_challenge(seed, length: int, g2s_xy) -> np.ndarray:
     g = np.ascontiguousarray(g2s_xy, dtype=np.uint64).reshape(24)
     out = np.zeros(4, dtype=np.uint64)
     rc = lib.typlonk_srs_check_challenge(_u8p(s), length, _u64p(g), _u64p(out))
+    if rc:
+        raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
+    return out
+
+
+def verify_chunks_challenge(seed, log_n: int, log_l: int, n_cells: int, n_commits: int, g2sl_xy) -> np.ndarray:
+    """typlonk_verify_chunks_challenge (host-only): the weight rho typlonk_verify_chunks derives from (seed, log_n, log_l, N, M,
+    [s^l]G2), 4 Montgomery limbs"""
+    lib = load_library()
+    s = _seed_arg(seed)
+    g = np.ascontiguousarray(g2sl_xy, dtype=np.uint64).reshape(24)
+    out = np.zeros(4, dtype=np.uint64)
+    rc = lib.typlonk_verify_chunks_challenge(_u8p(s), log_n, log_l, n_cells, n_commits, _u64p(g), _u64p(out))
     if rc:
         raise TyplonkError(rc, lib.typlonk_strerror(rc).decode())
     return out
@@ -823,6 +850,29 @@ class Context:
             ptrs = (C.c_void_p * max(count, 1))(*[c.ctypes.data for c in cos])
             self._chk(self.lib.typlonk_open_chunks_host(self.h, table, ptrs, m, count, _u64p(xy), _u8p(inf), evp))
         return (xy, inf, ev) if evals else (xy, inf)
+
+    def verify_chunks(self, sid: int, log_n: int, log_l: int, g2sl_xy, seed, commits, cell_commit, cell_coset, evals, proofs) -> dict:
+        """typlonk_verify_chunks: N cells of multi-proofs against M commitments in one call.  commits, proofs: (xy (k, 12), inf (k,))
+        as srs_download gives points; cell_commit, cell_coset: N indices; evals: (N, l, 4) u64 Montgomery, evals[i, t] =
+        f(w^(k_i + r t)); g2sl_xy: [s^l]G2, 24 limbs; seed: 32 bytes that whoever made the cells cannot have known.  Returns
+        {"status": (N,) uint8 of CELL_*, "folds", "live", "count": [cells per status]}; a bad cell is a status, not an exception."""
+        g = np.ascontiguousarray(g2sl_xy, dtype=np.uint64).reshape(24)
+        s = _seed_arg(seed)
+        cxy, cinf = _as_u64(commits[0], 12), np.ascontiguousarray(commits[1], dtype=np.uint8).reshape(-1)
+        pxy, pinf = _as_u64(proofs[0], 12), np.ascontiguousarray(proofs[1], dtype=np.uint8).reshape(-1)
+        cc = np.ascontiguousarray(cell_commit, dtype=np.uint32).reshape(-1)
+        ck = np.ascontiguousarray(cell_coset, dtype=np.uint32).reshape(-1)
+        n, m = pxy.shape[0], cxy.shape[0]
+        ev = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1)
+        if cinf.shape[0] != m or pinf.shape[0] != n or cc.shape[0] != n or ck.shape[0] != n or ev.shape[0] != (n << log_l) * 4:
+            raise ValueError("verify_chunks: the arrays of a call do not agree on N, M or l")
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        rep = ChunksReport()
+        u32 = C.POINTER(C.c_uint32)
+        self._chk(self.lib.typlonk_verify_chunks(self.h, sid, log_n, log_l, _u64p(g), _u8p(s), _u64p(cxy), _u8p(cinf), m,
+                                                 cc.ctypes.data_as(u32), ck.ctypes.data_as(u32), _u64p(ev), _u64p(pxy), _u8p(pinf), n,
+                                                 _u8p(status), C.byref(rep)))
+        return {"status": status[:n], "folds": rep.folds, "live": rep.live, "count": list(rep.count)}
 
     def g1_decompress(self, data, skip_subgroup: bool = False):
         """g1_decompress on this context's device"""

@@ -158,5 +158,25 @@ void launch_open_chunks_coeffs(const Fr* const* f, uint64_t m, uint64_t r, uint6
 void launch_open_chunks_pad(const Fr* const* f, uint64_t m, uint64_t n, uint64_t count, Fr* e, hipStream_t st);
 // out[p r l + k l + t] = ev[p r l + k + r t]; ev and out must not overlap
 void launch_open_chunks_evals(const Fr* ev, uint64_t r, uint64_t l, uint64_t count, Fr* out, hipStream_t st);
+// typlonk_verify_chunks (kernels: verify_chunks.hip; host: verify_chunks_host.hip; the fold's shape: verify_chunks_plan.hpp)
+// flags[i] = the reject class of record i (PC_OK, PC_NOT_ON_CURVE, PC_NOT_IN_SUBGROUP); clear: a failing record becomes the identity
+void launch_chunks_membership(uint32_t* pts, uint64_t n, uint8_t* flags, bool clear, hipStream_t st);
+// once per call: coset_a[i] = root_r^(cell_coset[i]) and twist[i] = w_inv^(cell_coset[i]), i < N
+void launch_chunks_cosets(const uint32_t* cell_coset, uint64_t N, const Fr& root_r, const Fr& w_inv, Fr* coset_a, Fr* twist, hipStream_t st);
+// The weights of the fold over the cells i of [lo, hi) with live[i] != 0 ("in"), pw[i] = rho^i: s_pi[i] = pw[i],
+// s_all[i] = pw[i] coset_a[i], scale[i] = pw[i] l_inv for a cell that is in and zero for any other; s_pi[N + c] = 0 and
+// s_all[N + c] = the sum of pw[i] over the cells in among order[first[c] .. first[c + 1]), c < M -- the cells of commitment c,
+// ascending: `order` is a permutation of [0, N) sorted by commitment, first[0] = 0, first[M] = N.  s_pi, s_all: N + M
+// elements; scale: N.
+void launch_chunks_weights(const Fr* pw, const Fr* coset_a, const uint32_t* order, const uint32_t* first, const uint8_t* live, uint64_t N,
+                           uint64_t M, uint64_t lo, uint64_t hi, const Fr& l_inv, Fr* s_pi, Fr* s_all, Fr* scale, hipStream_t st);
+// partial[b l + j] = sum over the cells i of workgroup b's strip of twist[i]^j sum_t scale[i] evals[i l + t] mu^(-j t), j < l =
+// 2^log_l, over the `cells` >= 1 cells from lo on; tw[j] = mu^(-j), j < max(l / 2, 1), mu the generator of the size-l domain;
+// pl = verify_chunks_plan(cells, log_l[, strip]); partial: pl.blocks * l elements
+struct VerifyChunksPlan;
+void launch_chunks_fold(const Fr* evals, const Fr* scale, const Fr* twist, const Fr* tw, uint64_t lo, uint64_t cells, uint32_t log_l,
+                        const VerifyChunksPlan& pl, Fr* partial, hipStream_t st);
+// out[j] = sum_{b < blocks} partial[b l + j] in that order, j < l
+void launch_chunks_fold_sum(const Fr* partial, uint64_t blocks, uint32_t l, Fr* out, hipStream_t st);
 
 }  // namespace ty

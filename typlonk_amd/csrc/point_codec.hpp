@@ -104,6 +104,17 @@ TY_HD bool g1_in_subgroup(const Fq30& x, const Fq30& y) {
     return pc_eq_mod(lx, q2.x) && pc_eq_mod(ly, q2.y);                 // X < 5.1, Y < 3.2 <= 6
 }
 
+// The reject class of a stored record with canonical coordinates: PC_OK for an identity and for an element of the group of
+// order r, else PC_NOT_ON_CURVE or PC_NOT_IN_SUBGROUP.  The body of srs_membership_kernel (srs_gen.hip) and of
+// chunks_membership_kernel (verify_chunks.hip).
+TY_HD uint32_t g1_record_class(const G1Affine& p) {
+    if (p.is_inf()) return PC_OK;
+    const Fq30 four = fq30_mulk_lazy<2>(fq30_mulk_lazy<2>(fq30_one()));                // < 4.1
+    const Fq30 rhs = fq30_add_lazy(fq30_mul(fq30_sqr(p.x), p.x), four);                // x^3 + 4 < 5.2
+    if (!pc_eq_mod(fq30_sqr(p.y), rhs)) return PC_NOT_ON_CURVE;
+    return g1_in_subgroup(p.x, p.y) ? PC_OK : PC_NOT_IN_SUBGROUP;
+}
+
 // The 48 bytes as the twelve 32-bit words a little-endian load of them gives (raw[k] = bytes 4k .. 4k + 3) -> the point in
 // the internal form, canonical, the identity as (0, 0).  A rejected encoding gives the identity and its class.
 TY_HD uint32_t g1_decode(const uint32_t (&raw)[12], bool check_subgroup, G1Affine& out) {

@@ -246,15 +246,9 @@ __global__ __launch_bounds__(64) void srs_membership_kernel(const uint32_t* pts,
     const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
     const bool live = i < n;
     const G1Affine p = ld_affine(pts, live ? i : n - 1);
-    uint32_t st = PC_OK;
-    if (live && !p.is_inf()) {
-        // (coordinates are canonical in every record: the generator, the decoder and the contribution write them so, and
-        // typlonk_srs_load reduces what it is given -- fq30_from_ark, msm_convert_points_kernel)
-        const Fq30 four = fq30_mulk_lazy<2>(fq30_mulk_lazy<2>(fq30_one()));                // < 4.1
-        const Fq30 rhs = fq30_add_lazy(fq30_mul(fq30_sqr(p.x), p.x), four);                // x^3 + 4 < 5.2
-        if (!pc_eq_mod(fq30_sqr(p.y), rhs)) st = PC_NOT_ON_CURVE;
-        else if (!g1_in_subgroup(p.x, p.y)) st = PC_NOT_IN_SUBGROUP;
-    }
+    // (coordinates are canonical in every record: the generator, the decoder and the contribution write them so, and
+    // typlonk_srs_load reduces what it is given -- fq30_from_ark, msm_convert_points_kernel)
+    const uint32_t st = live ? g1_record_class(p) : PC_OK;
     if (i == 0) {
         Fq30 gx, gy;
         g1_generator(gx, gy);

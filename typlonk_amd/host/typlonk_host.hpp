@@ -434,6 +434,18 @@ struct KzgChunkOpening {
     std::vector<Fr> ys;
 };
 
+// one cell of KzgScheme::verify_chunks: a multi-proof, the commitment it is claimed against (an index into the call's
+// commitments) and its coset
+struct KzgCell {
+    uint32_t commitment, coset;
+    KzgChunkOpening opening;
+};
+struct KzgCellVerdicts {
+    std::vector<uint8_t> status;    // TYPLONK_CELL_* per cell
+    typlonk_chunks_report report;
+    bool all_ok() const { return report.count[TYPLONK_CELL_OK] == status.size(); }
+};
+
 class KzgScheme {
    public:
     explicit KzgScheme(const Srs& srs) : srs_(srs) {}
@@ -490,6 +502,41 @@ class KzgScheme {
                 o.p.infinity = inf[p * r + k] != 0;
                 o.ys.assign(ys.begin() + (p * n + k * l), ys.begin() + (p * n + (k + 1) * l));
             }
+        return out;
+    }
+    // typlonk_verify_chunks: the cells (multi-proofs of open_chunks, in any order, from any number of polynomials) against
+    // `commitments`, over the domain of 2^log_n points cut into cosets of 2^log_l.  g2sl = [s^l]G2 for the s of this scheme's
+    // SRS, which an Srs does not hold; seed: 32 bytes that whoever made the cells cannot have known (typlonk.h).  A bad cell
+    // is its status, not an exception.
+    KzgCellVerdicts verify_chunks(uint32_t log_n, uint32_t log_l, const pairing::G2Affine& g2sl, const uint8_t seed[32],
+                                  const std::vector<KzgCommitment>& commitments, const std::vector<KzgCell>& cells) const {
+        const size_t N = cells.size(), M = commitments.size(), l = (size_t)1 << log_l;
+        uint64_t g2[24];
+        std::memcpy(g2, g2sl.x.a.v, 48);
+        std::memcpy(g2 + 6, g2sl.x.b.v, 48);
+        std::memcpy(g2 + 12, g2sl.y.a.v, 48);
+        std::memcpy(g2 + 18, g2sl.y.b.v, 48);
+        std::vector<uint64_t> cxy(M * 12 + 1), pxy(N * 12 + 1), ev(N * l * 4 + 1);   // (+ 1: data() is never null)
+        std::vector<uint8_t> cinf(M + 1), pinf(N + 1);
+        std::vector<uint32_t> cc(N + 1), ck(N + 1);
+        for (size_t c = 0; c < M; ++c) {
+            std::memcpy(&cxy[c * 12], commitments[c].p.xy, 96);
+            cinf[c] = commitments[c].p.infinity;
+        }
+        for (size_t i = 0; i < N; ++i) {
+            if (cells[i].opening.ys.size() != l) throw std::runtime_error("verify_chunks: a cell holds 2^log_l evaluations");
+            std::memcpy(&pxy[i * 12], cells[i].opening.p.xy, 96);
+            pinf[i] = cells[i].opening.p.infinity;
+            cc[i] = cells[i].commitment;
+            ck[i] = cells[i].coset;
+            std::memcpy(&ev[i * l * 4], cells[i].opening.ys[0].limbs(), l * 32);
+        }
+        KzgCellVerdicts out;
+        out.status.assign(N + 1, 0);
+        check(typlonk_verify_chunks(srs_.ctx().raw(), srs_.id(), log_n, log_l, g2, seed, cxy.data(), cinf.data(), M, cc.data(), ck.data(),
+                                    ev.data(), pxy.data(), pinf.data(), N, out.status.data(), &out.report),
+              srs_.ctx().raw());
+        out.status.resize(N);
         return out;
     }
     KzgCommitment identity() const { return commit(Poly::from_coefficients_vec({Fr(1)})); }
