@@ -6,7 +6,12 @@ of A, for l in {1, 2, 8, 64, 128, 1024} (a wavefront per cell up to 64, the work
 thread), N in {1, 2, one strip + 1, three strips with a ragged last one} for two named strip sizes and the plan's own -- every
 strip size gives the same words, a sum of field elements being a canonical residue --, sub-ranges inside one strip and across
 strips with dead cells inside, cosets 0 and r - 1, one cell twice, all-zero evaluations and evaluations of r - 1, every cell
-under one commitment and a commitment no cell names.  chunks_membership_kernel: one flag per record, and the failing records
+under one commitment and a commitment no cell names.  chunks_cosets_kernel past the r = 8 of those cases: r = 32 and 64, and
+log_n = 24 at l = 1, 8, 64, 1024 with coset indices 0, 1, 31, 32, 33, 2^16 - 1, 2^16, r/2, r - 1 and random ones -- w^(-k_i) and
+rho_i w^(l k_i) from Python's pow --, and pairs of cells that differ in one bit of k_i alone (bit 5, the top bit, one between).
+chunks_weights_kernel past four commitments: M = 1000 over N = 700 cells in no order (one commitment of 300 cells, 300 of one or
+two, runs of unnamed ones, ranges that cut the big one and that miss it), M = 65536 over N = 5, and M = N = 1.
+chunks_membership_kernel: one flag per record, and the failing records
 cleared, on the generator, an identity, the order-3 point (0, 2) and an off-curve record, over more than one wavefront."""
 import ctypes
 
@@ -15,7 +20,7 @@ import pytest
 
 import arith_cases as AC
 import verify_chunks_ref as VR
-from helpers import O, ROOT, fr_pack
+from helpers import O, ROOT, fr_pack, fr_unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -63,9 +68,13 @@ def _rand(rng, k):
 class Case:
     """N cells of l evaluations over M commitments, their device inputs, and the reference's outputs for any range"""
 
-    def __init__(self, log_l, N, M, seed, one_commitment=False):
-        self.log_l, self.log_n, self.N, self.M = log_l, log_l + LOG_R, N, M
-        l, r = 1 << log_l, 1 << LOG_R
+    def __init__(self, log_l, N, M, seed, one_commitment=False, log_r=LOG_R, cosets=None, commits=None, same_evals=()):
+        """cosets, commits: the cells' k_i and c_i, named by the caller (N of each) instead of drawn; same_evals: pairs (i, j),
+        cell j gets cell i's evaluations"""
+        self.log_l, self.log_n, self.N, self.M = log_l, log_l + log_r, N, M
+        l, r = 1 << log_l, 1 << log_r
+        assert cosets is None or (len(cosets) == N and all(0 <= k < r for k in cosets))
+        assert commits is None or (len(commits) == N and all(0 <= c < M for c in commits))
         rng = np.random.default_rng(seed)
         self.rho = _rand(rng, 1)[0]
         cells = []
@@ -75,11 +84,19 @@ class Case:
                 ys = [0] * l                                   # all-zero evaluations
             if i == 3:
                 ys = [R - 1] * l                               # full-range values
-            k = (0, r - 1)[i] if i < 2 and N > 2 else int(rng.integers(0, r))
-            c = 0 if one_commitment else int(rng.integers(0, M - 1)) if M > 1 else 0    # commitment M - 1: no cell names it
+            if cosets is not None:
+                k = cosets[i]
+            else:
+                k = (0, r - 1)[i] if i < 2 and N > 2 else int(rng.integers(0, r))
+            if commits is not None:
+                c = commits[i]
+            else:
+                c = 0 if one_commitment else int(rng.integers(0, M - 1)) if M > 1 else 0    # commitment M - 1: no cell names it
             cells.append((c, k, ys, 0))
-        if N >= 6:
+        if N >= 6 and cosets is None and commits is None:
             cells[5] = cells[4]                                # the same cell twice
+        for i, j in same_evals:
+            cells[j] = (cells[j][0], cells[j][1], cells[i][2], 0)
         self.cells = cells
         w = O.domain_root(self.log_n)
         mu_inv = pow(O.domain_root(log_l), -1, R)
@@ -164,6 +181,139 @@ def test_every_cell_under_one_commitment_and_one_unnamed(lib, log_l):
         _compare(got, want, (lo, hi))
         w = VR.weights(N, case.rho, lo, hi, live)
         assert (got["s_all"][N] == _words([sum(w) % R])[0]).all() and not got["s_all"][N + 1:].any()
+
+
+# ---- cosets past 32: every bit of k_i counts ------------------------------------------------------------------------------------
+# (log_l, log_r): log_n = 24, the widest domain the call admits, at l = 1, 8, 64, 1024 -- k_i up to 2^24 - 1 --, and r = 32 and
+# 64, the first sizes past the r = 8 of every case above
+COSET_SHAPES = [(0, 24), (3, 21), (6, 18), (10, 14), (3, 5), (3, 6)]
+
+
+def _ints(words) -> list[int]:
+    """(k, 8) uint32 Montgomery words -> canonical ints"""
+    return fr_unpack(np.ascontiguousarray(words).view(np.uint64).reshape(-1, 4))
+
+
+def _cosets(log_r, seed):
+    """0, 1, 31, 32, 33, 2^16 - 1, 2^16, r/2 and r - 1 where they are below r, and seeded random ones to make twelve"""
+    r = 1 << log_r
+    ks = [k for k in (0, 1, 31, 32, 33, (1 << 16) - 1, 1 << 16, r // 2, r - 1) if k < r]
+    rng = np.random.default_rng(seed)
+    return ks + [int(rng.integers(0, r)) for _ in range(12 - len(ks))]
+
+
+@pytest.mark.parametrize("log_l,log_r", COSET_SHAPES)
+def test_cosets_across_the_admitted_range(lib, log_l, log_r):
+    """twist[i] = w^(-k_i), s_all[i] = rho_i w^(l k_i) and the fold's coefficients, for coset indices that use every bit up to
+    log_r - 1, under the plan's own strip and a named one; the whole range, and a sub-range with dead cells"""
+    r, l = 1 << log_r, 1 << log_l
+    ks = _cosets(log_r, 0xC05E7 + 64 * log_l + log_r)
+    N = len(ks)
+    assert N == 12 and max(ks) == r - 1 and (log_r < 17 or (1 << 16) in ks)
+    case = Case(log_l, N, 3, 0xC05 + 64 * log_l + log_r, log_r=log_r, cosets=ks)
+    w = O.domain_root(log_l + log_r)
+    assert pow(w, 1 << (log_l + log_r - 1), R) == R - 1                      # w has order n exactly: w^k differ for k < n
+    for lo, hi, live in [(0, N, [1] * N), (1, N - 1, [0 if i in (4, 9) else 1 for i in range(N)])]:
+        want = case.expected(lo, hi, live)
+        rho_i = VR.weights(N, case.rho, lo, hi, live)
+        for strip in (0, 5):
+            got, _ = case.run(lib, lo, hi, live, strip)
+            assert _ints(got["twist"]) == [pow(w, -k, R) for k in ks], (lo, hi, strip)
+            assert _ints(got["s_all"][:N]) == [x * pow(w, l * k, R) % R for x, k in zip(rho_i, ks)], (lo, hi, strip)
+            _compare(got, want, (lo, hi, strip))
+
+
+@pytest.mark.parametrize("log_l,log_r", COSET_SHAPES)
+def test_cosets_that_differ_in_one_high_bit(lib, log_l, log_r):
+    """cells 2j and 2j + 1 carry the same evaluations under the same commitment and the cosets k and k XOR 2^b, for b = 5,
+    b = log_r - 1 and one bit between: their twists and their a_k = s_all / s_pi differ, and each is the reference's"""
+    r = 1 << log_r
+    bits = sorted({5, (5 + log_r - 1) // 2, log_r - 1} & set(range(log_r)))
+    assert bits[-1] == log_r - 1 and (5 in bits or log_r == 5)              # (r = 32 has no bit 5: its top bit is 4)
+    rng = np.random.default_rng(0xB17 + 64 * log_l + log_r)
+    ks = []
+    for b in bits:
+        k = int(rng.integers(0, r))
+        ks += [k, k ^ (1 << b)]
+    N = len(ks)
+    case = Case(log_l, N, 2, 0xB175 + 64 * log_l + log_r, log_r=log_r, cosets=ks, commits=[0] * N,
+                same_evals=[(2 * j, 2 * j + 1) for j in range(N // 2)])
+    live = [1] * N
+    got, _ = case.run(lib, 0, N, live, 0)
+    _compare(got, case.expected(0, N, live), (log_l, log_r))
+    rho_i, a = _ints(got["s_pi"][:N]), _ints(got["s_all"][:N])
+    a = [x * pow(y, -1, R) % R for x, y in zip(a, rho_i)]
+    assert a == [VR.coset_constant(k, log_l + log_r, log_l) for k in ks]
+    for j, b in enumerate(bits):
+        assert case.cells[2 * j][2] == case.cells[2 * j + 1][2]
+        assert (got["twist"][2 * j] != got["twist"][2 * j + 1]).any(), b
+        assert a[2 * j] != a[2 * j + 1], b
+
+
+# ---- many commitments ------------------------------------------------------------------------------------------------------------
+def _thousand_commitments(seed):
+    """(commits of 700 cells over M = 1000, the named commitments): commitment 7 holds 300 cells, 200 commitments hold one and 100
+    hold two; commitment 0 and 400 .. 519 are among the unnamed.  The first 100 cells name none of commitment 7's, the other 600
+    are commitment 7's and the rest in a seeded order: nothing is sorted by commitment."""
+    rng = np.random.default_rng(seed)
+    pool = [c for c in range(1, 1000) if c != 7 and not 400 <= c < 520]
+    named = [int(c) for c in rng.choice(pool, size=300, replace=False)]
+    if 999 not in named:
+        named[0] = 999                                                       # the last workgroup of the launch has a cell
+    others = named + named[:100]
+    rng.shuffle(others)
+    tail = [7] * 300 + others[100:]
+    rng.shuffle(tail)
+    return others[:100] + tail, set(named) | {7}
+
+
+@pytest.mark.parametrize("log_l", [0, 6])
+def test_a_thousand_commitments(lib, log_l):
+    """M = 1000 outnumbers N = 700.  w_c for a commitment of 300 cells (every thread of its workgroup strides), of one and of two
+    cells, and for runs of commitments no cell names; over the whole call, a range that cuts commitment 7's cells in two and one
+    that holds none of them, with dead cells everywhere: an unnamed commitment and one whose cells all lie outside the range or
+    are dead get zero"""
+    N, M = 700, 1000
+    commits, named = _thousand_commitments(0x7C0 + log_l)
+    assert len(commits) == N and commits.count(7) == 300 and 7 not in commits[:100] and commits != sorted(commits)
+    assert 0 not in named and not named & set(range(400, 520)) and len(named) == 301 and max(named) == 999
+    assert sum(commits.count(c) == 1 for c in named) == 200 and sum(commits.count(c) == 2 for c in named) == 100
+    assert sum(1 for c in named if c > 255) > 100
+    case = Case(log_l, N, M, 0x3E8 + log_l, commits=commits)
+    live = [0 if i % 7 == 3 else 1 for i in range(N)]
+    sevens = [i for i, c in enumerate(commits) if c == 7]
+    for lo, hi in [(0, N), (sevens[150], N), (3, 100)]:
+        got, _ = case.run(lib, lo, hi, live, 0)
+        _compare(got, case.expected(lo, hi, live), (lo, hi))
+        reached = {commits[i] for i in range(lo, hi) if live[i]}
+        assert (7 in reached) == (hi > 100) and len(reached) < M
+        for c in range(M):
+            assert got["s_all"][N + c].any() == (c in reached), (lo, hi, c)   # (a sum of distinct powers of rho is not zero)
+        assert not got["s_pi"][N:].any()
+    inside = [i for i in sevens if i >= sevens[150] and live[i]]
+    assert 0 < len(inside) < sum(live[i] for i in sevens)                     # the second range does cut commitment 7's cells
+
+
+def test_more_commitments_than_a_launch_has_cells(lib):
+    """M = 65536, the most the harness admits, and N = 5 cells that name commitments 0, 1, 32767 and 65535: one workgroup of
+    cells and 65536 of commitments"""
+    N, M = 5, 1 << 16
+    commits = [65535, 1, 0, 32767, 1]
+    for log_l in (0, 6):
+        case = Case(log_l, N, M, 0xFFFF + log_l, commits=commits)
+        for lo, hi, live in [(0, N, [1] * N), (1, 5, [1, 1, 1, 0, 1])]:
+            got, _ = case.run(lib, lo, hi, live, 0)
+            _compare(got, case.expected(lo, hi, live), (log_l, lo, hi))
+            reached = {commits[i] for i in range(lo, hi) if live[i]}
+            assert set(np.nonzero(got["s_all"][N:].any(axis=1))[0].tolist()) == reached
+
+
+def test_one_cell_one_commitment(lib):
+    for log_l in (0, 6):
+        case = Case(log_l, 1, 1, 0x111 + log_l)
+        got, _ = case.run(lib, 0, 1, [1], 0)
+        _compare(got, case.expected(0, 1, [1]), log_l)
+        assert (got["s_all"][1] == got["s_pi"][0]).all()                      # w_0 = rho^0
 
 
 def _record(pt) -> list[int]:

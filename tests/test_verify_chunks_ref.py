@@ -3,10 +3,15 @@ feature that needs no GPU: typlonk_verify_chunks_challenge against hashlib.
 
 The cells are the honest openings of tests/open_chunks_ref.py for a known s: A is the weighted sum of FK.interpolant's
 coefficients (the l^2 sum, where the reference itself goes through O.ntt); the honest cells satisfy the fold for every
-sub-range; each tampering the GPU tests use breaks it, and the bisection of `check` names exactly the tampered cells."""
+sub-range; each tampering the GPU tests use breaks it, and the bisection of `check` names exactly the tampered cells.
+
+What tests/test_gpu_verify_chunks_wide.py leans on, at (10, 3) and (8, 0) -- r = 128 and 256 cosets --: `check` accepts the cells
+made of tests/g1_wide_ref.py's closed forms, `cell_holds` rejects a coset moved in bit 5 and in its top bit, and `check` blames
+exactly the cells of a commitment that was replaced."""
 import numpy as np
 import pytest
 
+import g1_wide_ref as W
 import open_chunks_ref as FK
 import verify_chunks_ref as VR
 from helpers import O
@@ -117,6 +122,68 @@ def test_three_tamperings_at_once():
     status, folds = VR.check(bad, commitments, s, rho, log_n, log_l)
     assert status == [VR.BAD_PROOF if i in at else VR.OK for i in range(N)]
     assert folds <= 2 * 3 * (N - 1).bit_length() + 1
+
+
+WIDE = [(10, 3), (8, 0)]
+_wide = {}
+
+
+def wide(log_n, log_l):
+    """(cells, commitment scalars, s) of two random polynomials from g1_wide_ref's closed forms, cell (p, k) at position p r + k;
+    made once a shape"""
+    if (log_n, log_l) not in _wide:
+        n, l, r = FK.shape(log_n, log_l)
+        rng = np.random.default_rng(0x71DE + 64 * log_n + log_l)
+        s = _rand(rng, 1)[0]
+        cells, commitments = [], []
+        for p in range(2):
+            f = _rand(rng, n)
+            ys = W.unpack(W.chunk_major(W.domain_evaluations(f, log_n), log_n, log_l))
+            pis = W.open_chunks_scalars(f, s, log_n, log_l)
+            cells += [(p, k, ys[k * l:(k + 1) * l], pis[k]) for k in range(r)]
+            commitments.append(W.horner(f, s))
+        _wide[(log_n, log_l)] = (cells, commitments, s)
+    cells, commitments, s = _wide[(log_n, log_l)]
+    return list(cells), list(commitments), s
+
+
+@pytest.mark.parametrize("log_n,log_l", WIDE)
+def test_cells_of_the_closed_forms_are_accepted(log_n, log_l):
+    cells, commitments, s = wide(log_n, log_l)
+    N = len(cells)
+    assert all(VR.cell_holds(c, commitments, s, log_n, log_l) for c in cells)
+    order = list(np.random.default_rng(0x0DE).permutation(N))
+    assert VR.check([cells[i] for i in order], commitments, s, 0xABCDEF0123, log_n, log_l) == ([VR.OK] * N, 1)
+
+
+@pytest.mark.parametrize("log_n,log_l", WIDE)
+def test_a_coset_moved_in_one_high_bit_is_rejected(log_n, log_l):
+    cells, commitments, s = wide(log_n, log_l)
+    n, l, r = FK.shape(log_n, log_l)
+    for i in (0, 31, 32, r // 2, r - 1, r + 45, 2 * r - 1):
+        c, k, ys, pi = cells[i]
+        for bit in (32, r // 2):
+            assert not VR.cell_holds((c, k ^ bit, ys, pi), commitments, s, log_n, log_l), (i, bit)
+    at = r + 33
+    c, k, ys, pi = cells[at]
+    for bit in (32, r // 2):
+        bad = list(cells)
+        bad[at] = (c, k ^ bit, ys, pi)
+        status, folds = VR.check(bad, commitments, s, 0x5EED, log_n, log_l)
+        assert status == [VR.BAD_PROOF if i == at else VR.OK for i in range(len(cells))]
+        assert 1 < folds <= 2 * (len(cells) - 1).bit_length() + 1
+
+
+@pytest.mark.parametrize("log_n,log_l", WIDE)
+def test_a_wrong_commitment_blames_exactly_its_cells(log_n, log_l):
+    """64 cells, commitment 1's in runs of 8 among commitment 0's: C_1 + G where C_1 belongs fails them all and no other"""
+    cells, commitments, s = wide(log_n, log_l)
+    n, l, r = FK.shape(log_n, log_l)
+    sub = [cells[p * r + 4 * j + t] for j in range(0, 32, 8) for p in (0, 1) for t in range(8)]
+    status, folds = VR.check(sub, [commitments[0], (commitments[1] + 1) % R], s, 0xC0FFEE, log_n, log_l)
+    assert status == [VR.BAD_PROOF if c[0] == 1 else VR.OK for c in sub] and status.count(VR.BAD_PROOF) == 32
+    assert folds <= 2 * 32 * 6 + 1
+    assert VR.check(sub, commitments, s, 0xC0FFEE, log_n, log_l) == ([VR.OK] * 64, 1)
 
 
 def test_rho_reads_every_input():
