@@ -1094,6 +1094,60 @@ int typlonk_verify_chunks(typlonk_ctx* ctx, uint32_t srs_id, uint32_t log_n, uin
  * hashes the 24 limbs as given (no curve check); a null argument returns TYPLONK_ERR_INVALID_ARG. */
 int typlonk_verify_chunks_challenge(const uint8_t seed[32], uint32_t log_n, uint32_t log_l, uint64_t N, uint64_t M,
                                     const uint64_t g2sl_xy[24], uint64_t rho[4]);
+
+/* ---- Recovery of polynomials from a subset of their cells ------------------------------------------------------------------------
+ * n = 2^log_n, l = 2^log_l, r = n / l, w the generator of the size-n domain; coset k is {w^(k + r t) : t < l} and a cell holds
+ * the l evaluations on one coset in that order, as typlonk_open_chunks_* writes them and typlonk_verify_chunks reads them.
+ * The call is given K DISTINCT coset indices cosets[0 .. K) in any order -- the same for all `count` polynomials, a node
+ * lacking columns rather than single cells -- and per polynomial p its K cells, evals[((p K + i) l + t) 4 ..] =
+ * f_p(w^(cosets[i] + r t)) (Montgomery), and a degree bound m, 1 <= m <= K l.
+ * There is exactly one h_p of degree < K l through p's cells.  p is CONSISTENT iff h_p has no nonzero coefficient at an index
+ * j, m <= j < K l; then h_p is the only polynomial of degree < m through them and the call returns its m coefficients and/or
+ * its n evaluations.  With m = K l every input is consistent and the call is an interpolation.
+ *   status[p]   TYPLONK_RECOVER_OK            the outputs hold h_p
+ *               TYPLONK_RECOVER_BAD_EVAL      an evaluation of p is not a canonical residue (judged on the host before the upload)
+ *               TYPLONK_RECOVER_INCONSISTENT  no polynomial of degree < m takes p's values; first_excess[p] (may be NULL) = the
+ *                                             lowest j >= m with a nonzero coefficient of h_p, UINT64_MAX for any other status
+ *               A polynomial that is not OK gets zeros in every output that was given.  It is data, not an error of the call:
+ *               the other polynomials of the call are not affected.
+ *   outputs     at least one of the three:
+ *               coeffs_dev  `count` device buffers; coeffs_dev[p] receives m elements at offsets[p] (offsets NULL: at 0),
+ *                           stream-ordered on the context's stream: a following typlonk_open_chunks_dev on the same buffers
+ *                           makes the proofs
+ *               coeffs      count * m elements on the host
+ *               evals_out   count * n elements on the host, chunk-major: polynomial p, coset k, point t at ((p r + k) l + t) 4
+ *   report      K and r - K, and the polynomials per status
+ * The call blocks for the status.  It is not a collective and takes no SRS.
+ * Method: with Z the polynomial that vanishes on the r - K missing cosets (constant on each coset of the domain, of period r on
+ * the shifted domain g H), the values of h_p Z are known on the WHOLE domain -- the cell's times Z on a known coset, zero on a
+ * missing one -- and deg h_p Z < n, so one inverse transform gives h_p Z and a division on g H (a coset transform, a pointwise
+ * product with 1 / Z, the inverse coset transform) gives h_p: three batched transforms over the `count` vectors, a fourth for
+ * evals_out.  Z on the r cosets and at the r distinct points of g H is 2r plain products of r - K factors: quadratic in r, hence
+ * the bound on log_n - log_l.
+ * Temporaries, freed when the call returns, in bytes: 32 (count n + count K l + 4 r + 2 r S) for the work vectors, the staged
+ * cells, the constants and the S <= 64 partial products of the vanishing values; 4 (2 r - K) of indices (4 (r + 1) at K = r);
+ * 32 count m when coeffs or evals_out is given and 32 count n more when evals_out is; count (25 + 8 B) for the verdicts, B <= 256.
+ * Refusals, judged in this order (typlonk_last_error names the cause); a refused call leaves every output as it was:
+ *     TYPLONK_ERR_INVALID_ARG  a null ctx, cosets, evals, status or report; all three outputs null; a null entry of coeffs_dev
+ *     TYPLONK_ERR_DOMAIN       log_n outside 1..24; log_l >= log_n; log_n - log_l > 16
+ *     TYPLONK_ERR_LENGTH       K = 0, K > r, count = 0, m = 0, m > K l ("too few cells for this degree bound"), count n > 2^26
+ *     TYPLONK_ERR_RANGE        a coset >= r; offsets[p] / m outside coeffs_dev[p]
+ *     TYPLONK_ERR_INVALID_ARG  a coset named twice; the same range of one buffer given for two polynomials
+ *     TYPLONK_ERR_OOM          an allocation is refused
+ * Under typlonk_set_profiling the call records recover_vanish, recover_scatter, recover_interp, recover_divide, recover_finish
+ * and -- with evals_out -- recover_evals (ms, each with a wait for the device behind it). */
+#define TYPLONK_RECOVER_OK 0
+#define TYPLONK_RECOVER_BAD_EVAL 1
+#define TYPLONK_RECOVER_INCONSISTENT 2
+typedef struct typlonk_recover_report {
+    uint32_t known, missing;   /* K, r - K */
+    uint64_t count[3];         /* polynomials per status, indexed by TYPLONK_RECOVER_* */
+} typlonk_recover_report;
+int typlonk_recover_chunks(typlonk_ctx* ctx, uint32_t log_n, uint32_t log_l, size_t m, const uint32_t* cosets /* K */, size_t K,
+                           const uint64_t* evals /* count*K*l*4 */, size_t count, typlonk_buf* const* coeffs_dev /* NULL, or count */,
+                           const size_t* offsets /* NULL: 0 */, uint64_t* coeffs /* NULL, or count*m*4 */,
+                           uint64_t* evals_out /* NULL, or count*n*4 */, uint8_t* status /* count */,
+                           uint64_t* first_excess /* NULL, or count */, typlonk_recover_report* report);
 /* Host-only.  A field that is not a canonical residue, or a point that is not on the curve, returns
  * TYPLONK_ERR_INVALID_ARG (vk: also a g2s off the twist; log_n outside 1..24 returns TYPLONK_ERR_DOMAIN). */
 int typlonk_proof_compact_to_bytes(const typlonk_proof_compact* proof, uint8_t out[TYPLONK_PROOF_COMPACT_BYTES]);

@@ -19,6 +19,11 @@
                                   typlonk_verify_chunks (tests/test_gpu_verify_chunks_kernels.py) -- hipcc
   tests/cpp/verify_chunks_plan_host  host build of verify_chunks_plan, the launch shape of that fold, a program of its own
                                   (tests/test_verify_chunks_plan_host.py) -- g++
+  tests/cpp/libdevice_recover_chunks.so  device harness over recover_chunks.hip, the vanishing products, the scatter, the scale and the finish of
+                                  typlonk_recover_chunks, each alone (tests/test_gpu_recover_chunks_kernels.py) -- hipcc
+  tests/cpp/recover_chunks_plan_host[_san]  host build of recover_chunks_plan, every decision of that call (refusals, sizes, launch shapes), a
+                                  program of its own, once plain and once under the address and undefined-behaviour sanitizers
+                                  (tests/test_recover_chunks_plan_host.py) -- g++
   tests/cpp/ntt_plan_host         host build of ntt_plan, every decision of a batch of NTTs, a program of its own (tests/test_ntt_plan_host.py) -- g++
   tests/cpp/solve_plan_host[_san] host build of solve_plan, every decision of a witness solve, a program of its own, once plain and once under the
                                   address and undefined-behaviour sanitizers (tests/test_solve_plan_host.py) -- g++
@@ -66,7 +71,8 @@ def hipcc_path() -> str:
     return p
 
 
-HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip", "g1_fft.hip", "open_chunks.hip", "verify_chunks.hip", "verify_chunks_host.hip"]
+HIP_UNITS = ["ctx.hip", "ntt_host.hip", "msm_host.hip", "comm.hip", "prover.hip", "ntt_kernels.hip", "msm_sort.hip", "msm_accum.hip", "msm_reduce.hip", "srs_gen.hip", "quotient.hip", "plonk_ops.hip", "poly_eval.hip", "verify.hip", "prove_batch.hip", "point_codec.hip", "witness_check.hip", "perm_pairs.hip", "witness_solve.hip", "srs_check.hip", "g1_fft.hip", "open_chunks.hip", "verify_chunks.hip", "verify_chunks_host.hip",
+             "recover_chunks.hip", "recover_chunks_host.hip"]
 # per-unit flags (none in use).  -DFQ30_ASM_CHAIN for msm_accum.hip was measured: the micro-benchmark's mixed-add ceiling
 # rises 7.0 -> 7.3-7.5 G/s (profiles/r02_ubench2_chain.txt) but the real accumulation kernel does not move in a same-box
 # A/B (profiles/r02_ab_chain_ntt.txt: 1.85-1.90 ms either way), so the compiler-scheduled form stays.
@@ -258,6 +264,31 @@ def build_verify_chunks_plan_host(force: bool = False) -> str:
     return out
 
 
+def build_device_recover_chunks(force: bool = False) -> str:
+    """tests/cpp/libdevice_recover_chunks.so: csrc/harness/device_recover_chunks.hip, recover_chunks.hip compiled as a unit behind entry
+    points that run each kernel of typlonk_recover_chunks alone, the vanishing products with a named number of slices
+    (tests/test_gpu_recover_chunks_kernels.py).  Test-only and not linked into the shipped library; the flags are build_hip()'s."""
+    src = os.path.join(CSRC, "harness", "device_recover_chunks.hip")
+    out = os.path.join(ROOT, "tests", "cpp", "libdevice_recover_chunks.so")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(CSRC, "recover_chunks.hip")]
+    if force or _stale(out, [src] + deps):
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out])
+    return out
+
+
+def build_recover_chunks_plan_host(force: bool = False, sanitize: bool = False) -> str:
+    """tests/cpp/recover_chunks_plan_host: recover_chunks_refusal and recover_chunks_plan (csrc/recover_chunks_plan.hpp) as the host compiles
+    them, printing the verdict and the plan of each case it reads; sanitize: the same program as tests/cpp/recover_chunks_plan_host_san,
+    compiled with -fsanitize=address,undefined"""
+    src = os.path.join(ROOT, "tests", "cpp", "recover_chunks_plan_host.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "recover_chunks_plan_host_san" if sanitize else "recover_chunks_plan_host")
+    deps = [src, os.path.join(CSRC, "recover_chunks_plan.hpp")]
+    if force or _stale(out, deps):
+        extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+        _run(["g++", *extra, "-std=c++17", src, "-o", out])
+    return out
+
+
 def build_fq30_pair_host(force: bool = False) -> str:
     """tests/cpp/libfq30_pair_host.so: fq30_mul_pair / fq30_sqr_pair / fq30_mul2_add as the host compiles them"""
     src = os.path.join(ROOT, "tests", "cpp", "fq30_pair_host.cpp")
@@ -403,10 +434,10 @@ def build_host_tests(force: bool = False) -> list[str]:
                  "test_comm_host", "test_comm_ranks_host", "test_compact_ranks_host", "test_verify_host", "test_prove_batch_host", "test_compact_host",
                  "test_prove_batch_compact_host", "test_wire_host", "test_witness_check_host", "test_circuit_compile_host",
                  "test_circuit_pairs_host", "test_witness_solve_host", "test_witness_hints_host", "test_srs_check_host",
-                 "test_srs_lagrange_host", "test_open_all_host", "test_open_chunks_host", "test_verify_chunks_host"):
+                 "test_srs_lagrange_host", "test_open_all_host", "test_open_chunks_host", "test_verify_chunks_host", "test_recover_chunks_host"):
         src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
         out = os.path.join(ROOT, "tests", "cpp", name)
-        if name in ("test_witness_hints_host", "test_srs_check_host", "test_srs_lagrange_host", "test_open_all_host", "test_open_chunks_host", "test_verify_chunks_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
+        if name in ("test_witness_hints_host", "test_srs_check_host", "test_srs_lagrange_host", "test_open_all_host", "test_open_chunks_host", "test_verify_chunks_host", "test_recover_chunks_host") and not os.path.exists(src):   # (an earlier commit's tests/, as in build_all)
             continue
         if force or _stale(out, [src] + hdr):
             _run(["g++", "-O2", "-std=c++17", src, "-o", out, "-L", os.path.join(ROOT, "typlonk_amd"), "-ltyplonk_hip",
@@ -465,6 +496,10 @@ def build_all(force: bool = False) -> None:
     build_device_verify_chunks(force)
     if os.path.exists(os.path.join(ROOT, "tests", "cpp", "verify_chunks_plan_host.cpp")):
         build_verify_chunks_plan_host(force)
+    build_device_recover_chunks(force)
+    if os.path.exists(os.path.join(ROOT, "tests", "cpp", "recover_chunks_plan_host.cpp")):
+        build_recover_chunks_plan_host(force)
+        build_recover_chunks_plan_host(force, sanitize=True)
     build_host_tests(force)
     build_fake_rccl(force)
 

@@ -44,6 +44,7 @@ SYMBOLS = [
     "typlonk_srs_open_all_table", "typlonk_open_all_dev", "typlonk_open_all_host",
     "typlonk_srs_open_chunks_table", "typlonk_open_chunks_dev", "typlonk_open_chunks_host",
     "typlonk_verify_chunks", "typlonk_verify_chunks_challenge",
+    "typlonk_recover_chunks",
 ]
 VERIFY_PI_AS_PROVER = 1
 SRS_TO_LAGRANGE, SRS_FROM_LAGRANGE = 0, 1   # typlonk_srs_g1_ntt's direction
@@ -135,6 +136,15 @@ CELL_OK, CELL_BAD_EVAL, CELL_BAD_POINT, CELL_BAD_COMMITMENT, CELL_BAD_PROOF = 0,
 class ChunksReport(C.Structure):
     """typlonk_chunks_report"""
     _fields_ = [("folds", C.c_uint32), ("reserved", C.c_uint32), ("live", C.c_uint64), ("count", C.c_uint64 * 5)]
+
+
+RECOVER_OK, RECOVER_BAD_EVAL, RECOVER_INCONSISTENT = 0, 1, 2   # TYPLONK_RECOVER_* of typlonk_recover_chunks
+NO_EXCESS = 0xFFFFFFFFFFFFFFFF   # first_excess of a polynomial that is not RECOVER_INCONSISTENT
+
+
+class RecoverReport(C.Structure):
+    """typlonk_recover_report"""
+    _fields_ = [("known", C.c_uint32), ("missing", C.c_uint32), ("count", C.c_uint64 * 3)]
 
 
 class SolveInfo(C.Structure):
@@ -425,6 +435,10 @@ def load_library() -> C.CDLL:
         lib.typlonk_verify_chunks.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u8p, C.c_size_t, u32p, u32p, u64p,
                                               u64p, u8p, C.c_size_t, u8p, C.POINTER(ChunksReport)]
         lib.typlonk_verify_chunks_challenge.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p]
+    if hasattr(lib, "typlonk_recover_chunks") or not os.environ.get("TYPLONK_LIB_PATH"):   # (as typlonk_ntt_fr_batch_devptr above)
+        u32p = C.POINTER(C.c_uint32)
+        lib.typlonk_recover_chunks.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, u32p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp),
+                                               C.POINTER(C.c_size_t), u64p, u64p, u8p, u64p, C.POINTER(RecoverReport)]
     _lib = lib
     return lib
 
@@ -873,6 +887,43 @@ class Context:
                                                  cc.ctypes.data_as(u32), ck.ctypes.data_as(u32), _u64p(ev), _u64p(pxy), _u8p(pinf), n,
                                                  _u8p(status), C.byref(rep)))
         return {"status": status[:n], "folds": rep.folds, "live": rep.live, "count": list(rep.count)}
+
+    def recover_chunks(self, log_n: int, log_l: int, m: int, cosets, evals, out_bufs=None, offsets=None, want_coeffs: bool = True,
+                       want_evals: bool = True) -> dict:
+        """typlonk_recover_chunks: `count` polynomials of degree < m from K of the r = n / l cosets of their domain.  cosets: K distinct
+        indices in any order, the same for every polynomial; evals: (count, K, l, 4) u64 Montgomery, evals[p, i, t] =
+        f_p(w^(cosets[i] + r t)); out_bufs: None or `count` DeviceBuffers that receive the m coefficients at offsets[p] (default 0).
+        Returns {"status": (count,) uint8 of RECOVER_*, "first_excess": (count,) uint64 (NO_EXCESS unless RECOVER_INCONSISTENT), "known",
+        "missing", "count": [polynomials per status][, "coeffs": (count, m, 4)][, "evals": (count, r, l, 4), as open_chunks gives
+        them]}; a polynomial that is not RECOVER_OK gets zeros in every output and is a status, not an exception."""
+        ck = np.ascontiguousarray(cosets, dtype=np.uint32).reshape(-1)
+        k, l, n = ck.shape[0], 1 << log_l, 1 << log_n
+        ev = np.ascontiguousarray(evals, dtype=np.uint64)
+        if k == 0 or ev.size % (k * l * 4):
+            raise ValueError("recover_chunks: evals does not hold whole polynomials of K cells of l evaluations")
+        count = ev.size // (k * l * 4)
+        ev = ev.reshape(-1)
+        handles = offs = None
+        if out_bufs is not None:
+            out_bufs = list(out_bufs)
+            if len(out_bufs) != count or (offsets is not None and len(offsets) != count):
+                raise ValueError("recover_chunks: one buffer and one offset per polynomial")
+            handles = (C.c_void_p * max(count, 1))(*[b.handle for b in out_bufs])
+            offs = None if offsets is None else (C.c_size_t * max(count, 1))(*[int(o) for o in offsets])
+        co = np.zeros((count, m, 4), dtype=np.uint64) if want_coeffs else None
+        eo = np.zeros((count, n // l, l, 4), dtype=np.uint64) if want_evals else None
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        first = np.zeros(max(count, 1), dtype=np.uint64)
+        rep = RecoverReport()
+        self._chk(self.lib.typlonk_recover_chunks(self.h, log_n, log_l, m, ck.ctypes.data_as(C.POINTER(C.c_uint32)), k, _u64p(ev), count,
+                                                  handles, offs, _u64p(co) if want_coeffs else None, _u64p(eo) if want_evals else None,
+                                                  _u8p(status), _u64p(first), C.byref(rep)))
+        out = {"status": status[:count], "first_excess": first[:count], "known": rep.known, "missing": rep.missing, "count": list(rep.count)}
+        if want_coeffs:
+            out["coeffs"] = co
+        if want_evals:
+            out["evals"] = eo
+        return out
 
     def g1_decompress(self, data, skip_subgroup: bool = False):
         """g1_decompress on this context's device"""

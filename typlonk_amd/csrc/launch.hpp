@@ -178,5 +178,23 @@ void launch_chunks_fold(const Fr* evals, const Fr* scale, const Fr* twist, const
                         const VerifyChunksPlan& pl, Fr* partial, hipStream_t st);
 // out[j] = sum_{b < blocks} partial[b l + j] in that order, j < l
 void launch_chunks_fold_sum(const Fr* partial, uint64_t blocks, uint32_t l, Fr* out, hipStream_t st);
+// typlonk_recover_chunks (kernels: recover_chunks.hip; host: recover_chunks_host.hip; every shape: recover_chunks_plan.hpp)
+struct RecoverChunksPlan;
+// z[k] = prod_j (pw[k] - pw[missing_idx[j]]) and z[r + k] = prod_j (gl pw[k] - pw[missing_idx[j]]), k < r, j < pl.missing, cut
+// into pl.slices partial products (partial: pl.slices * 2r elements) that are multiplied in slice order; pw: r elements
+void launch_recover_vanish(const Fr* pw, const uint32_t* missing_idx, const Fr& gl, const RecoverChunksPlan& pl, Fr* partial, Fr* z, hipStream_t st);
+// z[i] <- 1 / z[i], i < cnt
+void launch_recover_invert(Fr* z, uint64_t cnt, hipStream_t st);
+// v[p n + k + r t] = cells[(p K + pos[k]) l + t] zd[k], or zero where pos[k] = RECOVER_NO_CELL; k < r, t < l, p < count
+void launch_recover_scatter(const Fr* cells, const uint32_t* pos, const Fr* zd, uint64_t K, uint32_t log_n, uint32_t log_l, uint64_t count,
+                            const RecoverChunksPlan& pl, Fr* v, hipStream_t st);
+// v[i] *= zc_inv[i & (r - 1)], i < total
+void launch_recover_scale(Fr* v, const Fr* zc_inv, uint64_t r, uint64_t total, hipStream_t st);
+// Per polynomial p < count of v (n apart): first = the lowest j of [m, m + pl.excess_len) with v[p n + j] != 0.  status = fixed[p]
+// when that is not zero, else TYPLONK_RECOVER_INCONSISTENT when there is such a j, else TYPLONK_RECOVER_OK.  verdict[p] = first for an
+// inconsistent polynomial and all ones otherwise, verdict[count + p] = status; dst[p][0, m) (dst or dst[p] NULL: none) and
+// out[p m, + m) (out NULL: none) = v[p n, + m) for an OK polynomial, zeros for any other.  mins: count * pl.excess_blocks words.
+void launch_recover_finish(const Fr* v, uint64_t n, uint64_t m, uint64_t count, const RecoverChunksPlan& pl, const uint8_t* fixed,
+                           Fr* const* dst, Fr* out, unsigned long long* mins, unsigned long long* verdict, hipStream_t st);
 
 }  // namespace ty

@@ -446,6 +446,17 @@ struct KzgCellVerdicts {
     bool all_ok() const { return report.count[TYPLONK_CELL_OK] == status.size(); }
 };
 
+// what KzgScheme::recover_chunks returns: per polynomial the recovered coefficients (m of them; all zero when its status is not
+// TYPLONK_RECOVER_OK), the status, and for an inconsistent one the lowest excess coefficient
+struct KzgRecovered {
+    std::vector<std::vector<Fr>> coeffs;
+    std::vector<uint8_t> status;          // TYPLONK_RECOVER_* per polynomial
+    std::vector<uint64_t> first_excess;   // UINT64_MAX unless TYPLONK_RECOVER_INCONSISTENT
+    typlonk_recover_report report;
+    bool all_ok() const { return report.count[TYPLONK_RECOVER_OK] == status.size(); }
+    Poly poly(size_t p) const { return Poly::from_coefficients_vec(coeffs[p]); }
+};
+
 class KzgScheme {
    public:
     explicit KzgScheme(const Srs& srs) : srs_(srs) {}
@@ -537,6 +548,35 @@ class KzgScheme {
                                     ev.data(), pxy.data(), pinf.data(), N, out.status.data(), &out.report),
               srs_.ctx().raw());
         out.status.resize(N);
+        return out;
+    }
+    // typlonk_recover_chunks: the polynomials of degree < m whose cells on the K distinct cosets `cosets` (any order, the same for
+    // every polynomial) are cells[p][i], the l = 2^log_l evaluations on coset cosets[i] in open_chunks' order.  It uses this
+    // scheme's context and no SRS.  A polynomial whose cells no polynomial of degree < m takes, or that holds a value that is no
+    // canonical residue, is its status, not an exception.
+    KzgRecovered recover_chunks(uint32_t log_n, uint32_t log_l, size_t m, const std::vector<uint32_t>& cosets,
+                                const std::vector<std::vector<std::vector<Fr>>>& cells) const {
+        const size_t count = cells.size(), K = cosets.size(), l = log_l < 32 ? (size_t)1 << log_l : 0;
+        std::vector<uint64_t> ev(count * K * l * 4 + 1), co(count * m * 4 + 1);   // (+ 1: data() is never null)
+        for (size_t p = 0; p < count; ++p) {
+            if (cells[p].size() != K) throw std::runtime_error("recover_chunks: one cell per named coset");
+            for (size_t i = 0; i < K; ++i) {
+                if (cells[p][i].size() != l) throw std::runtime_error("recover_chunks: a cell holds 2^log_l evaluations");
+                if (l) std::memcpy(&ev[(p * K + i) * l * 4], cells[p][i][0].limbs(), l * 32);
+            }
+        }
+        std::vector<uint32_t> ck(cosets);
+        ck.push_back(0);
+        KzgRecovered out;
+        out.status.assign(count + 1, 0);
+        out.first_excess.assign(count + 1, 0);
+        check(typlonk_recover_chunks(srs_.ctx().raw(), log_n, log_l, m, ck.data(), K, ev.data(), count, nullptr, nullptr, co.data(), nullptr,
+                                     out.status.data(), out.first_excess.data(), &out.report),
+              srs_.ctx().raw());
+        out.status.resize(count);
+        out.first_excess.resize(count);
+        out.coeffs.assign(count, std::vector<Fr>(m));
+        for (size_t p = 0; p < count; ++p) std::memcpy(out.coeffs[p][0].limbs(), &co[p * m * 4], m * 32);
         return out;
     }
     KzgCommitment identity() const { return commit(Poly::from_coefficients_vec({Fr(1)})); }
